@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - CDSegNet single-step inference throughput on MI355X (points/s/node).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 with no torch.distributed environment: bench.py launches its own N ranks (re-executes itself under
 torch.distributed.run on 127.0.0.1, like the reference's self-spawning launcher, pointcept/engines/launch.py:35-135);
@@ -12,11 +12,13 @@ A step = one SSI pass (DefaultSegmentorV2.inference: PTv3 dual backbone + cross-
 ~120k voxels each - sizes 103k..137k, mean 120k - 6-ch features, 20 classes, IEEE-half trunk + fp32 heads by default), inputs already resident in HBM.
 Scenes are independent units: every rank runs its own scenes, no data-path collective ("scaling": "weak").  Every lane
 (HIP stream) gets one collated forward of 8 scenes (the reference's collate_fn batching), three forwards are in flight.
-`value` counts all points of all scenes; `single_scene_latency_ms` is the one-scene-at-a-time (bs = 1) latency, the
-median of 9 synchronised calls.
+`value` counts all points of all scenes; `single_scene_latency_ms` (--full) is the one-scene-at-a-time (bs = 1) latency,
+the median of 9 synchronised calls.
 RCCL is used once to broadcast the weights from rank 0 and for the final timing / counter reductions.
 
-Prints ONE JSON line on rank 0.  `roofline` (window attention, the north-star kernel) and `roofline_conv` (all k = 3 sparse
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps, writes the last step's outputs if
+--dump-outputs is given and prints the headline (`value`, `ms_per_step`, `config`).  Everything else comes with --full,
+after the timed region: `roofline` (window attention, the north-star kernel) and `roofline_conv` (all k = 3 sparse
 convs of the forward) are timed with HIP events around every launch ON THE LAUNCH STREAM, in a pass
 right after the timed region that replays the timed configuration's own forward (the same 8 collated scenes) with
 nothing else on the GPU; `cpu_baseline` is the CPU oracle on the host cores.
@@ -43,6 +45,8 @@ if ROOT not in sys.path:
 
 PEAK_TFLOPS = {"bf16": 2500.0, "bf16+head": 2500.0, "fp16": 2500.0, "fp16+head": 2500.0, "fp32": 157.3}  # dense MFMA peaks, MI355X_MICROARCH.md
 PEAK_HBM_GBS = 8000.0
+DUMP_BYTES = 48 << 20  # --dump-outputs: cap of the logits written (the row numbers of a sample add a tenth of it)
+SCENE_WORKERS = 8  # processes that generate the bench scenes (per node, split among its ranks)
 CPU_THREADS = 16  # fastest of {8, 16, 32} torch threads on the GPU box host at the baseline's own 120 k-voxel scene (tools/cpu_sweep.py, profiles/r05_cpu_sweep.txt; r02: 24 k voxels)
 
 
@@ -91,8 +95,22 @@ def parse():
                          "every rank runs its share through inference_many (--scenes-per-forward collated per forward), the "
                          "per-class counters are all-reduced and the mIoU printed; a step = all S scenes")
     ap.add_argument("--dry-run", action="store_true",
-                    help="launcher / process-group plumbing only (no model, gloo when there is no GPU): what the CPU test runs")
-    return ap.parse_args()
+                    help="launcher / process-group plumbing only (no model, gloo when the node has fewer GPUs than ranks): what the CPU test runs")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline, after the timed region: the kernel-level pass (rooflines, bs = 1 "
+                         "latency, paper protocol, half saturation, the bfloat16 build), the round-5 setting, the 16-bit "
+                         "agreement and exact-fp32 legs, the eval counters, the CPU baseline and its parity check (the --no-* "
+                         "switches above trim a --full run).  Without it a run sets up, warms up, times --steps steps and "
+                         "prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's scenes) as DIR/<name>.npy: "
+                         "seg_logits.npy (float32 rows of all scenes in scene order, or a fixed seeded sample of them when "
+                         "they exceed %d MiB; seg_logits_rows.npy then holds the row numbers, float64) and "
+                         "scene_offset.npy (float64 cumulative rows per scene)" % (DUMP_BYTES >> 20))
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _free_port():
@@ -112,23 +130,55 @@ def self_launch(args):
     return subprocess.call(cmd, env=env)
 
 
-def make_scenes(args, rank, count):
-    """`count` distinct scenes of this rank: different seeds AND sizes (mean = --points), so ragged patches, LPT
-    sharding and the allocator see what a real scene list gives them."""
+def _scene(spec):
+    """One bench scene from its (dataset, seed, size, robust) spec (a module-level function: the pool's workers call it)."""
     from cdsegnet_amd import synth
-    scenes = []
+    dataset, seed, n, robust = spec
+    sc = synth.lidar_scene(seed, n) if dataset == "nuscenes" else synth.room_scene(seed, n)
+    if robust:
+        sc = synth.perturb_scene(sc, seed=seed, sigma=0.05, drop=0.5, voxel=0.05 if dataset == "nuscenes" else 0.02)
+    return sc
+
+
+def make_scenes(args, rank, count, local_world=1):
+    """`count` distinct scenes of this rank: different seeds AND sizes (mean = --points), so ragged patches, LPT
+    sharding and the allocator see what a real scene list gives them.  Generated by a pool of fresh processes (every
+    scene is a function of its seed and size alone, so the list is the same as one process would make)."""
+    specs = []
     for i in range(count):
-        seed = 1000 * rank + i
         if args.dataset == "nuscenes":
             n = int(round(args.points * (1.0 + 0.25 * ((i + 0.5) / count - 0.5))))
-            sc = synth.lidar_scene(seed, n)
         else:
             n = int(round(args.points * (1.0 + 0.3 * ((i + 0.5) / count - 0.5))))  # 0.85 .. 1.15 x, mean 1.0
-            sc = synth.room_scene(seed, n)
-        if args.robust:
-            sc = synth.perturb_scene(sc, seed=seed, sigma=0.05, drop=0.5, voxel=0.05 if args.dataset == "nuscenes" else 0.02)
-        scenes.append(sc)
-    return scenes
+        specs.append((args.dataset, 1000 * rank + i, n, args.robust))
+    workers = min(count, max(1, SCENE_WORKERS // max(1, local_world)))
+    if workers <= 1:
+        return [_scene(s) for s in specs]
+    import multiprocessing
+    from concurrent.futures import ProcessPoolExecutor
+    with ProcessPoolExecutor(workers, mp_context=multiprocessing.get_context("spawn")) as ex:
+        return list(ex.map(_scene, specs))
+
+
+def dump_outputs(path, outs, seed=0):
+    """--dump-outputs: the output dicts of the last timed step (one per scene, seg_logits (n_i, classes) fp32 on the
+    device) as <path>/seg_logits.npy, all scenes' rows in scene order - or, beyond DUMP_BYTES, a sample of rows drawn
+    with a fixed seed (same arguments, same rows), whose row numbers go to <path>/seg_logits_rows.npy - and the
+    cumulative rows per scene as <path>/scene_offset.npy."""
+    os.makedirs(path, exist_ok=True)
+    logits = torch.cat([o["seg_logits"] for o in outs], 0).float()
+    rows, classes = logits.shape
+    offset = np.cumsum([o["seg_logits"].shape[0] for o in outs]).astype(np.float64)
+    keep = DUMP_BYTES // (4 * max(1, classes))
+    rows_file = os.path.join(path, "seg_logits_rows.npy")
+    if rows > keep:
+        pick = np.sort(np.random.default_rng(seed).choice(rows, size=keep, replace=False))
+        logits = logits.index_select(0, torch.from_numpy(pick).to(logits.device))
+        np.save(rows_file, pick.astype(np.float64))
+    elif os.path.exists(rows_file):  # (left by an earlier, larger run into the same directory)
+        os.remove(rows_file)
+    np.save(os.path.join(path, "seg_logits.npy"), logits.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "scene_offset.npy"), offset)
 
 
 def shard_sizes(args):
@@ -257,8 +307,9 @@ def paper_protocol(args, model, cfg, dev, rank, world, dist):
     if world > 1:
         dist.barrier()
     t0 = time.perf_counter()
+    out = None
     for d in dicts:  # the reference's input dict (no offset_host hint): every host sync of the call is inside
-        model.inference(dict(d), eval=False)
+        out = model.inference(dict(d), eval=False)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -267,6 +318,8 @@ def paper_protocol(args, model, cfg, dev, rank, world, dist):
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
         dist.all_reduce(tp, op=dist.ReduceOp.SUM)
+    if rank == 0 and args.dump_outputs and out is not None:  # a step of this protocol is one scene
+        dump_outputs(args.dump_outputs, [out])
     if rank == 0:
         sec = float(el.item())
         print(json.dumps({
@@ -316,6 +369,8 @@ def shard_mode(args, model, cfg, dev, rank, world, dist):
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if rank == 0 and args.dump_outputs and outs:
+        dump_outputs(args.dump_outputs, outs)
     counts = torch.zeros(3, cfg["num_classes"], dtype=torch.int64, device=dev)
     for sc, o in zip(scenes, outs or []):
         counts += cdist.confusion_counts(o["seg_logits"].argmax(1), torch.as_tensor(sc["segment"]).to(dev), cfg["num_classes"])
@@ -358,9 +413,11 @@ def main():
     if world > 1:
         import torch.distributed as dist
     if args.dry_run:
-        dev = torch.device("cuda", local_rank) if have_gpu else torch.device("cpu")
+        # RCCL when every rank of the node has a GPU of its own, else gloo on the CPU (e.g. two ranks on a one-GPU box)
+        on_gpu = have_gpu and torch.cuda.device_count() >= int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
+        dev = torch.device("cuda", local_rank) if on_gpu else torch.device("cpu")
         if world > 1:
-            dist.init_process_group("nccl" if have_gpu else "gloo", **(dict(device_id=dev) if have_gpu else {}))
+            dist.init_process_group("nccl" if on_gpu else "gloo", **(dict(device_id=dev) if on_gpu else {}))
             dist.barrier()
         t = torch.tensor([1.0 + rank], dtype=torch.float64, device=dev)
         ones = torch.ones(1, dtype=torch.int64, device=dev)
@@ -386,7 +443,7 @@ def main():
             dist.all_reduce(ones, op=dist.ReduceOp.SUM)
         if rank == 0:
             print(json.dumps({"dry_run": True, "n_gpus": world, "ranks_seen": int(ones.item()), "max_over_ranks": float(t.item()),
-                              "backend": "nccl" if have_gpu else "gloo", **extra}))
+                              "backend": "nccl" if on_gpu else "gloo", **extra}))
         if world > 1:
             dist.destroy_process_group()
         return
@@ -429,7 +486,7 @@ def main():
     if args.shard:
         return shard_mode(args, model, cfg, dev, rank, world, dist)
     scenes_per_step = args.scenes_per_forward * args.lanes
-    scenes = make_scenes(args, rank, scenes_per_step)
+    scenes = make_scenes(args, rank, scenes_per_step, local_world)
     dicts = []
     for sc in scenes:
         d = {k: torch.as_tensor(sc[k]).to(dev) for k in ("coord", "grid_coord", "feat", "offset")}
@@ -447,7 +504,7 @@ def main():
             out = model.inference_many([dict(d) for d in dicts], lanes=args.lanes, batch=args.scenes_per_forward)
         return out
 
-    timer = not args.no_kernel_timer
+    timer = args.full and not args.no_kernel_timer
     if args.serial:
         model.engine().fork_stage = None
     out = None
@@ -467,12 +524,14 @@ def main():
     last = out[-1]["seg_logits"]
     assert torch.isfinite(last).all()
     hbm_peak_gb = torch.cuda.max_memory_allocated(dev) / 2 ** 30  # (allocator high-water mark through warm-up + timed region)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     # rounds 1 - 5 timed 8 scenes per forward x 3 lanes (24 scenes per step); round 6 collates 24 per forward (the deep stages'
     # launches are three times as full, profiles/r06_lanes_sweep.txt).  The old setting on this step's first 24 scenes, right
     # after the timed region, so that the line stays comparable with the earlier rounds' `value`
     r5cfg = None
     if (rank == 0 and world == 1 and (args.scenes_per_forward, args.lanes) != (8, 3) and len(dicts) >= 24
-            and not args.no_kernel_timer):  # (profiling / A-B runs pass --no-kernel-timer: the timed configuration only)
+            and timer):  # (profiling / A-B runs pass --no-kernel-timer: the timed configuration only)
         sub24 = dicts[:24]
         k5 = max(3, args.steps // 2)
         for _ in range(2):
@@ -602,12 +661,12 @@ def main():
 
     # ---- 16-bit accuracy on a bench scene: same draws through the exact-fp32 HIP path (rank 0)
     agreement = None
-    if rank == 0 and low and not args.no_agreement:
+    if rank == 0 and low and args.full and not args.no_agreement:
         agreement = agreement_leg(model, dicts[0], sizes[0], cfg, args.precision)
         model.precision = args.precision
         model.noise_source = "device"
     parity_mode = None
-    if rank == 0 and low and not args.no_agreement:
+    if rank == 0 and low and args.full and not args.no_agreement:
         # throughput of the exact-fp32 mode (inside north_star's 1e-3 logit bound): 8 collated scenes per forward, two
         # forwards in flight (round 6; 4 x 1 before: 9.3 -> 10.9 M points/s, gpurun_out/r06ae_fp32_sweep.txt), the same scenes
         model.precision = "fp32"
@@ -648,8 +707,10 @@ def main():
 
     # per-class intersection/union/target counters of the last scene: the per-scene record the reference
     # gathers over gloo (test.py:374) - here one RCCL all-reduce (random-init weights: the value is meaningless)
-    counts = cdist.confusion_counts(last.argmax(1), torch.as_tensor(scenes[-1]["segment"]).to(dev), last.shape[1])
-    cdist.reduce_counts(counts)
+    counts = None
+    if args.full:
+        counts = cdist.confusion_counts(last.argmax(1), torch.as_tensor(scenes[-1]["segment"]).to(dev), last.shape[1])
+        cdist.reduce_counts(counts)
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     pts = torch.tensor([pts_per_step], dtype=torch.int64, device=dev)
     if world > 1:
@@ -833,9 +894,10 @@ def main():
             res["agreement_vs_fp32"] = agreement
         if parity_mode:
             res["parity_mode"] = parity_mode
-        m = cdist.metrics(counts)
-        res["eval_counters"] = {"mIoU_random_init": m["mIoU"], "points_counted": int(counts[2].sum())}
-        if args.cpu_baseline and world == 1:
+        if counts is not None:
+            m = cdist.metrics(counts)
+            res["eval_counters"] = {"mIoU_random_init": m["mIoU"], "points_counted": int(counts[2].sum())}
+        if args.full and args.cpu_baseline and world == 1:
             res["cpu_baseline"], cpu_case = cpu_baseline(cfg, sd, args.cpu_points, args.dataset, args.cpu_threads)
             if low:
                 live = parity_vs_cpu(model, dev, cpu_case, ["fp32", "fp32x3", args.precision])

@@ -87,6 +87,8 @@ def test_two_ranks_gloo(tmp_path):
     from tests import emu_ops
     old = engine_mod.ops
     engine_mod.ops = emu_ops
+    threads = torch.get_num_threads()
+    torch.set_num_threads(2)  # the ranks' thread count: CPU GEMM results depend on it, and the comparison is bit for bit
     try:
         cfg = configs.mini_config()
         model = build_model(cfg).eval()
@@ -101,6 +103,7 @@ def test_two_ranks_gloo(tmp_path):
                 assert np.array_equal(out, r[f"logits{int(i)}"])
     finally:
         engine_mod.ops = old
+        torch.set_num_threads(threads)
 
 
 def _bcast_worker(rank, world, port, out_dir):

@@ -8,7 +8,7 @@ import sys, runpy
 import cdsegnet_amd.ops as o
 if '$v' == 'off':
     o.pool_fused_ok = lambda *a: False
-sys.argv = ['bench.py', '--steps', '10', '--warmup', '3', '--no-cpu-baseline', '--no-agreement']
+sys.argv = ['bench.py', '--full', '--steps', '10', '--warmup', '3', '--no-cpu-baseline', '--no-agreement']
 runpy.run_path('bench.py', run_name='__main__')" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
