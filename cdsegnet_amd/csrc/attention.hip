@@ -500,8 +500,10 @@ __global__ __launch_bounds__(64 * WAVES, 4) void attn_bf16_kernel(AttnP p) {
     // shift registers per query tile - rounds 2 - 5 subtracted the Cauchy-Schwarz bound |q'| max |k|), and the denominator
     // that falls out of the same MFMA says whether it was legitimate: a row whose denominator left [1e-30, 1e30] (an exp2 that
     // overflowed shows up as inf / NaN there, a row of underflows as 0) is redone with the exact row maximum below
-    // (wave-uniform branch; tests/test_gpu_ops.py::test_attention_softmax_is_shift_safe drives it).  Relative precision is
-    // that of the shifted form: the terms only differ by a power of two.
+    // (wave-uniform branch).  A denominator in range does not bound the numerator: sum_j P~_j v_j leaves fp32 once
+    // |v| den > FLT_MAX (|v| > 3.4e8 at den = 1e30 - a bfloat16 V can be that large), so a lane whose own outputs are not
+    // finite votes for the redo as well.  tests/test_gpu_attention_range.py drives both votes, in both block shapes and
+    // both builds.  Relative precision is that of the shifted form: the terms only differ by a power of two.
     // everything outside the key loops (prologue, normalise + store, the next tile's set-up) runs at raised priority:
     // it is a few hundred instructions that otherwise queue behind the older waves' key loops on the same SIMD
     if (ATTN_PRIO_OUTSIDE) __builtin_amdgcn_s_setprio(0);
@@ -517,7 +519,10 @@ __global__ __launch_bounds__(64 * WAVES, 4) void attn_bf16_kernel(AttnP p) {
 #endif
     {
       const float den = __shfl(o[8], ql, 64);
-      const bool redo = qvalid && !(den >= 1e-30f && den <= 1e30f);
+      bool fin = true;
+#pragma unroll
+      for (int r = 0; r < 8; ++r) fin = fin && __builtin_isfinite(o[r]);
+      const bool redo = qvalid && (!(den >= 1e-30f && den <= 1e30f) || !fin);
       if (__any(redo)) {
         // ---- exact pass 1: row max of S'^T = K Q'^T (lane (q,h) sees keys (r&3) + 8*(r>>2) + 4h of each tile)
         float m0 = -INFINITY;
@@ -693,7 +698,8 @@ __global__ __launch_bounds__(ATTN_THREADS) void attn_f32_kernel(AttnP p) {
 //   P V      P~ = exp2(s) (unshifted single pass, see attn_bf16_kernel) and v as BFLOAT16 pairs (fp32's exponent range; 16
 //            significant bits): O^T = V1^T P1^T + V2^T P1^T + V1^T P2^T; the row of ones that yields the denominator sits
 //            behind V1 only (behind V2: zeros), so the denominator is sum(p1 + p2)
-// Rows whose denominator left [1e-30, 1e30] are redone with the exact row max.  Same block -> (patch, head, slice) map and the
+// Rows whose denominator left [1e-30, 1e30], or whose outputs are not finite (a numerator past FLT_MAX: |v| den > FLT_MAX), are
+// redone with the exact row max (tests/test_gpu_attention_range.py).  Same block -> (patch, head, slice) map and the
 // same LDS images as the 16-bit kernel (K planes with the source-side half swap, V planes row-major for ds_read_b64_tr_b16);
 // four 32 KB planes = one block of 8 waves per CU, two score tiles in flight per wave.
 constexpr int X3_KH = 0, X3_KL = KV_STAGE, X3_V1 = 2 * KV_STAGE, X3_V2 = 3 * KV_STAGE;
@@ -883,7 +889,10 @@ __global__ __launch_bounds__(X3_THREADS) void attn_x3_kernel(AttnP p) {
     f32x16_t o = exp_pv_pass(std::false_type{}, 0.f);
     {
       const float den = __shfl(o[8], ql, 64);
-      const bool redo = qvalid && !(den >= 1e-30f && den <= 1e30f);
+      bool fin = true;
+#pragma unroll
+      for (int r = 0; r < 8; ++r) fin = fin && __builtin_isfinite(o[r]);
+      const bool redo = qvalid && (!(den >= 1e-30f && den <= 1e30f) || !fin);
       if (__any(redo)) {  // exact row max, then the shifted pass (wave-uniform, rare)
         float m0 = -INFINITY;
         const char* kp = k_lane;

@@ -1034,8 +1034,10 @@ def test_batched_plan_kernels_equal_single_calls(ops, name):
 
 @LPS
 def test_attention_bf16_loose_score_bound_falls_back_to_exact_max(ops, lp):
-    """The bf16 kernel takes m_i = |q_i| max_j |k_j| (Cauchy-Schwarz) instead of the row max; rows where that bound is
-    more than 2^60 above the scores are redone with the exact max.  Build exactly that: huge, nearly orthogonal q / k."""
+    """Huge, nearly orthogonal q / k (|q| |k| * scale ~ 900, scores O(10)) on a two-patch launch whose second patch is padded.
+    Written for the Cauchy-Schwarz shift of rounds 2 - 5 (m_i = |q_i| max_j |k_j|, loose by 2^60 here); the unshifted
+    kernel of round 6 takes no redo on these rows (the denominator stays inside [1e-30, 1e30]), so this now checks large
+    operands whose products cancel.  The redo itself is driven by tests/test_gpu_attention_range.py."""
     g = torch.Generator().manual_seed(3)
     n, H = 1500, 2
     C = 16 * H
