@@ -1,14 +1,15 @@
-// Training path, first slices: the backward of a PTv3 Block (attention core, LayerNorm, GELU; weight / bias gradients of
-// the Linears and of the submanifold conv), exact fp32.
+// Training path: the backward of a PTv3 Block (attention core, LayerNorm, GELU; weight / bias gradients of the Linears and
+// of the submanifold conv).
 //
 // ref: pointcept/models/default.py:424-493 (training forward), engines/train.py:216-271 (loss.backward()); what
 //      autograd differentiates here: point_transformer_v3m1_base.py:246-296 (SerializedAttention core),
 //      :399-428 (Block: x += proj(attn); x += fc2(GELU(fc1(LN(x))))).
 //
-// These are the fp32 kernels of the 1e-3 parity mode's backward, written to pin the arithmetic and the index plumbing
-// (slot plan, padding duplicates) against the reference's autograd.  The attention core and the weight gradients run on
-// the fp32 matrix pipe (v_mfma_f32_16x16x4_f32); LayerNorm / GELU are row kernels.  The 16-bit recompute-P form of
-// attn_bf16_kernel's backward (what an AMP training step would run) is the next step.
+// The fp32 kernels are those of the 1e-3 parity mode's backward, written to pin the arithmetic and the index plumbing
+// (slot plan, padding duplicates) against the reference's autograd: the attention core and the weight gradients run on
+// the fp32 matrix pipe (v_mfma_f32_16x16x4_f32); LayerNorm / GELU are row kernels.  The attention core also exists in the
+// build's 16-bit type (attn_bwd16_*_kernel below, v_mfma_f32_32x32x16_{bf16,f16}): the recompute-P backward of
+// attn_bf16_kernel, what the reference's flash-attention path computes in a training step.
 #include <mutex>
 
 #include "common.h"
@@ -259,6 +260,270 @@ __global__ __launch_bounds__(BW_WAVES * 64) void attn_bwd_kv_mfma_kernel(AttnBwd
 constexpr int BW_Q_LDS = 2 * BW_MAXL * 64;
 constexpr int BW_KV_LDS = 2 * BW_MAXL * 64 + 3 * BW_MAXL * 4;
 
+// ------------------------------------------------------------------------------------ 16-bit attention backward
+// The recompute-P backward of attn_bf16_kernel on the 16-bit matrix pipe (v_mfma_f32_32x32x16_{bf16,f16}).  The function
+// differentiated is the one that kernel computes: q' = q * fp32(scale * log2 e) rounded ONCE to the 16-bit type (treated
+// as the identity in the chain rule), s' = q'.k, P = exp2(s' - m') / l.  Rounding points are flash-attention's: P and
+// dS = P o (dP - D) are rounded to the 16-bit type as MFMA operands and nowhere else; the statistics (m', l, D) and every
+// accumulator are fp32.  Unlike the forward's loop this one always subtracts the exact row maximum, so rows with |s'| of
+// hundreds come out finite.  dO is never clamped and dS is converted WITHOUT saturation (half build): a scaled gradient
+// beyond half's range reaches dq / dk / dv as inf / NaN, which is what a GradScaler looks for.
+// Same two-kernel split and slot plan as the fp32 form, 32 x 32 (query, key) tiles, 8 waves, two blocks per CU; blockIdx.z
+// deals a patch-head's tiles to 1, 2 or 4 blocks (results differ by the order of the fp32 atomics only):
+//   q kernel  (K, V row-major in LDS, 32 KB each; a wave owns 32-query tiles): S'^T = K Q'^T and dP^T = V dO^T have a query
+//             per lane column and 16 keys per lane.  Sweep 1: online (m', l, sum e dP) -> M = m' + log2 l and D per query
+//             (P = exp2(s' - M): the normalisation costs nothing per score).  Sweep 2: -M is the MFMA's C operand, dS^T goes
+//             from the accumulator registers into dQ^T += K^T dS^T as the B operand (k-slots <-> keys as in the forward's
+//             P V product) and K^T is two ds_read_b64_tr_b16 of the row-major K;
+//   kv kernel (Q', dO row-major in LDS, -M and D per query; a wave owns 32-key tiles): S' - M = Q' K^T + (-M) and
+//             dP = dO V^T with a key per lane column, then dV^T += dO^T P and dK^T += Q'^T dS the same way.
+// The transposed products use rows 0 .. 15 (the head dims) of the 32-row MFMA; rows 16 .. 31 repeat them and are dropped.
+// 2 + 4 and 6 MFMAs per tile against 16 + 17 v_exp_f32 and 24 conversions: like the forward, VALU-bound.
+// LDS rows are 32 bytes; the two 16-byte halves are swapped for rows with bit 3 set (conflict-free 16-byte operand reads,
+// the forward's K image).  Every (slot, head, dim) result leaves with one fp32 atomic, as in the fp32 form.
+constexpr int B16_WAVES = 8;
+constexpr int B16_IMG = BW_MAXL * 32;  // one 16-bit operand of a patch-head
+constexpr int B16_Q_LDS = 2 * B16_IMG;
+constexpr int B16_KV_LDS = 2 * B16_IMG + 2 * BW_MAXL * 4;
+
+struct AttnBwd16P {
+  const bf16_t* q; const bf16_t* k; const bf16_t* v; const bf16_t* dout;
+  const int32_t* q_gidx; const int32_t* kv_gidx; const int32_t* widx; const int32_t* patch_start;
+  float* dq; float* dk; float* dv;
+  float* stats;  // (slot, head, {M = m' + log2 l, D})
+  int ldq, ldk, ldv, lddo, lddq, lddk, lddv;
+  int num_heads;
+  float scale;
+};
+
+typedef __attribute__((ext_vector_type(4))) short b16_s16x4_t;
+typedef __attribute__((address_space(3))) b16_s16x4_t b16_lds_s16x4_t;
+
+// byte offset of (row, 4-dim chunk c4) in a row-major 16-bit image
+__device__ __forceinline__ int b16_off(int row, int c4) { return row * 32 + ((((c4 >> 1) ^ (row >> 3)) & 1) << 4) + ((c4 & 1) << 3); }
+
+// A operand = rows 0 .. 15 of X^T for the 16 rows (k-slots) of X the lane's half wave covers: two transposing reads
+__device__ __forceinline__ bf16x8_t b16_tr_pair(unsigned a0, unsigned a1) {
+  const b16_s16x4_t v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<b16_lds_s16x4_t*>(a0));
+  const b16_s16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<b16_lds_s16x4_t*>(a1));
+  return __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// q * c rounded once to the 16-bit type, as attn_bf16_kernel prepares its B operand (flags 0)
+__device__ __forceinline__ uint4 b16_prescale(uint4 r, float c) {
+  float lo, hi;
+  unpack_bf16x2(r.x, lo, hi); r.x = pack_bf16x2(lo * c, hi * c);
+  unpack_bf16x2(r.y, lo, hi); r.y = pack_bf16x2(lo * c, hi * c);
+  unpack_bf16x2(r.z, lo, hi); r.z = pack_bf16x2(lo * c, hi * c);
+  unpack_bf16x2(r.w, lo, hi); r.w = pack_bf16x2(lo * c, hi * c);
+  return r;
+}
+
+__device__ __forceinline__ bf16x8_t b16_frag(uint4 u) { return __builtin_bit_cast(bf16x8_t, u); }
+
+// registers 8 mf .. 8 mf + 7 of a 32 x 32 accumulator as the 16-bit B fragment of k-slots 8 h .. 8 h + 7 (no saturation)
+__device__ __forceinline__ bf16x8_t b16_pack8(const float* x) {
+  return b16_frag(make_uint4(pack_bf16x2_inrange(x[0], x[1]), pack_bf16x2_inrange(x[2], x[3]), pack_bf16x2_inrange(x[4], x[5]),
+                             pack_bf16x2_inrange(x[6], x[7])));
+}
+
+__global__ __launch_bounds__(B16_WAVES * 64, 4) void attn_bwd16_q_kernel(AttnBwd16P p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* Ks = smem;
+  char* Vs = smem + B16_IMG;
+  const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+  const int patch = blockIdx.x, head = blockIdx.y;
+  const int ps = p.patch_start[patch], L = p.patch_start[patch + 1] - ps;
+  const int nt = (L + 31) >> 5;
+  if ((int)blockIdx.z * B16_WAVES >= nt) return;  // (block-uniform) a slice without tiles
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int i = tid; i < nt * 64; i += B16_WAVES * 64) {  // (row, 16-byte half)
+    const int s = i >> 1, hs = i & 1;
+    uint4 kk = make_uint4(0, 0, 0, 0), vv = kk;
+    if (s < L) {
+      const long r = p.kv_gidx[ps + s];
+      kk = *reinterpret_cast<const uint4*>(p.k + r * p.ldk + head * HD + hs * 8);
+      vv = *reinterpret_cast<const uint4*>(p.v + r * p.ldv + head * HD + hs * 8);
+    }
+    const int o = b16_off(s, 2 * hs);
+    *reinterpret_cast<uint4*>(Ks + o) = kk;
+    *reinterpret_cast<uint4*>(Vs + o) = vv;
+  }
+  __syncthreads();
+  const int ql = lane & 31, h = lane >> 5;
+  const float c2 = p.scale * 1.44269504088896340736f;
+  const int row_off = b16_off(ql, 2 * h);  // A operand of S'^T / dP^T: key ql of the tile, head dims 8 h .. 8 h + 7
+  // K^T fragments: the lane's 16-lane group reads keys 4 h + {0 .. 3} (and + 8) of a 16-key half tile
+  const unsigned tr0 = lds_base + b16_off(4 * h + ((lane & 15) >> 2), lane & 3);
+  const unsigned tr1 = lds_base + b16_off(4 * h + ((lane & 15) >> 2) + 8, lane & 3);
+  const f32x16_t zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int qt = blockIdx.z * B16_WAVES + wave; qt < nt; qt += B16_WAVES * gridDim.z) {
+    const int qslot = qt * 32 + ql;
+    const bool valid = qslot < L;
+    long qrow = 0;
+    uint4 qraw = make_uint4(0, 0, 0, 0), graw = qraw;  // B operands: (query ql, head dims 8 h .. 8 h + 7)
+    if (valid) {
+      qrow = p.q_gidx[ps + qslot];
+      qraw = *reinterpret_cast<const uint4*>(p.q + qrow * p.ldq + head * HD + 8 * h);
+      const int w = p.widx[ps + qslot];  // the slot's output row; padding duplicates have none: dO = 0
+      if (w >= 0) graw = *reinterpret_cast<const uint4*>(p.dout + (long)w * p.lddo + head * HD + 8 * h);
+    }
+    const bf16x8_t qf = b16_frag(b16_prescale(qraw, c2)), gf = b16_frag(graw);
+    // ---- sweep 1: online (m', l, sum e dP) over the lane's keys (rows (r & 3) + 8 (r >> 2) + 4 h of each tile)
+    float m = -INFINITY, l = 0.f, dn = 0.f;
+    for (int kt = 0; kt < nt; ++kt) {
+      f32x16_t sc = mfma_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(Ks + kt * 1024 + row_off), qf, zero16);
+      const f32x16_t dp = mfma_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(Vs + kt * 1024 + row_off), gf, zero16);
+      if (kt == nt - 1) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h >= L) sc[r] = -INFINITY;
+      }
+      float mn = m;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) mn = fmaxf(mn, sc[r]);
+      if (mn > -INFINITY) {
+        const float a = __builtin_amdgcn_exp2f(m - mn);
+        l *= a; dn *= a;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float e = __builtin_amdgcn_exp2f(sc[r] - mn);
+          l += e;
+          dn = fmaf(e, dp[r], dn);
+        }
+        m = mn;
+      }
+    }
+    {
+      const float m2 = __shfl_xor(m, 32, 64), l2 = __shfl_xor(l, 32, 64), d2 = __shfl_xor(dn, 32, 64);
+      const float mn = fmaxf(m, m2);
+      if (mn > -INFINITY) {
+        const float a = __builtin_amdgcn_exp2f(m - mn), b = __builtin_amdgcn_exp2f(m2 - mn);
+        l = l * a + l2 * b;
+        dn = dn * a + d2 * b;
+      }
+      m = mn;
+    }
+    const float M = m + __builtin_amdgcn_logf(l), D = dn / l;  // (v_log_f32 = log2)
+    if (valid && h == 0) {
+      float* st = p.stats + ((long)(ps + qslot) * p.num_heads + head) * 2;
+      st[0] = M; st[1] = D;
+    }
+    // ---- sweep 2: dQ^T (rows = head dims, column = query ql) += K^T dS^T
+    const float nm = valid ? -M : 0.f;
+    const f32x16_t negm = {nm, nm, nm, nm, nm, nm, nm, nm, nm, nm, nm, nm, nm, nm, nm, nm};
+    f32x16_t dq = zero16;
+    for (int kt = 0; kt < nt; ++kt) {
+      const f32x16_t sc = mfma_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(Ks + kt * 1024 + row_off), qf, negm);
+      const f32x16_t dp = mfma_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(Vs + kt * 1024 + row_off), gf, zero16);
+      float ds[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) ds[r] = __builtin_amdgcn_exp2f(sc[r]) * (dp[r] - D);
+      if (kt == nt - 1) {  // keys past the end of a ragged patch (their K rows are zero: s' = 0, not -inf)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h >= L) ds[r] = 0.f;
+      }
+#pragma unroll
+      for (int mf = 0; mf < 2; ++mf) {
+        const bf16x8_t kT = b16_tr_pair(tr0 + kt * 1024 + mf * 512, tr1 + kt * 1024 + mf * 512);
+        dq = mfma_32x32x16_bf16(kT, b16_pack8(ds + 8 * mf), dq);
+      }
+    }
+    if (valid) {  // rows 4 h + (r & 3) + 8 (r >> 2), r < 8; a point padded into two slots collects both
+      float* o = p.dq + qrow * p.lddq + head * HD + 4 * h;
+#pragma unroll
+      for (int r = 0; r < 8; ++r) atomicAdd(o + (r & 3) + 8 * (r >> 2), dq[r] * p.scale);
+    }
+  }
+}
+
+__global__ __launch_bounds__(B16_WAVES * 64, 4) void attn_bwd16_kv_kernel(AttnBwd16P p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* Qs = smem;                                                   // Q' = round16(Q * scale * log2 e)
+  char* Gs = smem + B16_IMG;                                         // dO
+  float* sNM = reinterpret_cast<float*>(smem + 2 * B16_IMG);         // -M (-inf for the slots past the end: P = 0)
+  float* sD = sNM + BW_MAXL;
+  const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+  const int patch = blockIdx.x, head = blockIdx.y;
+  const int ps = p.patch_start[patch], L = p.patch_start[patch + 1] - ps;
+  const int nt = (L + 31) >> 5;
+  if ((int)blockIdx.z * B16_WAVES >= nt) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float c2 = p.scale * 1.44269504088896340736f;
+  for (int i = tid; i < nt * 64; i += B16_WAVES * 64) {
+    const int s = i >> 1, hs = i & 1;
+    uint4 qq = make_uint4(0, 0, 0, 0), gg = qq;
+    float nM = -INFINITY, D = 0.f;
+    if (s < L) {
+      const long r = p.q_gidx[ps + s];
+      qq = b16_prescale(*reinterpret_cast<const uint4*>(p.q + r * p.ldq + head * HD + hs * 8), c2);
+      const int w = p.widx[ps + s];
+      if (w >= 0) gg = *reinterpret_cast<const uint4*>(p.dout + (long)w * p.lddo + head * HD + hs * 8);
+      const float* st = p.stats + ((long)(ps + s) * p.num_heads + head) * 2;
+      nM = -st[0]; D = st[1];
+    }
+    const int o = b16_off(s, 2 * hs);
+    *reinterpret_cast<uint4*>(Qs + o) = qq;
+    *reinterpret_cast<uint4*>(Gs + o) = gg;
+    if (hs == 0) { sNM[s] = nM; sD[s] = D; }
+  }
+  __syncthreads();
+  const int kl = lane & 31, h = lane >> 5;
+  const int row_off = b16_off(kl, 2 * h);
+  const unsigned tr0 = lds_base + b16_off(4 * h + ((lane & 15) >> 2), lane & 3);
+  const unsigned tr1 = lds_base + b16_off(4 * h + ((lane & 15) >> 2) + 8, lane & 3);
+  const f32x16_t zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int kt = blockIdx.z * B16_WAVES + wave; kt < nt; kt += B16_WAVES * gridDim.z) {
+    const int kslot = kt * 32 + kl;
+    const bool valid = kslot < L;
+    long krow = 0;
+    uint4 kraw = make_uint4(0, 0, 0, 0), vraw = kraw;  // B operands: (key kl, head dims 8 h .. 8 h + 7)
+    if (valid) {
+      krow = p.kv_gidx[ps + kslot];
+      kraw = *reinterpret_cast<const uint4*>(p.k + krow * p.ldk + head * HD + 8 * h);
+      vraw = *reinterpret_cast<const uint4*>(p.v + krow * p.ldv + head * HD + 8 * h);
+    }
+    const bf16x8_t kf = b16_frag(kraw), vf = b16_frag(vraw);
+    f32x16_t dk = zero16, dv = zero16;  // rows = head dims, column = key kl
+    for (int qt = 0; qt < nt; ++qt) {
+      // rows = queries (r & 3) + 8 (r >> 2) + 4 h of the tile: their -M is the C operand, so S' - M leaves the MFMA
+      f32x16_t cm, Dr;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float4 a = *reinterpret_cast<const float4*>(sNM + qt * 32 + 8 * j + 4 * h);
+        const float4 b = *reinterpret_cast<const float4*>(sD + qt * 32 + 8 * j + 4 * h);
+        cm[4 * j] = a.x; cm[4 * j + 1] = a.y; cm[4 * j + 2] = a.z; cm[4 * j + 3] = a.w;
+        Dr[4 * j] = b.x; Dr[4 * j + 1] = b.y; Dr[4 * j + 2] = b.z; Dr[4 * j + 3] = b.w;
+      }
+      const f32x16_t sc = mfma_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(Qs + qt * 1024 + row_off), kf, cm);
+      const f32x16_t dp = mfma_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(Gs + qt * 1024 + row_off), vf, zero16);
+      float pr[16], ds[16];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        pr[r] = __builtin_amdgcn_exp2f(sc[r]);
+        ds[r] = pr[r] * (dp[r] - Dr[r]);
+      }
+#pragma unroll
+      for (int mf = 0; mf < 2; ++mf) {
+        const unsigned o0 = tr0 + qt * 1024 + mf * 512, o1 = tr1 + qt * 1024 + mf * 512;
+        dv = mfma_32x32x16_bf16(b16_tr_pair(o0 + B16_IMG, o1 + B16_IMG), b16_pack8(pr + 8 * mf), dv);
+        dk = mfma_32x32x16_bf16(b16_tr_pair(o0, o1), b16_pack8(ds + 8 * mf), dk);
+      }
+    }
+    if (valid) {
+      float* ok = p.dk + krow * p.lddk + head * HD + 4 * h;
+      float* ov = p.dv + krow * p.lddv + head * HD + 4 * h;
+      const float ln2 = 0.69314718055994530942f;  // Q' carries scale * log2(e): dK = scale dS^T Q = ln 2 dS^T Q'
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        atomicAdd(ok + (r & 3) + 8 * (r >> 2), dk[r] * ln2);
+        atomicAdd(ov + (r & 3) + 8 * (r >> 2), dv[r]);
+      }
+    }
+  }
+}
+
 // ---- LayerNorm backward: dx = (1/sigma) (dyg - mean(dyg) - xhat mean(dyg xhat)), dyg = dy * gamma.  One wave per row, 16 rows
 // per wave; d gamma / d beta are summed over the block's 64 rows in registers + LDS and leave with ONE atomic per column
 // and block (the first version issued one atomic per element onto C addresses: 82 of a 450 ms training step).
@@ -418,22 +683,49 @@ extern "C" int cdseg_attention_bwd(const void* q, const void* k, const void* v, 
                                    float scale, const void* dout, int lddo, void* dq, void* dk, void* dv, int lddq, int lddk,
                                    int lddv, int dtype, void* ws, size_t ws_bytes, void* stream) {
   if (num_patches <= 0 || num_heads <= 0) return CDSEG_OK;
-  if (dtype != CDSEG_F32) return CDSEG_ERR_UNSUPPORTED;  // first slice: the exact-fp32 mode
+  if (dtype != CDSEG_F32 && dtype != CDSEG_BF16) return CDSEG_ERR_UNSUPPORTED;
   // the patch-head lives in LDS (like the forward): a longer patch would write past the staged K / V / statistics
   if (max_len <= 0 || max_len > CDSEG_MAX_PATCH) return CDSEG_ERR_UNSUPPORTED;
   if (!q || !k || !v || !dout || !dq || !dk || !dv || !patch_start) return CDSEG_ERR_ARG;
-  // float4 operand loads: 16-byte aligned rows
-  if ((ldq | ldk | ldv | lddo | lddq | lddk | lddv) & 3) return CDSEG_ERR_ARG;
+  // 16-byte operand loads (float4 / eight 16-bit values): 16-byte aligned rows
+  const int op_mask = dtype == CDSEG_F32 ? 3 : 7;
+  if (((ldq | ldk | ldv | lddo) & op_mask) || ((lddq | lddk | lddv) & 3)) return CDSEG_ERR_ARG;
   if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) & 15) != 0)
     return CDSEG_ERR_ARG;
   if (!ws || ws_bytes < cdseg_attention_bwd_ws_bytes(num_slots, num_heads)) return CDSEG_ERR_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid((unsigned)num_patches, (unsigned)num_heads);
+  if (dtype == CDSEG_BF16) {
+    AttnBwd16P p;
+    p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.dout = (const bf16_t*)dout;
+    p.q_gidx = q_gidx; p.kv_gidx = kv_gidx; p.widx = widx; p.patch_start = patch_start;
+    p.dq = (float*)dq; p.dk = (float*)dk; p.dv = (float*)dv; p.stats = (float*)ws;
+    p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.lddo = lddo; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
+    p.num_heads = num_heads; p.scale = scale;
+    static std::once_flag attr16_once;
+    static bool attr16_ok = false;
+    std::call_once(attr16_once, [] {
+      attr16_ok = hipFuncSetAttribute((const void*)attn_bwd16_q_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, B16_Q_LDS) == hipSuccess &&
+                  hipFuncSetAttribute((const void*)attn_bwd16_kv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, B16_KV_LDS) == hipSuccess;
+    });
+    if (!attr16_ok) return CDSEG_ERR_LAUNCH;
+    // A patch-head is cut into `split` slices of its query (q kernel) / key (kv kernel) tiles, each a block that stages the
+    // whole patch-head, while the launch does not fill the chip's 2 x 256 block slots: one block per patch-head left a single
+    // scene's launches (at most 236 blocks) with two waves per SIMD, the deep stages with a quarter of the CUs
+    int split = 1;
+    while (split < 4 && (long)num_patches * num_heads * split * 2 <= 512) split *= 2;
+    const dim3 grid16((unsigned)num_patches, (unsigned)num_heads, (unsigned)split);
+    hipLaunchKernelGGL(attn_bwd16_q_kernel, grid16, dim3(B16_WAVES * 64), B16_Q_LDS, s, p);
+    hipLaunchKernelGGL(attn_bwd16_kv_kernel, grid16, dim3(B16_WAVES * 64), B16_KV_LDS, s, p);
+    CDSEG_CHECK_LAUNCH();
+    return CDSEG_OK;
+  }
   AttnBwdP p;
   p.q = (const float*)q; p.k = (const float*)k; p.v = (const float*)v; p.dout = (const float*)dout;
   p.q_gidx = q_gidx; p.kv_gidx = kv_gidx; p.widx = widx; p.patch_start = patch_start;
   p.dq = (float*)dq; p.dk = (float*)dk; p.dv = (float*)dv; p.stats = (float*)ws;
   p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.lddo = lddo; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
   p.num_heads = num_heads; p.scale = scale;
-  hipStream_t s = (hipStream_t)stream;
   static std::once_flag attr_once;  // (one device per process: one process per GPU)
   static bool attr_ok = false;
   std::call_once(attr_once, [] {
@@ -441,7 +733,6 @@ extern "C" int cdseg_attention_bwd(const void* q, const void* k, const void* v, 
               hipFuncSetAttribute((const void*)attn_bwd_kv_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BW_KV_LDS) == hipSuccess;
   });
   if (!attr_ok) return CDSEG_ERR_LAUNCH;
-  dim3 grid((unsigned)num_patches, (unsigned)num_heads);
   hipLaunchKernelGGL(attn_bwd_q_mfma_kernel, grid, dim3(BW_WAVES * 64), BW_Q_LDS, s, p);
   hipLaunchKernelGGL(attn_bwd_kv_mfma_kernel, grid, dim3(BW_WAVES * 64), BW_KV_LDS, s, p);
   CDSEG_CHECK_LAUNCH();

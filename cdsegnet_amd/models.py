@@ -424,6 +424,10 @@ class DefaultSegmentorV2(nn.Module):
         # "fp16+head" (default) | "fp16" | "bf16+head" | "bf16": 16-bit MFMA operands / activations (IEEE half or bfloat16),
         # fp32 accumulation and residual stream, "+head" = seg heads in exact fp32 | "fp32": exact-fp32 MFMA everywhere
         self.precision = "fp16+head"
+        # training forward: "fp32" (default: exact fp32) | "fp16-attn" | "bf16-attn": the attention core (forward and backward,
+        # self and cross attention) in IEEE half / bfloat16 like the reference's flash-attention path, everything else fp32;
+        # read at every forward(), anything else raises ValueError there
+        self.train_precision = "fp32"
         self._lanes = {}
         self.noise_source = "torch_cpu"  # "torch_cpu" replays the reference's CPU-generator draws | "device"
         # noise_level jitter: "torch_cpu" = the CPU-run reference's draw order (golden vectors) | "device" = device
@@ -572,8 +576,9 @@ class DefaultSegmentorV2(nn.Module):
 
     def forward(self, input_dict, draws=None):
         """Training forward (ref: default.py:424-493): returns dict(loss=...) under torch autograd - `loss.backward()` fills
-        the `.grad` of this module's parameters like the reference's does (engines/train.py:216-271).  fp32, on the HIP
-        kernels behind torch.autograd.Functions: cdsegnet_amd/train_graph.py.  `draws` replays recorded random draws."""
+        the `.grad` of this module's parameters like the reference's does (engines/train.py:216-271).  fp32, or with a 16-bit
+        attention core (`train_precision`), on the HIP kernels behind torch.autograd.Functions: cdsegnet_amd/train_graph.py.
+        `draws` replays recorded random draws."""
         from .train_graph import TrainGraph
         if getattr(self, "_train_graph", None) is None:
             self._train_graph = TrainGraph(self)

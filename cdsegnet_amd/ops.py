@@ -1143,27 +1143,37 @@ def serialization(grid_coord, batch, orders=("z", "z-trans", "hilbert", "hilbert
     return torch.stack(codes), torch.stack(orders_), torch.stack(inverses), depth
 
 
-# ------------------------------------------------------------------ training path, first slice (csrc/train.hip)
+# ------------------------------------------------------------------ training path (csrc/train.hip)
 def attention_bwd(q, k, v, q_gidx, kv_gidx, widx, patch_start, patch_start_host, num_heads, scale, dout, dq, dk, dv):
-    """Gradients of `attention` (fp32): dq / dk / dv (views of zero-initialised buffers, any row stride) += at the
-    gathered rows.  patch_start_host: the same patch table as Python ints (tile count of the launch)."""
+    """Gradients of `attention`: fp32 dq / dk / dv (views of zero-initialised buffers, any row stride) += at the gathered
+    rows.  q / k / v / dout share a dtype: fp32 (exact-fp32 kernels), or the active build's 16-bit type (the recompute-P
+    backward of the 16-bit forward on the 16-bit matrix pipe; dout is used as it comes: an inf stays an inf).
+    patch_start_host: the same patch table as Python ints (tile count of the launch)."""
     _need_gpu(q, dout)
-    if q.dtype != torch.float32:
-        raise _lib.CdsegError("attention_bwd: exact-fp32 mode only (first slice of the training path)")
+    if not (q.dtype == k.dtype == v.dtype == dout.dtype):
+        raise _lib.CdsegError("attention_bwd: q, k, v, dout must share a dtype")
+    if not (dq.dtype == dk.dtype == dv.dtype == torch.float32):
+        raise _lib.CdsegError("attention_bwd: dq, dk, dv are fp32 (accumulated into)")
+    code = dt(q)  # (a 16-bit tensor of the other build's type raises here)
     ps = [int(x) for x in patch_start_host]
     num_patches = len(ps) - 1
     max_len = max((ps[i + 1] - ps[i] for i in range(num_patches)), default=0)
     if max_len > 1024:
         raise _lib.CdsegError("attention_bwd: a patch holds at most 1024 slots (the patch-head lives in LDS, like the forward)")
+    per16 = 16 // q.element_size()
     for t, ld in ((q, q.stride(0)), (k, k.stride(0)), (v, v.stride(0)), (dout, dout.stride(0))):
-        if ld % 4 or t.data_ptr() % 16:
-            raise _lib.CdsegError("attention_bwd: rows must be 16-byte aligned (float4 operand loads)")
+        if ld % per16 or t.data_ptr() % 16 or t.stride(1) != 1:
+            raise _lib.CdsegError("attention_bwd: rows must be 16-byte aligned (float4 operand loads)" if per16 == 4 else
+                                  "attention_bwd: rows must be 16-byte aligned (eight 16-bit values per operand load)")
+    for t in (dq, dk, dv):
+        if t.stride(0) % 4 or t.data_ptr() % 16 or t.stride(1) != 1:
+            raise _lib.CdsegError("attention_bwd: gradient rows must be 16-byte aligned")
     lib = _lib.load()
     ws = torch.empty(max(1, lib.cdseg_attention_bwd_ws_bytes(ps[-1], int(num_heads))), dtype=torch.uint8, device=q.device)
     check(lib.cdseg_attention_bwd(_ptr(q), _ptr(k), _ptr(v), q.stride(0), k.stride(0), v.stride(0), _ptr(q_gidx),
                                   _ptr(kv_gidx), _ptr(widx), _ptr(patch_start), num_patches, int(num_heads), ps[-1], max(1, max_len),
                                   float(scale), _ptr(dout), dout.stride(0), _ptr(dq), _ptr(dk), _ptr(dv), dq.stride(0),
-                                  dk.stride(0), dv.stride(0), dt(q), _ptr(ws), ws.numel(), _stream()), "attention_bwd")
+                                  dk.stride(0), dv.stride(0), code, _ptr(ws), ws.numel(), _stream()), "attention_bwd")
 
 
 def layernorm_bwd(x, gamma, dy, dx, accumulate=False, eps=1e-5, dgamma=None, dbeta=None):

@@ -17,8 +17,10 @@ unchanged - and underneath, every product that carries the FLOPs runs on this li
     serialized (cross) attention                 cdseg_attention / cdseg_attention_bwd (recompute-P, gathered rows)
     segment max of the pooling                   cdseg_segment_max forward; the arg-max mask is recomputed in the backward
 
-in exact fp32 (the reference trains its trunk in fp32 with an fp16 attention core under AMP; the 16-bit backward is the
-next step).  What stays plain torch device ops: train-mode BatchNorm1d (3 per pooling stage, batch
+in exact fp32 by default.  The reference never runs its attention core in fp32 on a GPU (`qkv.half()` into flash-attention,
+whose backward is half too): `model.train_precision = "fp16-attn"` / `"bf16-attn"` runs the attention core of every Block
+and of the cross attention in 16 bits - the inference path's 16-bit forward kernel and the recompute-P backward on the 16-bit
+matrix pipe (csrc/train.hip), fp32 dq / dk / dv - and leaves everything else in fp32.  What stays plain torch device ops: train-mode BatchNorm1d (3 per pooling stage, batch
 statistics), GELU between them, the swish timestep MLP on B rows, row masks of stochastic depth, q_sample, the two
 (C -> classes) heads, and the criteria (cdsegnet_amd.losses).  All integer work - serialization, pooling structure,
 kernel maps, padded patch plans - is the inference engine's plan (Engine.build_plan), shared with the inference path.
@@ -29,6 +31,7 @@ import torch
 import torch.nn.functional as F
 
 from . import engine as _engine
+from . import _lib
 from ._lib import DuplicateVoxelsError
 from . import ops
 from .losses import build_criteria
@@ -143,6 +146,9 @@ def layernorm(x, mod):
     return _LayerNorm.apply(x, mod.weight, mod.bias, float(mod.eps))
 
 
+TRAIN_PRECISIONS = {"fp32": None, "fp16-attn": "f16", "bf16-attn": "bf16"}  # train_precision -> library build of the attention core
+
+
 class _Attention(torch.autograd.Function):
     """softmax(q k^T scale) v per padded patch and head on gathered rows (ref: ptv3.py:246-296 / :988-1055).
     q (N, C), kv (N, 2C) (self attention: views of the packed qkv)."""
@@ -162,6 +168,50 @@ class _Attention(torch.autograd.Function):
         dq, dk, dv = torch.zeros_like(q), torch.zeros_like(k), torch.zeros_like(v)
         ops.attention_bwd(q, k, v, q_gidx, kv_gidx, widx, patch_start, psh, heads, scale, _c(do), dq, dk, dv)
         return dq, dk, dv, None, None, None, None, None, None, None, None
+
+
+class _Attention16(torch.autograd.Function):
+    """_Attention with a 16-bit core (ref: ptv3.py:282-289 `qkv.half()` into flash-attention, :1038-1047): `src` is the packed
+    fp32 projection (qkv of a Block; q and kv of the cross attention arrive as two calls' worth: `src2`), cast ONCE to the
+    16-bit type of library build `variant`; the forward is the inference path's 16-bit kernel (flags 0) with its 16-bit output
+    cast up; the 16-bit copies are what the backward keeps; dout is cast WITHOUT saturation (a scaled gradient beyond half's
+    range must reach the GradScaler as inf, the library's own casts would clamp it); dq / dk / dv come back fp32, and the
+    cast's backward is the identity.  The build is selected inside forward AND backward from ctx (`_lib.use` is per thread
+    and autograd runs backward on a thread of its own)."""
+
+    @staticmethod
+    def forward(ctx, src, src2, cq, q_gidx, kv_gidx, widx, patch_start, patch_start_host, heads, max_len, scale, variant):
+        t16 = ops.LP_DTYPES[variant]
+        with _lib.use(variant):
+            a = ops.cast(_c(src), t16)
+            b = a if src2 is None else ops.cast(_c(src2), t16)
+            q, k, v = (a[:, :cq], a[:, cq:2 * cq], a[:, 2 * cq:]) if src2 is None else (a, b[:, :cq], b[:, cq:])
+            o = torch.empty((src.shape[0], cq), dtype=t16, device=src.device)
+            ops.attention(q, k, v, q_gidx, kv_gidx, widx, patch_start, heads, max_len, scale, o)
+        ctx.save_for_backward(a, b, q_gidx, kv_gidx, widx, patch_start)
+        ctx.meta = (list(patch_start_host), heads, scale, variant, cq, src2 is None)
+        return o.float()
+
+    @staticmethod
+    def backward(ctx, do):
+        a, b, q_gidx, kv_gidx, widx, patch_start = ctx.saved_tensors
+        psh, heads, scale, variant, cq, packed = ctx.meta
+        q, k, v = (a[:, :cq], a[:, cq:2 * cq], a[:, 2 * cq:]) if packed else (a, b[:, :cq], b[:, cq:])
+        da = torch.zeros(a.shape, dtype=torch.float32, device=a.device)
+        db = da if packed else torch.zeros(b.shape, dtype=torch.float32, device=a.device)
+        dq, dk, dv = (da[:, :cq], da[:, cq:2 * cq], da[:, 2 * cq:]) if packed else (da, db[:, :cq], db[:, cq:])
+        with _lib.use(variant):
+            ops.attention_bwd(q, k, v, q_gidx, kv_gidx, widx, patch_start, psh, heads, scale, _c(do).to(a.dtype), dq, dk, dv)
+        return da, (None if packed else db), None, None, None, None, None, None, None, None, None, None
+
+
+def attention_core(variant, q_src, kv_src, cq, q_gidx, kv_gidx, widx, patch_start, psh, heads, max_len, scale):
+    """The attention core of a Block (kv_src None: q_src is the packed (N, 3 cq) qkv) or of the cross attention (q_src (N, cq),
+    kv_src (M, 2 cq)); variant None = exact fp32, "f16" / "bf16" = 16-bit core on that build of the library."""
+    if variant is None:
+        q, k, v = (q_src[:, :cq], q_src[:, cq:2 * cq], q_src[:, 2 * cq:]) if kv_src is None else (q_src, kv_src[:, :cq], kv_src[:, cq:])
+        return _Attention.apply(q, k, v, q_gidx, kv_gidx, widx, patch_start, psh, heads, max_len, scale)
+    return _Attention16.apply(q_src, kv_src, cq, q_gidx, kv_gidx, widx, patch_start, psh, heads, max_len, scale, variant)
 
 
 class _SegmentMax(torch.autograd.Function):
@@ -257,6 +307,7 @@ class TrainGraph:
 
     def __init__(self, model):
         self.model = model
+        self.attn_variant = None  # library build of the attention core, from model.train_precision at every forward
         self.eng = _engine.Engine(model, "fp32")  # the plan builder (never prepared: no second copy of the weights)
         self.criteria = build_criteria(model.criteria_cfg, model.loss_type, model.task_num)
 
@@ -300,8 +351,7 @@ class TrainGraph:
         gidx, widx = lv.slots(st.curves[att.order_index], att.patch_size, att.enable_flash)
         patch_start, max_len = lv.pad(att.patch_size, att.enable_flash)[4:6]
         psh = lv.pad_host(att.patch_size, att.enable_flash)[3].tolist()
-        o = _Attention.apply(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], gidx, gidx, widx, patch_start, psh, att.num_heads,
-                             max_len, att.scale)
+        o = attention_core(self.attn_variant, qkv, None, c, gidx, gidx, widx, patch_start, psh, att.num_heads, max_len, att.scale)
         a = linear(o, att.proj)
         m = self._mask(st, name + ".drop_path.0", mod.drop_prob, masks)
         x = x + (a if m is None else a * m)
@@ -367,7 +417,7 @@ class TrainGraph:
         kv_gidx, _ = clv.slots(cst.curves[att.order_index], K, att.enable_flash)
         patch_start, max_len = lv.pad(K, att.enable_flash)[4:6]
         psh = lv.pad_host(K, att.enable_flash)[3].tolist()
-        o = _Attention.apply(q, kv[:, :cq], kv[:, cq:], q_gidx, kv_gidx, widx, patch_start, psh, att.num_heads, max_len, att.scale)
+        o = attention_core(self.attn_variant, q, kv, cq, q_gidx, kv_gidx, widx, patch_start, psh, att.num_heads, max_len, att.scale)
         a = linear(o, att.proj)
         name = "backbone._tm_dec0.cross_block2.drop_path.0"
         m = self._mask(nst, name, cb.drop_prob, masks)
@@ -383,9 +433,15 @@ class TrainGraph:
         Returns dict(loss, n_pred, c_pred, c_target).
 
         The reference trainer calls the model inside `torch.cuda.amp.autocast(enabled=cfg.enable_amp)` and scales the loss
-        with a GradScaler (engines/train.py:226-240).  This forward is exact fp32 whatever the context: autocast is switched
-        off inside it (torch's own ops here - heads, BatchNorm, GELU - would otherwise hand half tensors to fp32 kernels), so
-        the trainer's AMP branch runs unchanged: the scaler multiplies an fp32 loss and finds no overflow."""
+        with a GradScaler (engines/train.py:226-240).  This forward computes what `model.train_precision` says whatever the
+        context ("fp32": exact fp32; "fp16-attn" / "bf16-attn": the attention core in 16 bits, the rest fp32): autocast is
+        switched off inside it (torch's own ops here - heads, BatchNorm, GELU - would otherwise hand half tensors to fp32
+        kernels), so the trainer's AMP branch runs unchanged: the scaler multiplies an fp32 loss, and only a scaled gradient
+        that leaves half's range inside the "fp16-attn" core shows up as an overflow (non-finite dq / dk / dv)."""
+        tp = getattr(self.model, "train_precision", "fp32")
+        if tp not in TRAIN_PRECISIONS:
+            raise ValueError(f"train_precision must be one of {sorted(TRAIN_PRECISIONS)}, not {tp!r}")
+        self.attn_variant = TRAIN_PRECISIONS[tp]
         if feat_is_cuda(input_dict):
             with torch.autocast(device_type="cuda", enabled=False):
                 return self._forward(input_dict, draws)

@@ -582,15 +582,24 @@ int cdseg_plan_finish_layout(const cdseg_plan_spec* spec, long n, int nb, const 
                              long* off_out, long* info_out);
 int cdseg_plan_finish(const cdseg_plan_spec* spec, const cdseg_plan_finish_io* io, void* stream);
 
-/* ------------------------------------------------------------------ training path, first slice (exact fp32)
+/* ------------------------------------------------------------------ training path (exact fp32; the attention core also in 16 bits)
  * ref: pointcept/models/default.py:424-493 (training forward), pointcept/engines/train.py:216-271 (loss.backward());
  *      what autograd differentiates: ptv3.py:246-296 (SerializedAttention core), ptv3.py:399-428 (Block tail).
  * cdseg_attention_bwd: gradients of cdseg_attention's inputs.  dout (rows, H*16) is the gradient of its output; dq / dk /
  *   dv are ACCUMULATED into (+=, the caller zeroes them) at the gathered rows - a point that the padding plan put into
  *   two slots collects both (the backward of the reference's `qkv[order]` gather); slots without an output row (widx -1)
  *   receive no output gradient but still act as keys.  num_slots = patch_start[num_patches]; max_len = the longest patch,
- *   <= 1024 (the patch-head lives in LDS: longer -> CDSEG_ERR_UNSUPPORTED); rows 16-byte aligned (else CDSEG_ERR_ARG).
- *   ws: cdseg_attention_bwd_ws_bytes.  dtype: CDSEG_F32 only so far.
+ *   <= 1024 (the patch-head lives in LDS: longer -> CDSEG_ERR_UNSUPPORTED).  ws: cdseg_attention_bwd_ws_bytes (one size,
+ *   sufficient for either dtype).  dtype is that of q, k, v and dout; dq, dk, dv are fp32 in both forms:
+ *     CDSEG_F32   exact fp32 (the backward of the parity mode's forward).
+ *     CDSEG_BF16  the build's 16-bit type: the recompute-P backward of the 16-bit forward (flags 0) on the 16-bit matrix
+ *                 pipe.  Differentiates what that forward computes: q' = q * fp32(scale * log2 e) rounded once to the
+ *                 16-bit type (the rounding counts as the identity), s' = q'.k, P = exp2(s' - m') / l.  The row statistics
+ *                 (m', l, D = sum_j P dP) are recomputed here in fp32 with the exact row maximum; P and dS = P (dP - D) are
+ *                 rounded to the 16-bit type as MFMA operands only; all accumulators are fp32.  dout is not clamped and dS
+ *                 is converted without saturation (half build): a gradient beyond the 16-bit range arrives as inf / NaN.
+ *   Alignment (CDSEG_ERR_ARG otherwise): every pointer 16-byte aligned; ldq, ldk, ldv, lddo (in elements) multiples of 4
+ *   (CDSEG_F32) or of 8 (CDSEG_BF16), i.e. 16-byte rows; lddq, lddk, lddv multiples of 4.
  * cdseg_layernorm_bwd: dx (=, or += when accumulate) for y = LayerNorm(x) * gamma + beta; optional dgamma / dbeta (+=).
  * cdseg_gelu_bwd: dx = dy * d/du GELU(u) on the pre-activation u (erf form, torch.nn.GELU()).
  * cdseg_linear_wgrad: dw[n][k] += sum_m dy[m][n] * x[row(m)][k] and (db != NULL) db[n] += sum_m dy[m][n], fp32; row(m) = m,

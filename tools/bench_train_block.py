@@ -2,12 +2,13 @@
 parameter gradients, exact fp32) on the HIP kernels, at a real stage shape, next to torch autograd on the CPU oracle.
 usage: python tools/bench_train_block.py [n_points=56000] [heads=4] [cpu=1]
 Prints ms per forward / backward, the algorithmic FLOPs (backward = 2x forward for the Linears and the conv, 2.5x for
-the attention core: recomputed scores + four products) and the CPU time of the same gradients."""
+the attention core: recomputed scores + four products) and the CPU time of the same gradients; last, the attention backward
+alone (HIP events around the two kernels) in fp32 and in both 16-bit builds on the same patch tables."""
 import os, sys, time
 import numpy as np
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from cdsegnet_amd import ops, synth, train
+from cdsegnet_amd import _lib, ops, synth, train
 
 n_req = int(sys.argv[1]) if len(sys.argv) > 1 else 56000
 H = int(sys.argv[2]) if len(sys.argv) > 2 else 4
@@ -110,3 +111,30 @@ for name, fn in (("attention backward", attn_b), ("conv weight gradient (27 offs
                  ("conv data gradient (gathered GEMM, mirrored kernel)", conv_d)):
     ms, _ = timeit(fn)
     print(f"  {name}: {ms:.2f} ms")
+
+# ---- the attention backward alone, fp32 against the 16-bit form of both builds: same patch tables, same values (rounded),
+#      HIP events around the call (two kernels), gradient buffers zeroed outside the timed region
+def attn_events(variant, reps=9):
+    with _lib.use(variant or "bf16"):
+        qkv = t.qkv if variant is None else ops.cast(t.qkv, ops.LP_DTYPES[variant])
+        g = do if variant is None else do.to(qkv.dtype)
+        ms = []
+        for _ in range(reps + 2):
+            dqkv = torch.zeros((n, 3 * c), dtype=torch.float32, device=dev)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ops.bind_stream()
+            e0.record()
+            ops.attention_bwd(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], t.gidx, t.gidx, t.widx, t.patch_start, t.patch_start_host,
+                              t.num_heads, t.scale, g, dqkv[:, :c], dqkv[:, c:2 * c], dqkv[:, 2 * c:])
+            e1.record()
+            ops.unbind_stream()
+            torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1))
+    ms = sorted(ms[2:])
+    return ms[len(ms) // 2], ms[0], ms[-1]
+base = None
+for variant in (None, "bf16", "f16"):
+    med, lo, hi = attn_events(variant)
+    base = base or med
+    print(f"  attention backward kernels, n={n} H={H}, {variant or 'fp32'}: {med:.3f} ms (min {lo:.3f}, max {hi:.3f}; 9 runs)"
+          + ("" if variant is None else f" = {base / med:.2f}x the fp32 form"))
