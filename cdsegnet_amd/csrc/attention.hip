@@ -259,6 +259,7 @@ __global__ __launch_bounds__(64 * WAVES, 4) void attn_bf16_kernel(AttnP p) {
   constexpr int NPC = 32 / WAVES;  // 32-key pieces of K (and of V) a wave stages
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Ks = smem;
+  int* s_live = reinterpret_cast<int*>(smem + 2 * KV_STAGE + ONES_BYTES);                // per staging wave: its highest kept slot + 1
   unsigned* s_next = reinterpret_cast<unsigned*>(smem + 2 * KV_STAGE + ONES_BYTES + 48);  // query tiles handed out so far
   int* s_qidx = reinterpret_cast<int*>(smem + 2 * KV_STAGE + ONES_BYTES + 64);           // slot -> query row
   const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
@@ -285,7 +286,11 @@ __global__ __launch_bounds__(64 * WAVES, 4) void attn_bf16_kernel(AttnP p) {
 
   const int ql = lane & 31;  // query (B operand column) / key or head-dim row (A operand row)
   const int h = lane >> 5;
-  const int nqt = nkt;
+  // Query tiles: up to the last one that holds a slot whose row is kept (widx >= 0).  The slots a scene's last patch borrows from
+  // the patch before (cdseg_pad_plan) are keys only - their rows as queries are dropped by the store - so the tiles behind the
+  // last kept slot are neither handed out nor computed.  Known once the staging waves have looked at the patch's widx (below):
+  // until the staging barrier the bound is the number of key tiles.
+  int nqt = nkt;
   // Query tiles are handed out dynamically (LDS counter): the SIMD issues its waves oldest first, so the waves of a
   // block advance at very different rates (2 : 1 and more); with a static split the fast waves exit early and their
   // slots stay empty until the block's slowest wave is done (the next block needs all eight).  A wave claims its next
@@ -328,6 +333,18 @@ __global__ __launch_bounds__(64 * WAVES, 4) void attn_bf16_kernel(AttnP p) {
     if (wave < ATTN_RUN) {  // (1024 slots: 128 per wave of the first eight)
 #pragma unroll
       for (int i = 0; i < 2; ++i) gq[i] = p.q_gidx[ps + min(wave * 128 + i * 64 + lane, L - 1)];
+    }
+    // ... and the highest of the wave's 128 slots whose row is kept, + 1 (0: none): whatever the caller's widx says, no
+    // assumption that the kept slots are a prefix
+    if (wave < ATTN_RUN) {
+      int live = 0;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int s = wave * 128 + i * 64 + lane;
+        const unsigned long long m = __ballot(s < L && p.widx[ps + min(s, L - 1)] >= 0);
+        if (m) live = wave * 128 + i * 64 + 64 - __builtin_clzll(m);
+      }
+      if (lane == 0) s_live[wave] = live;
     }
     // the wave's FIRST query tile is fixed: tile 4 w of an unsliced patch-head (its rows are the first 32 of the indices
     // just loaded), tile `first run of the slice` + w of a slice (its row indices are fetched here, with the others)
@@ -398,6 +415,12 @@ __global__ __launch_bounds__(64 * WAVES, 4) void attn_bf16_kernel(AttnP p) {
       }
     }
     __syncthreads();  // everybody's DMA has landed, the ones page is written
+  }
+  {
+    const int4 a = *reinterpret_cast<const int4*>(s_live), b = *reinterpret_cast<const int4*>(s_live + 4);
+    const int live = __builtin_amdgcn_readfirstlane(max(max(max(a.x, a.y), max(a.z, a.w)), max(max(b.x, b.y), max(b.z, b.w))));
+    nqt = (live + 31) >> 5;
+    if (qt_first >= nqt) qt_first = -1;  // the pre-assigned tile has no kept row (its query rows were fetched for nothing)
   }
   if (!ATTN_PRIO_OUTSIDE) __builtin_amdgcn_s_setprio(0);
   ATTN_STAMP(t1);

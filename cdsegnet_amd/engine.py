@@ -187,6 +187,13 @@ class Level:
             self.set_pad(key, K, offs_pad, patch_start, up[:a], up[a:b], up[b:])
         return self._pad[key]
 
+    def attn_l2(self, patch_size, enable_flash):
+        """sum over patches of L * L_kept: the (key, query) pairs attention computes.  The slots a scene's last patch borrows
+        from the patch before are keys only - the kernel hands out no query tile behind a patch's last kept slot - so each of
+        the n_pad - n borrowed slots takes K pairs off sum_L2 (scenes of at most K points are not padded)."""
+        K, n_pad, _, _, _, _, sum_l2 = self.pad(patch_size, enable_flash)
+        return sum_l2 - float(K) * (n_pad - self.n)
+
     def slots(self, curve, patch_size, enable_flash):
         lz = self._slot_lazy.pop((curve, patch_size, enable_flash), None) if self._slot_lazy else None
         if lz is not None:
@@ -310,7 +317,7 @@ class Engine:
         self.fork_stage = int(os.environ["CDSEG_FORK_STAGE"]) if os.environ.get("CDSEG_FORK_STAGE") else 2
         self._work_lock = threading.Lock()
         self._tls = threading.local()  # per host thread: device-RNG cursor
-        self.attn_work = 0.0  # algorithmic attention FLOPs issued so far (4 * 16 * H * sum_p L_p^2 per launch)
+        self.attn_work = 0.0  # algorithmic attention FLOPs issued so far (4 * 16 * H * sum_p L_p * kept queries of p per launch)
         # algorithmic HBM bytes of the k = 3 sparse convs issued so far: features in + out, the kernel map as stored
         # (27 x int32 per point), the weights once per launch
         self.conv_bytes = 0.0
@@ -1050,7 +1057,7 @@ class Engine:
             att = mod.attn
             gidx, widx = lv.slots(st.curves[att.order_index], att.patch_size, att.enable_flash)
             _, _, _, _, patch_start, max_len, sum_l2 = lv.pad(att.patch_size, att.enable_flash)
-            self.attn_work += 64.0 * att.num_heads * sum_l2
+            self.attn_work += 64.0 * att.num_heads * lv.attn_l2(att.patch_size, att.enable_flash)
             self.attn_bytes += 4.0 * n * c * st.xc.element_size()
             self._count_conv(n, c, st.xc.element_size())
             desc = self.block_desc[pre]
@@ -1099,7 +1106,8 @@ class Engine:
         curve = st.curves[att.order_index]
         gidx, widx = lv.slots(curve, att.patch_size, att.enable_flash)
         _, _, _, _, patch_start, max_len, sum_l2 = lv.pad(att.patch_size, att.enable_flash)
-        self._add_work(64.0 * att.num_heads * sum_l2, 4.0 * n * c * qkv.element_size())
+        work = 64.0 * att.num_heads * lv.attn_l2(att.patch_size, att.enable_flash)
+        self._add_work(work, 4.0 * n * c * qkv.element_size())
         o = self._buf(n, c, self.T)
         if self.exact_attention_core and self.T != torch.float32:
             # error-budget tool only (tools/bf16_budget.py): the attention core in fp32 on the 16-bit q k v
@@ -1112,7 +1120,7 @@ class Engine:
             o.copy_(o32)
         else:
             ops.attention(qkv[:, :c], qkv[:, c:2 * c], qkv[:, 2 * c:], gidx, gidx, widx, patch_start, att.num_heads,
-                          max_len, att.scale, o, work=64.0 * att.num_heads * sum_l2, flags=aflags)
+                          max_len, att.scale, o, work=work, flags=aflags)
         hid = w[pre + ".fc1.w"].shape[0]
         if xs is not None:  # deep stages: proj + LN2 + MLP, one launch (+ the reduce launch of a split one)
             st.xc = self._buf(n, c, self.T)
@@ -1251,10 +1259,11 @@ class Engine:
         q_gidx, widx = lv.slots(nst.curves[att.order_index], K, att.enable_flash)
         kv_gidx, _ = clv.slots(cst.curves[att.order_index], K, att.enable_flash)
         _, _, _, _, patch_start, max_len, sum_l2 = lv.pad(K, att.enable_flash)
-        self._add_work(64.0 * att.num_heads * sum_l2, 4.0 * n * cq * q.element_size())
+        work = 64.0 * att.num_heads * lv.attn_l2(K, att.enable_flash)
+        self._add_work(work, 4.0 * n * cq * q.element_size())
         o = self._buf(n, cq, self.T)
         ops.attention(q, kv[:, :cq], kv[:, cq:], q_gidx, kv_gidx, widx, patch_start, att.num_heads, max_len, att.scale, o,
-                      work=64.0 * att.num_heads * sum_l2, flags=ops.ATTN_Q_PRESCALED if self.q_prescaled else 0)
+                      work=work, flags=ops.ATTN_Q_PRESCALED if self.q_prescaled else 0)
         if "x.tail_img" in w and n >= ops.DEEP512_MIN_ROWS:
             nst.xc = self._buf(n, cq, self.T)
             ops.attn_tail_rr(o, w["x.tail_img"], w["x.proj.b"], w["x.q_norm2.g"], w["x.q_norm2.b"], w["x.fc1.b"], w["x.fc2.b"],
@@ -1279,8 +1288,8 @@ class Engine:
     # ------------------------------------------------------------------ accounting
     def forward_work(self, plan):
         """Algorithmic FLOPs (2 x multiply-add) of ONE single-step forward on `plan`, by kernel class - SURVEY.md 8(d)'s
-        formulas on the plan's real sizes: sparse convs count the OCCUPIED neighbours only, attention 4 * L^2 * 16 per
-        patch-head, the dead c-decoder is not counted.  Synchronises (reads the kernel maps' occupancy): for reports."""
+        formulas on the plan's real sizes: sparse convs count the OCCUPIED neighbours only, attention 4 * L * L_kept * 16
+        per patch-head (Level.attn_l2: borrowed padding slots are keys, not queries), the dead c-decoder is not counted.  Synchronises (reads the kernel maps' occupancy): for reports."""
         bb, w = self.model.backbone, self.w
         cache = {}
 
@@ -1298,7 +1307,7 @@ class Engine:
             if c > 64 or self.T == torch.float32:
                 deep[0] += 2.0 * occ(lv, 3) * c * c
             out["linear"] += 2.0 * lv.n * (5.0 * c * c + 2.0 * c * hid)
-            out["attention"] += 64.0 * mod.attn.num_heads * lv.pad(mod.attn.patch_size, mod.attn.enable_flash)[6]
+            out["attention"] += 64.0 * mod.attn.num_heads * lv.attn_l2(mod.attn.patch_size, mod.attn.enable_flash)
 
         def stages(branch, cum, n_stages):
             for s in range(n_stages):
@@ -1324,7 +1333,7 @@ class Engine:
             out["conv"] += 2.0 * occ(lq, 3) * cq * cq + 2.0 * occ(lc, 3) * ck * ck
             deep[0] += 2.0 * occ(lq, 3) * cq * cq + 2.0 * occ(lc, 3) * ck * ck
             out["linear"] += 2.0 * lq.n * (cq * cq * 3 + 2.0 * cq * w["x.fc1.w"].shape[0]) + 2.0 * lc.n * (ck * ck + ck * 2 * cq)
-            out["attention"] += 64.0 * cb.attn.num_heads * lq.pad(cb.attn.q_patch_size, cb.attn.enable_flash)[6]
+            out["attention"] += 64.0 * cb.attn.num_heads * lq.attn_l2(cb.attn.q_patch_size, cb.attn.enable_flash)
         for s in reversed(range(bb.n_num_stages - 1)):
             lf, lc = plan.levels[plan.n_cum[s]], plan.levels[plan.n_cum[s + 1]]
             pre = f"n_dec{s}.up"

@@ -666,6 +666,9 @@ def attn_tail_fused(o, wp, bp, ln_g, ln_b, w1, b1, w2, b2, x, xc=None, eps=1e-5)
 # library read the CDSEG_DEEP512_MIN_ROWS environment knob (csrc/runtime.hip); the binding path follows the same variable so
 # that the two executors never disagree under an A/B run
 DEEP512_MIN_ROWS = int(os.environ.get("CDSEG_DEEP512_MIN_ROWS", 2560))
+# csrc/deep.hip DEEP512_ROWS64_MIN: from this many rows a C = 512 head / tail launch runs 64-row tiles (8 waves x 64 channels)
+# instead of 32-row ones; the results are bit-identical, the constant is here for the tests and tools that compare the two
+DEEP512_ROWS64_MIN = 256 * 32 + 1
 DEEP_CHANNELS = (128, 256, 512)  # deep-stage head / tail kernels (csrc/deep.hip): weights streamed L2 -> registers
 
 
@@ -868,7 +871,7 @@ ATTN_Q_PRESCALED, ATTN_V_BF16 = 1, 2  # include/cdseg.h: producer-side preproces
 def attention(q, k, v, q_gidx, kv_gidx, widx, patch_start, num_heads, max_len, scale, out, work=0.0, flags=0):
     """q/k/v: 2-D views (rows, H*16) of the projection buffers (any row stride); out (rows, H*16).
     flags: ATTN_Q_PRESCALED (q carries scale * log2 e: `scale` ignored) | ATTN_V_BF16 (v is bfloat16 in the half build too).
-    work: algorithmic FLOPs of this launch (4 * 16 * H * sum_p L_p^2), only used by the bench timer."""
+    work: algorithmic FLOPs of this launch (4 * 16 * H * sum_p L_p * kept queries of p), only used by the bench timer."""
     num_patches = patch_start.numel() - 1
     if not (q.dtype == k.dtype == out.dtype) or (v.dtype != q.dtype and not (flags & ATTN_V_BF16)):
         raise _lib.CdsegError("attention: q, k, v, out must share a dtype")

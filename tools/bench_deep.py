@@ -1,19 +1,33 @@
 #!/usr/bin/env python3
 """Deep-stage Block head / tail (csrc/deep.hip, C = 128 / 256 / 512) against the separate GEMM launches they replace, on
-stage-shaped problems.  usage: python tools/bench_deep.py [scenes=8] [f16|bf16]"""
+stage-shaped problems.  usage: python tools/bench_deep.py [scenes=8] [f16|bf16] [rows=N,N,...]
+  rows=...   the C = 512 head and tail alone at these row counts (the 32- / 64-row tile threshold sweep): median and min of
+             seven timed groups per launch
+  CDSEG_AB_LIB=path/to/other/libcdseg_hip.so  benchmark another build of the library (its libcdseg_hip_f16.so is taken from
+             the same directory; A/B runs, tools only).  Experimental builds read CDSEG_DEEP512_ROWS64_MIN (rows from which
+             C = 512 runs 64-row tiles)."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from cdsegnet_amd import _lib, ops
+from cdsegnet_amd import _lib
+if os.environ.get("CDSEG_AB_LIB"):
+    _lib.LIB_PATH = os.path.abspath(os.environ["CDSEG_AB_LIB"])
+    _lib.LIB_PATH_F16 = os.path.join(os.path.dirname(_lib.LIB_PATH), "libcdseg_hip_f16.so")
+from cdsegnet_amd import ops
 from tools.bench_gemm import time_op
 
-scenes = int(sys.argv[1]) if len(sys.argv) > 1 else 8
-variant = sys.argv[2] if len(sys.argv) > 2 else "f16"
+args = [a for a in sys.argv[1:] if not a.startswith("rows=")]
+rows = [int(v) for a in sys.argv[1:] if a.startswith("rows=") for v in a[5:].split(",")]
+scenes = int(args[0]) if len(args) > 0 else 8
+variant = args[1] if len(args) > 1 else "f16"
 _lib.activate(variant)
 dev = torch.device("cuda")
 bf = torch.float16 if variant == "f16" else torch.bfloat16
+tag = os.path.basename(os.path.dirname(_lib.LIB_PATH)) if os.environ.get("CDSEG_AB_LIB") else "tree"
 shapes = ((14293 * scenes, 128), (3364 * scenes, 256), (778 * scenes, 128), (778 * scenes, 512), (778, 512), (3364, 256),
           (14293, 128))
+if rows:
+    shapes = tuple((n, 512) for n in rows)
 for n, C in shapes:
     r = lambda *s: torch.randn(*s, device=dev)  # noqa: E731
     y, o = r(n, C).to(bf), r(n, C).to(bf)
@@ -38,6 +52,13 @@ for n, C in shapes:
             ops.gemm(u, w2, x, bias=b2, res=x, out2=xc)
 
     hf, tf = 2.0 * n * 4 * C * C / 1e6, 2.0 * n * 9 * C * C / 1e6  # MFLOP
+    if rows:  # the two fused launches alone (the residual stream is rewritten in place: its values do not matter to the time)
+        for name, fl, fn in (("head", hf, lambda: ops.cpe_head_rr(y, himg, bl, (g1, e1), x, None, (g2, e2), bq, qkv)),
+                             ("tail", tf, lambda: ops.attn_tail_rr(o, timg, bp, g1, e1, b1, b2, x, xc))):
+            us = sorted(time_op(fn, 10) for _ in range(7))
+            print(f"{name}[{tag} {variant}] n={n} C={C}: median {us[3]:.1f} us (min {us[0]:.1f}, max {us[-1]:.1f}), "
+                  f"{fl / us[3]:.0f} TFLOP/s", flush=True)
+        continue
     t_old = time_op(head_old, 10)
     t_new = time_op(lambda: ops.cpe_head_rr(y, himg, bl, (g1, e1), x, None, (g2, e2), bq, qkv), 10)
     print(f"head n={n} C={C}: separate launches {t_old:.1f} us, fused {t_new:.1f} us ({hf / t_new:.0f} TFLOP/s)")
