@@ -671,6 +671,161 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradP p) {
   }
 }
 
+// ---- the same weight gradient on 16-bit operands (the AMP step): dY and X are of the build's 16-bit type, products are
+//      exact and every sum is fp32 (v_mfma_f32_32x32x16_{f16,bf16} accumulators, fp32 atomics; nothing is rounded to 16 bits).
+//      The reduction index m is the ROW index of both operands, so both MFMA operands are column reads of row-major tiles:
+//      a chunk of W16_ROWS rows of dY [rows][32 TN] and of (gathered) X [rows][32 TK] is staged row-major in LDS with 16-byte
+//      loads and read with ds_read_b64_tr_b16 (as attn_bwd16_kv_kernel reads its transposed operands).
+//      LDS image: one [W16_ROWS][32 columns] sub-image (64-byte rows, 4 KiB) per 32 columns.  A transposed read of a 32-lane
+//      half takes rows r .. r + 3 x 32 columns = 256 contiguous bytes: all 64 banks once.
+//      A block is 4 waves = a (32 TN) x (32 TK) tile of dW in 32 x 32 sub-tiles; wave w owns sub-tiles w, w + 4, ...
+//      Columns past N / K are staged as zeros (C = 16 runs as a zero-padded 32-wide tile) and never stored.
+//      Two LDS buffers: chunk c + 1 is loaded into registers while chunk c feeds the MFMAs, one barrier per chunk.  The
+//      barrier also votes on whether chunk c + 1 has any live row (conv offsets are sparse): a dead chunk is not staged.
+//      EXEC is all ones at every transposed read: branches around them are block- or wave-uniform, tiles are padded.
+constexpr int W16_ROWS = 64;       // rows of a chunk (4 MFMA k-steps of 16)
+constexpr int W16_SUB = W16_ROWS * 64;  // bytes of one 32-column sub-image
+
+struct Wgrad16P {
+  const bf16_t* dy; const bf16_t* x; const int32_t* xidx; float* dw; float* db;
+  long M, rows_per_split, idx_stride;
+  int N, K, lddy, ldx, lddw;
+  int splits, dw_off_stride;
+};
+
+template <int TN, int TK>
+__global__ __launch_bounds__(256) void wgrad16_kernel(Wgrad16P p) {
+  constexpr int IMG = (TN + TK) * W16_SUB;               // one buffer: TN sub-images of dY, then TK of X
+  constexpr int CN = TN * 4, CK = TK * 4;                // 16-byte column chunks per staged row
+  constexpr int RN = 256 / CN, RK = 256 / CK;            // rows a pass of the block's 256 threads covers
+  constexpr int NSUB = TN * TK, SPW = (NSUB + 3) / 4;    // sub-tiles, sub-tiles per wave
+  __shared__ __attribute__((aligned(16))) char smem[2 * IMG];
+  const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n0 = blockIdx.x * (32 * TN), k0 = blockIdx.y * (32 * TK);
+  const int off = blockIdx.z / p.splits;
+  const long m_begin = (long)(blockIdx.z - off * p.splits) * p.rows_per_split;
+  const long m_end = min(p.M, m_begin + p.rows_per_split);
+  const int32_t* xidx = p.xidx ? p.xidx + off * p.idx_stride : nullptr;
+  float* dw = p.dw + (long)off * p.dw_off_stride;
+  const bool want_db = p.db && blockIdx.y == 0 && off == 0;
+  // staging: thread -> (row tid / CN + j RN, chunk tid % CN) of dY, (row tid / CK + j RK, chunk tid % CK) of X
+  const int cn = tid % CN, rn = tid / CN, ck = tid % CK, rk = tid / CK;
+  const bool n_ok = n0 + 8 * cn < p.N, k_ok = k0 + 8 * ck < p.K;
+  const bf16_t* dyp = p.dy + n0 + 8 * cn;
+  const bf16_t* xp = p.x + k0 + 8 * ck;
+  const int st_n = (cn >> 2) * W16_SUB + rn * 64 + (cn & 3) * 16;
+  const int st_k = (TN + (ck >> 2)) * W16_SUB + rk * 64 + (ck & 3) * 16;
+  uint4 gn[TN], gk[TK];
+  int32_t ridx[TK];  // gathered form: the thread's row indices of the chunk the next fetch() stages, loaded a chunk ahead
+  float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  auto fetch_idx = [&](long m0) {
+#pragma unroll
+    for (int j = 0; j < TK; ++j) {
+      const long m = m0 + rk + j * RK;
+      ridx[j] = (xidx && m < m_end) ? xidx[m] : -1;
+    }
+  };
+  auto fetch = [&](long m0) -> bool {  // chunk m0 .. m0 + 63 into registers; true: this thread saw a live row
+    bool live = false;
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      const long m = m0 + rn + j * RN;
+      gn[j] = make_uint4(0, 0, 0, 0);
+      if (n_ok && m < m_end) gn[j] = *reinterpret_cast<const uint4*>(dyp + m * p.lddy);
+    }
+#pragma unroll
+    for (int j = 0; j < TK; ++j) {
+      const long m = m0 + rk + j * RK;
+      gk[j] = make_uint4(0, 0, 0, 0);
+      const long row = xidx ? (long)ridx[j] : (m < m_end ? m : -1);
+      if (row >= 0) {
+        live = true;
+        if (k_ok) gk[j] = *reinterpret_cast<const uint4*>(xp + row * p.ldx);
+      }
+    }
+    fetch_idx(m0 + W16_ROWS);  // (the indices arrive while this chunk's rows do: the gather never waits for them)
+    return live || want_db;
+  };
+  // operands: lane (i = lane & 31, h = lane >> 5) holds rows 8 h .. 8 h + 7 of a 16-row k-step at column i of its sub-image;
+  // its 16-lane group g reads columns 16 (g & 1) ..: lane 4 q + pp of the group addresses row q, columns 4 pp .. 4 pp + 3
+  const int tr = (8 * (lane >> 5) + ((lane & 15) >> 2)) * 64 + ((lane >> 4) & 1) * 32 + (lane & 3) * 8;
+  int sub_n[SPW], sub_k[SPW];
+#pragma unroll
+  for (int j = 0; j < SPW; ++j) {
+    const int s = wave + 4 * j;
+    sub_n[j] = s % TN; sub_k[j] = (s / TN) % TK;  // (a wave without a sub-tile repeats one and stores nothing)
+  }
+  f32x16_t acc[SPW];
+#pragma unroll
+  for (int j = 0; j < SPW; ++j)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+  const bool has_work = wave < NSUB;  // wave-uniform
+  fetch_idx(m_begin);
+  bool live = __syncthreads_or(fetch(m_begin)) != 0;
+  int buf = 0;
+  for (long m0 = m_begin; m0 < m_end; m0 += W16_ROWS) {
+    if (live) {  // block-uniform
+      char* img = smem + buf * IMG;
+#pragma unroll
+      for (int j = 0; j < TN; ++j) *reinterpret_cast<uint4*>(img + st_n + j * RN * 64) = gn[j];
+#pragma unroll
+      for (int j = 0; j < TK; ++j) *reinterpret_cast<uint4*>(img + st_k + j * RK * 64) = gk[j];
+      if (want_db) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+          float lo, hi;
+          unpack_bf16x2(gn[j].x, lo, hi); bsum[0] += lo; bsum[1] += hi;
+          unpack_bf16x2(gn[j].y, lo, hi); bsum[2] += lo; bsum[3] += hi;
+          unpack_bf16x2(gn[j].z, lo, hi); bsum[4] += lo; bsum[5] += hi;
+          unpack_bf16x2(gn[j].w, lo, hi); bsum[6] += lo; bsum[7] += hi;
+        }
+      }
+    }
+    const bool was_live = live;
+    const bool mine = m0 + W16_ROWS < m_end ? fetch(m0 + W16_ROWS) : false;  // next chunk's loads fly over the MFMAs below
+    live = __syncthreads_or(mine) != 0;
+    if (was_live && has_work) {
+      const unsigned img = lds_base + buf * IMG + tr;
+#pragma unroll
+      for (int ks = 0; ks < W16_ROWS / 16; ++ks) {
+#pragma unroll
+        for (int j = 0; j < SPW; ++j) {
+          const unsigned a = img + sub_n[j] * W16_SUB + ks * 1024, b = img + (TN + sub_k[j]) * W16_SUB + ks * 1024;
+          acc[j] = mfma_32x32x16_bf16(b16_tr_pair(a, a + 256), b16_tr_pair(b, b + 256), acc[j]);
+        }
+      }
+    }
+    if (was_live) buf ^= 1;
+  }
+  // D[i][jj]: lane holds column jj = lane & 31 (k), rows i = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) (n)
+#pragma unroll
+  for (int j = 0; j < SPW; ++j) {
+    if (wave + 4 * j >= NSUB) continue;
+    const int kk = k0 + 32 * sub_k[j] + (lane & 31);
+    const int nb = n0 + 32 * sub_n[j] + 4 * (lane >> 5);
+    if (kk >= p.K) continue;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int nn = nb + (r & 3) + 8 * (r >> 2);
+      if (nn < p.N) atomicAdd(dw + (long)nn * p.lddw + kk, acc[j][r]);
+    }
+  }
+  if (want_db) {  // (block-uniform) the threads' column sums: one fp32 sum per column in LDS, one atomic per column
+    __syncthreads();
+    float* red = reinterpret_cast<float*>(smem);  // [RN][32 TN]
+#pragma unroll
+    for (int e = 0; e < 8; ++e) red[rn * (32 * TN) + 8 * cn + e] = bsum[e];
+    __syncthreads();
+    if (tid < 32 * TN && n0 + tid < p.N) {
+      float s = 0.f;
+      for (int r = 0; r < RN; ++r) s += red[r * (32 * TN) + tid];
+      atomicAdd(p.db + n0 + tid, s);
+    }
+  }
+}
+
 }  // namespace
 
 extern "C" size_t cdseg_attention_bwd_ws_bytes(long num_slots, int num_heads) {
@@ -788,4 +943,68 @@ extern "C" int cdseg_conv_wgrad(const float* x, int ldx, const int32_t* nbr_kmaj
   p.dy = dy; p.x = x; p.xidx = nbr_kmajor; p.dw = dw; p.db = db; p.M = m; p.N = cout; p.K = cin; p.lddy = lddy; p.ldx = ldx;
   p.lddw = kvol * cin; p.idx_stride = m; p.dw_off_stride = cin;
   return launch_wgrad(p, kvol, (hipStream_t)stream);
+}
+
+template <int TN, int TK>
+static void launch_wgrad16_tile(const Wgrad16P& p, int noff, hipStream_t stream) {
+  hipLaunchKernelGGL((wgrad16_kernel<TN, TK>), dim3((unsigned)cdiv(p.N, 32 * TN), (unsigned)cdiv(p.K, 32 * TK), (unsigned)(p.splits * noff)),
+                     dim3(256), 0, stream, p);
+}
+
+// Tile: the narrowest of 32 / 64 / 128 columns that covers N (K), so the narrow stages read dY and X once (C = 32: dW 96 x 32
+// is one tile); 128 x 128 would need 64 KiB of LDS, the deep stages take 128 x 64.  Rows are split over the grid as in
+// launch_wgrad: ~2 blocks per CU, at least 512 rows (8 chunks) per block so a tile's atomics stay rare next to its loads.
+static int launch_wgrad16(Wgrad16P p, int noff, hipStream_t stream) {
+  const int tn = p.N > 64 ? 4 : p.N > 32 ? 2 : 1;
+  int tk = p.K > 64 ? 4 : p.K > 32 ? 2 : 1;
+  if (tn == 4 && tk == 4) tk = 2;
+  const long tiles = (long)cdiv(p.N, 32 * tn) * cdiv(p.K, 32 * tk) * noff;
+  long splits = (512 + tiles - 1) / tiles;
+  const long max_splits = (p.M + 511) / 512;
+  if (splits > max_splits) splits = max_splits;
+  if (splits < 1) splits = 1;
+  p.rows_per_split = ((p.M + splits - 1) / splits + W16_ROWS - 1) / W16_ROWS * W16_ROWS;
+  splits = (p.M + p.rows_per_split - 1) / p.rows_per_split;
+  if (splits * noff > 65535) return CDSEG_ERR_UNSUPPORTED;
+  p.splits = (int)splits;
+  switch (tn * 8 + tk) {
+    case 1 * 8 + 1: launch_wgrad16_tile<1, 1>(p, noff, stream); break;
+    case 1 * 8 + 2: launch_wgrad16_tile<1, 2>(p, noff, stream); break;
+    case 1 * 8 + 4: launch_wgrad16_tile<1, 4>(p, noff, stream); break;
+    case 2 * 8 + 1: launch_wgrad16_tile<2, 1>(p, noff, stream); break;
+    case 2 * 8 + 2: launch_wgrad16_tile<2, 2>(p, noff, stream); break;
+    case 2 * 8 + 4: launch_wgrad16_tile<2, 4>(p, noff, stream); break;
+    case 4 * 8 + 1: launch_wgrad16_tile<4, 1>(p, noff, stream); break;
+    default: launch_wgrad16_tile<4, 2>(p, noff, stream); break;
+  }
+  CDSEG_CHECK_LAUNCH();
+  return CDSEG_OK;
+}
+
+static bool wgrad16_args_ok(const void* x, int ldx, const void* xidx, const void* dy, int lddy, const void* dw, const void* db) {
+  if (!x || !dy || !dw) return false;
+  if ((ldx | lddy) & 7) return false;  // 16-byte operand loads: eight 16-bit values
+  return ((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dw | (uintptr_t)db | (uintptr_t)xidx) & 15) == 0);
+}
+
+extern "C" int cdseg_linear_wgrad16(const void* x, int ldx, const int32_t* xidx, const void* dy, int lddy, long m, int k, int n,
+                                    float* dw, int lddw, float* db, void* stream) {
+  if (m <= 0 || n <= 0 || k <= 0) return CDSEG_OK;
+  if (!wgrad16_args_ok(x, ldx, xidx, dy, lddy, dw, db)) return CDSEG_ERR_ARG;
+  if ((n & 15) || (k & 15)) return CDSEG_ERR_UNSUPPORTED;
+  Wgrad16P p;
+  p.dy = (const bf16_t*)dy; p.x = (const bf16_t*)x; p.xidx = xidx; p.dw = dw; p.db = db; p.M = m; p.N = n; p.K = k; p.lddy = lddy;
+  p.ldx = ldx; p.lddw = lddw; p.idx_stride = 0; p.dw_off_stride = 0;
+  return launch_wgrad16(p, 1, (hipStream_t)stream);
+}
+
+extern "C" int cdseg_conv_wgrad16(const void* x, int ldx, const int32_t* nbr_kmajor, int kvol, const void* dy, int lddy, long m,
+                                  int cin, int cout, float* dw, float* db, void* stream) {
+  if (m <= 0 || kvol <= 0) return CDSEG_OK;
+  if (!nbr_kmajor || !wgrad16_args_ok(x, ldx, nbr_kmajor, dy, lddy, dw, db)) return CDSEG_ERR_ARG;
+  if ((cin & 15) || (cout & 15)) return CDSEG_ERR_UNSUPPORTED;
+  Wgrad16P p;
+  p.dy = (const bf16_t*)dy; p.x = (const bf16_t*)x; p.xidx = nbr_kmajor; p.dw = dw; p.db = db; p.M = m; p.N = cout; p.K = cin;
+  p.lddy = lddy; p.ldx = ldx; p.lddw = kvol * cin; p.idx_stride = m; p.dw_off_stride = cin;
+  return launch_wgrad16(p, kvol, (hipStream_t)stream);
 }

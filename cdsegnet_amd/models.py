@@ -426,6 +426,8 @@ class DefaultSegmentorV2(nn.Module):
         self.precision = "fp16+head"
         # training forward: "fp32" (default: exact fp32) | "fp16-attn" | "bf16-attn": the attention core (forward and backward,
         # self and cross attention) in IEEE half / bfloat16 like the reference's flash-attention path, everything else fp32;
+        # "fp16-amp" | "bf16-amp": the reference's AMP setting (enable_amp = True): that attention core, and every trunk Linear
+        # and sparse conv (forward, data gradient, weight gradient) on 16-bit products with fp32 accumulation and fp32 outputs;
         # read at every forward(), anything else raises ValueError there
         self.train_precision = "fp32"
         self._lanes = {}
@@ -576,8 +578,8 @@ class DefaultSegmentorV2(nn.Module):
 
     def forward(self, input_dict, draws=None):
         """Training forward (ref: default.py:424-493): returns dict(loss=...) under torch autograd - `loss.backward()` fills
-        the `.grad` of this module's parameters like the reference's does (engines/train.py:216-271).  fp32, or with a 16-bit
-        attention core (`train_precision`), on the HIP kernels behind torch.autograd.Functions: cdsegnet_amd/train_graph.py.
+        the `.grad` of this module's parameters like the reference's does (engines/train.py:216-271).  fp32, with a 16-bit
+        attention core, or under AMP (16-bit Linears and sparse convs too; `train_precision`), on the HIP kernels behind torch.autograd.Functions: cdsegnet_amd/train_graph.py.
         `draws` replays recorded random draws."""
         from .train_graph import TrainGraph
         if getattr(self, "_train_graph", None) is None:

@@ -1196,27 +1196,50 @@ def gelu_bwd(u, dy):
     return dx
 
 
+def _wgrad_operands(what, x, dy, dw, db):
+    """fp32 operands -> False; the active build's 16-bit type -> True (x and dy 16-byte aligned rows); dw / db are fp32."""
+    if x.dtype != dy.dtype:
+        raise _lib.CdsegError(f"{what}: x and dy must share a dtype")
+    if dw.dtype != torch.float32 or (db is not None and db.dtype != torch.float32):
+        raise _lib.CdsegError(f"{what}: dw, db are fp32 (accumulated into)")
+    if x.dtype == torch.float32:
+        return False
+    dt(x)  # (a 16-bit tensor of the other build's type raises here)
+    for t in (x, dy):
+        if t.stride(0) % 8 or t.data_ptr() % 16:
+            raise _lib.CdsegError(f"{what}: rows must be 16-byte aligned (eight 16-bit values per operand load)")
+    return True
+
+
 def linear_wgrad(x, dy, dw, db=None, xidx=None):
-    """dw (N, K view, any row stride) += dy^T x[xidx or arange] and db (N) += column sums of dy; fp32 (cdseg_linear_wgrad).
-    xidx (M) int32 with -1 = no row: one kernel offset of a submanifold conv."""
+    """dw (N, K view, any row stride) += dy^T x[xidx or arange] and db (N) += column sums of dy (cdseg_linear_wgrad).
+    xidx (M) int32 with -1 = no row: one kernel offset of a submanifold conv.  x and dy share a dtype: fp32, or the active
+    build's 16-bit type (cdseg_linear_wgrad16: exact products, fp32 sums); dw / db are fp32 either way."""
     _need_gpu(x, dy, dw)
-    assert x.dtype == dy.dtype == dw.dtype == torch.float32 and dy.stride(1) == 1 and x.stride(1) == 1 and dw.stride(1) == 1
+    lp = _wgrad_operands("linear_wgrad", x, dy, dw, db)
+    assert dy.stride(1) == 1 and x.stride(1) == 1 and dw.stride(1) == 1
     m, n = dy.shape
     k = x.shape[1]
     assert tuple(dw.shape) == (n, k) and (xidx is None or (xidx.dtype == torch.int32 and xidx.numel() == m))
-    check(_lib.load().cdseg_linear_wgrad(_ptr(x), x.stride(0), _ptr(xidx), _ptr(dy), dy.stride(0), m, k, n, _ptr(dw),
-                                         dw.stride(0), _ptr(db), _stream()), "linear_wgrad")
+    lib = _lib.load()
+    fn = lib.cdseg_linear_wgrad16 if lp else lib.cdseg_linear_wgrad
+    check(fn(_ptr(x), x.stride(0), _ptr(xidx), _ptr(dy), dy.stride(0), m, k, n, _ptr(dw), dw.stride(0), _ptr(db), _stream()),
+          "linear_wgrad")
     return dw
 
 
 def conv_wgrad(x, nbr_kmajor, dy, dw3, db=None):
     """dw3 (Cout, kvol, Cin) += the weight gradient of a submanifold conv over all kernel offsets (one launch), db += the
-    bias gradient; nbr_kmajor (kvol, M) int32 offset-major kernel map.  fp32 (cdseg_conv_wgrad)."""
+    bias gradient; nbr_kmajor (kvol, M) int32 offset-major kernel map.  fp32 (cdseg_conv_wgrad), or x and dy of the active
+    build's 16-bit type with fp32 dw3 / db (cdseg_conv_wgrad16)."""
     _need_gpu(x, dy, dw3)
+    lp = _wgrad_operands("conv_wgrad", x, dy, dw3, db)
     kvol, m = nbr_kmajor.shape
     cout, kv, cin = dw3.shape
-    assert kv == kvol and dw3.is_contiguous() and x.dtype == dy.dtype == dw3.dtype == torch.float32
+    assert kv == kvol and dw3.is_contiguous() and dy.stride(1) == 1 and x.stride(1) == 1
     assert nbr_kmajor.dtype == torch.int32 and nbr_kmajor.is_contiguous() and dy.shape == (m, cout) and x.shape[1] == cin
-    check(_lib.load().cdseg_conv_wgrad(_ptr(x), x.stride(0), _ptr(nbr_kmajor), kvol, _ptr(dy), dy.stride(0), m, cin, cout,
-                                       _ptr(dw3), _ptr(db), _stream()), "conv_wgrad")
+    lib = _lib.load()
+    fn = lib.cdseg_conv_wgrad16 if lp else lib.cdseg_conv_wgrad
+    check(fn(_ptr(x), x.stride(0), _ptr(nbr_kmajor), kvol, _ptr(dy), dy.stride(0), m, cin, cout, _ptr(dw3), _ptr(db), _stream()),
+          "conv_wgrad")
     return dw3

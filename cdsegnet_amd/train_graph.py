@@ -20,7 +20,14 @@ unchanged - and underneath, every product that carries the FLOPs runs on this li
 in exact fp32 by default.  The reference never runs its attention core in fp32 on a GPU (`qkv.half()` into flash-attention,
 whose backward is half too): `model.train_precision = "fp16-attn"` / `"bf16-attn"` runs the attention core of every Block
 and of the cross attention in 16 bits - the inference path's 16-bit forward kernel and the recompute-P backward on the 16-bit
-matrix pipe (csrc/train.hip), fp32 dq / dk / dv - and leaves everything else in fp32.  What stays plain torch device ops: train-mode BatchNorm1d (3 per pooling stage, batch
+matrix pipe (csrc/train.hip), fp32 dq / dk / dv - and leaves everything else in fp32.
+`"fp16-amp"` / `"bf16-amp"` is the reference's AMP setting (`enable_amp = True`: torch.cuda.amp.autocast around the model,
+engines/train.py:226-240): the same attention core, and every trunk Linear and sparse conv as `_Linear16` / `_SubMConv16` -
+input and weight rounded once to the 16-bit type, forward and data gradient by cdseg_gemm on 16-bit operands, the weight
+gradient by cdseg_linear_wgrad16 / cdseg_conv_wgrad16, fp32 accumulation throughout, the 16-bit input saved for the backward,
+dy cast without saturation so that a GradScaler sees an overflow.  The residual stream, LayerNorm, GELU, BatchNorm sites,
+heads, timestep MLP, criteria, parameters and .grad stay fp32.  ONE difference from torch autocast: autocast also rounds each
+Linear's OUTPUT to fp16; here the outputs stay fp32 (operand rounding and fp32 accumulation are the same).  What stays plain torch device ops: train-mode BatchNorm1d (3 per pooling stage, batch
 statistics), GELU between them, the swish timestep MLP on B rows, row masks of stochastic depth, q_sample, the two
 (C -> classes) heads, and the criteria (cdsegnet_amd.losses).  All integer work - serialization, pooling structure,
 kernel maps, padded patch plans - is the inference engine's plan (Engine.build_plan), shared with the inference path.
@@ -112,13 +119,101 @@ class _Linear(torch.autograd.Function):
         return dx, dw, db
 
 
-def linear(x, mod):
+class _SubMConv16(torch.autograd.Function):
+    """_SubMConv on 16-bit products (the AMP step; ref: spconv's SubMConv3d under torch.cuda.amp.autocast, engines/train.py:
+    226-240): x is cast ONCE to the 16-bit type of library build `variant` with the library's cast (saturating in the half
+    build, like the inference path), the weight likewise; forward, data gradient and weight gradient are cdseg_gemm /
+    cdseg_conv_wgrad16 on 16-bit operands with fp32 accumulation and fp32 outputs.  The 16-bit x is what the backward keeps.
+    dy is cast WITHOUT saturation (torch's cast): a scaled gradient beyond half's range must reach the GradScaler as inf.
+    The 16-bit weight copies are per-call temporaries (cache=False: no cache entry may pin them)."""
+
+    @staticmethod
+    def forward(ctx, x, w5, b, nbr, variant):
+        t16 = ops.LP_DTYPES[variant]
+        cout, cin = w5.shape[0], w5.shape[-1]
+        kvol = nbr.shape[0]
+        cp = (cin + 15) // 16 * 16
+        w3 = w5.reshape(cout, kvol, cin)
+        if cp != cin:
+            x = F.pad(x, (0, cp - cin))
+            w3 = F.pad(w3, (0, cp - cin))
+        with _lib.use(variant):
+            x16 = ops.cast(_c(x), t16)
+            w16 = ops.cast(_c(w3).reshape(cout, kvol * cp), t16)
+            y = _f32((x.shape[0], cout), x)
+            ops.gemm(x16, w16, y, bias=b, nbr=nbr, kvol=kvol, nbr_kmajor=True, cache=False)
+        ctx.save_for_backward(x16, w16, nbr)
+        ctx.meta = (cin, cp, kvol, b is not None, tuple(w5.shape), variant)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x16, w16, nbr = ctx.saved_tensors
+        cin, cp, kvol, has_b, wshape, variant = ctx.meta
+        cout = w16.shape[0]
+        dy16 = _c(dy).to(x16.dtype)
+        dw3 = torch.zeros((cout, kvol, cp), dtype=torch.float32, device=dy.device)
+        db = torch.zeros(cout, dtype=torch.float32, device=dy.device) if has_b else None
+        dx = None
+        with _lib.use(variant):
+            ops.conv_wgrad(x16, nbr, dy16, dw3, db)
+            if ctx.needs_input_grad[0]:
+                wt = _c(w16.view(cout, kvol, cp).flip(1).permute(2, 1, 0)).view(cp, kvol * cout)
+                dxp = _f32((x16.shape[0], cp), dy)
+                ops.gemm(dy16, wt, dxp, nbr=nbr, kvol=kvol, nbr_kmajor=True, cache=False)
+                dx = dxp[:, :cin]
+        return dx, dw3[:, :, :cin].reshape(wshape), db, None, None
+
+
+class _Linear16(torch.autograd.Function):
+    """_Linear on 16-bit products (the AMP step): operands rounded once to the 16-bit type of library build `variant`, fp32
+    accumulation, fp32 y / dx / dw / db; the saved input is the 16-bit copy.  See _SubMConv16 for the casts."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, variant):
+        t16 = ops.LP_DTYPES[variant]
+        with _lib.use(variant):
+            x16 = ops.cast(_c(x), t16)
+            w16 = ops.cast(_c(w), t16)
+            y = _f32((x.shape[0], w.shape[0]), x)
+            ops.gemm(x16, w16, y, bias=b, cache=False)
+        ctx.save_for_backward(x16, w16)
+        ctx.meta = (b is not None, variant)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x16, w16 = ctx.saved_tensors
+        has_b, variant = ctx.meta
+        dy16 = _c(dy).to(x16.dtype)
+        dx = None
+        dw = torch.zeros(w16.shape, dtype=torch.float32, device=dy.device)
+        db = torch.zeros(w16.shape[0], dtype=torch.float32, device=dy.device) if has_b else None
+        with _lib.use(variant):
+            if ctx.needs_input_grad[0]:
+                dx = _f32(x16.shape, dy)
+                ops.gemm(dy16, _c(w16.t()), dx, cache=False)
+            ops.linear_wgrad(x16, dy16, dw, db)
+        return dx, dw, db, None
+
+
+def linear(x, mod, variant=None):
     """nn.Linear on the library's GEMMs when both widths are multiples of 16 (every Linear of the trunk); the two heads
-    (C -> classes / c_in) and the B-row timestep MLP are plain torch."""
+    (C -> classes / c_in) and the B-row timestep MLP are plain torch.  variant "f16" / "bf16": 16-bit products on that build
+    of the library (the AMP step), None: exact fp32."""
     w, b = mod.weight, mod.bias
     if w.shape[0] % 16 or w.shape[1] % 16 or x.shape[0] < 1:
         return F.linear(x, w, b)
+    if variant is not None:
+        return _Linear16.apply(x, w, b, variant)
     return _Linear.apply(x, w, b)
+
+
+def subm_conv(x, w5, b, nbr, variant=None):
+    """Submanifold conv on the offset-major kernel map; variant as in `linear`."""
+    if variant is not None:
+        return _SubMConv16.apply(x, w5, b, nbr, variant)
+    return _SubMConv.apply(x, w5, b, nbr)
 
 
 class _LayerNorm(torch.autograd.Function):
@@ -146,7 +241,8 @@ def layernorm(x, mod):
     return _LayerNorm.apply(x, mod.weight, mod.bias, float(mod.eps))
 
 
-TRAIN_PRECISIONS = {"fp32": None, "fp16-attn": "f16", "bf16-attn": "bf16"}  # train_precision -> library build of the attention core
+TRAIN_PRECISIONS = {"fp32": None, "fp16-attn": "f16", "bf16-attn": "bf16",  # train_precision -> library build of the attention core
+                    "fp16-amp": "f16", "bf16-amp": "bf16"}                   # (-amp: of the Linears and sparse convs too)
 
 
 class _Attention(torch.autograd.Function):
@@ -308,6 +404,7 @@ class TrainGraph:
     def __init__(self, model):
         self.model = model
         self.attn_variant = None  # library build of the attention core, from model.train_precision at every forward
+        self.mm_variant = None    # library build of the Linears and sparse convs ("-amp" modes), None = exact fp32
         self.eng = _engine.Engine(model, "fp32")  # the plan builder (never prepared: no second copy of the weights)
         self.criteria = build_criteria(model.criteria_cfg, model.loss_type, model.task_num)
 
@@ -331,11 +428,11 @@ class TrainGraph:
         return torch.empty((st.x.shape[0], 1), dtype=torch.float32, device=st.x.device).bernoulli_(keep) / keep
 
     def _cpe(self, lv, x, seq):
-        y = _SubMConv.apply(x, seq[0].weight, seq[0].bias, lv.nbr(seq[0].kernel_size, True))
-        return layernorm(linear(y, seq[1]), seq[2])
+        y = subm_conv(x, seq[0].weight, seq[0].bias, lv.nbr(seq[0].kernel_size, True), self.mm_variant)
+        return layernorm(linear(y, seq[1], self.mm_variant), seq[2])
 
     def _mlp(self, h, mlp):
-        return linear(F.gelu(linear(h, mlp.fc1)), mlp.fc2)
+        return linear(F.gelu(linear(h, mlp.fc1, self.mm_variant)), mlp.fc2, self.mm_variant)
 
     def _block(self, st, mod, name, t_scene, masks):
         """ref: ptv3.py:399-428."""
@@ -347,12 +444,12 @@ class TrainGraph:
             x = x + _SceneRows.apply(F.linear(t_scene, mod.t_mlp.weight, mod.t_mlp.bias), lv.batch.long(), list(lv.offs_host))
         att = mod.attn
         c = x.shape[1]
-        qkv = linear(layernorm(x, mod.norm1[0]), att.qkv)
+        qkv = linear(layernorm(x, mod.norm1[0]), att.qkv, self.mm_variant)
         gidx, widx = lv.slots(st.curves[att.order_index], att.patch_size, att.enable_flash)
         patch_start, max_len = lv.pad(att.patch_size, att.enable_flash)[4:6]
         psh = lv.pad_host(att.patch_size, att.enable_flash)[3].tolist()
         o = attention_core(self.attn_variant, qkv, None, c, gidx, gidx, widx, patch_start, psh, att.num_heads, max_len, att.scale)
-        a = linear(o, att.proj)
+        a = linear(o, att.proj, self.mm_variant)
         m = self._mask(st, name + ".drop_path.0", mod.drop_prob, masks)
         x = x + (a if m is None else a * m)
         h = self._mlp(layernorm(x, mod.norm2[0]), mod.mlp[0])
@@ -364,14 +461,14 @@ class TrainGraph:
         """ref: ptv3.py:633-663.  inv0: caller row -> physical row (the reference's level-0 order is the caller's)."""
         lv = plan.levels[0]
         x = feat[plan.perm0.long()]
-        y = _SubMConv.apply(x, emb.stem.conv.weight, None, lv.nbr(emb.stem.conv.kernel_size, True))
+        y = subm_conv(x, emb.stem.conv.weight, None, lv.nbr(emb.stem.conv.kernel_size, True), self.mm_variant)
         return _St(lv, _bn_gelu(y, emb.stem.norm), curves, inv0)
 
     def _pooling(self, plan, st, down, cum_to, perm):
         """ref: ptv3.py:464-555."""
         fine, coarse = st.level, plan.levels[cum_to]
         cluster, seg = plan.link(fine.cum, cum_to)
-        y = _SegmentMax.apply(linear(st.x, down.proj), seg, cluster, coarse.n)
+        y = _SegmentMax.apply(linear(st.x, down.proj, self.mm_variant), seg, cluster, coarse.n)
         curves = st.curves if perm is None else [st.curves[int(j)] for j in perm]
         order = coarse.order(st.curves[0])  # the reference numbers the pooled points by unique(code[0]) (ptv3.py:489)
         if order is None:
@@ -383,8 +480,8 @@ class TrainGraph:
         parent = st.parent
         fine, coarse = parent.level, st.level
         cluster, _ = plan.link(fine.cum, coarse.cum)
-        child = _bn_gelu(linear(st.x, up.proj[0]), up.proj[1])
-        par = _bn_gelu(linear(parent.x, up.proj_skip[0]), up.proj_skip[1])
+        child = _bn_gelu(linear(st.x, up.proj[0], self.mm_variant), up.proj[1])
+        par = _bn_gelu(linear(parent.x, up.proj_skip[0], self.mm_variant), up.proj_skip[1])
         out = _St(fine, None, parent.curves, parent.ref_order, parent=parent.parent)
         out.conv = par  # what the next Block's CPE conv reads: the skip feature before scaling and merging
         f = 2 ** -0.5 if up.skip_connection_scale else 1.0
@@ -396,7 +493,7 @@ class TrainGraph:
         if up.skip_connection_mode == "add":
             out.x = par + gathered
         else:
-            out.x = linear(torch.cat([par, gathered], dim=-1), up.proj_cat[0])
+            out.x = linear(torch.cat([par, gathered], dim=-1), up.proj_cat[0], self.mm_variant)
         return out
 
     def _cross_block(self, nst, cst, cb, masks):
@@ -410,15 +507,15 @@ class TrainGraph:
         cst.x = hkv  # the kv point leaves the block holding its normed feature (modules.py:68-73)
         att = cb.attn
         cq = xq.shape[1]
-        q = linear(hq, att.q)
-        kv = linear(hkv, att.kv)
+        q = linear(hq, att.q, self.mm_variant)
+        kv = linear(hkv, att.kv, self.mm_variant)
         K = att.q_patch_size
         q_gidx, widx = lv.slots(nst.curves[att.order_index], K, att.enable_flash)
         kv_gidx, _ = clv.slots(cst.curves[att.order_index], K, att.enable_flash)
         patch_start, max_len = lv.pad(K, att.enable_flash)[4:6]
         psh = lv.pad_host(K, att.enable_flash)[3].tolist()
         o = attention_core(self.attn_variant, q, kv, cq, q_gidx, kv_gidx, widx, patch_start, psh, att.num_heads, max_len, att.scale)
-        a = linear(o, att.proj)
+        a = linear(o, att.proj, self.mm_variant)
         name = "backbone._tm_dec0.cross_block2.drop_path.0"
         m = self._mask(nst, name, cb.drop_prob, masks)
         x = xq + cb.tm_feat * (a if m is None else a * m)
@@ -434,14 +531,17 @@ class TrainGraph:
 
         The reference trainer calls the model inside `torch.cuda.amp.autocast(enabled=cfg.enable_amp)` and scales the loss
         with a GradScaler (engines/train.py:226-240).  This forward computes what `model.train_precision` says whatever the
-        context ("fp32": exact fp32; "fp16-attn" / "bf16-attn": the attention core in 16 bits, the rest fp32): autocast is
+        context ("fp32": exact fp32; "fp16-attn" / "bf16-attn": the attention core in 16 bits, the rest fp32; "fp16-amp" /
+        "bf16-amp": the Linears and sparse convs on 16-bit products as well, outputs fp32 - see the module docstring): autocast is
         switched off inside it (torch's own ops here - heads, BatchNorm, GELU - would otherwise hand half tensors to fp32
         kernels), so the trainer's AMP branch runs unchanged: the scaler multiplies an fp32 loss, and only a scaled gradient
-        that leaves half's range inside the "fp16-attn" core shows up as an overflow (non-finite dq / dk / dv)."""
+        that leaves half's range inside the "fp16-attn" core (non-finite dq / dk / dv) or, under "fp16-amp", in the unsaturated
+        cast of a Linear's / conv's dy (non-finite dx / dw / db) shows up as an overflow."""
         tp = getattr(self.model, "train_precision", "fp32")
         if tp not in TRAIN_PRECISIONS:
             raise ValueError(f"train_precision must be one of {sorted(TRAIN_PRECISIONS)}, not {tp!r}")
         self.attn_variant = TRAIN_PRECISIONS[tp]
+        self.mm_variant = TRAIN_PRECISIONS[tp] if tp.endswith("-amp") else None
         if feat_is_cuda(input_dict):
             with torch.autocast(device_type="cuda", enabled=False):
                 return self._forward(input_dict, draws)

@@ -623,6 +623,21 @@ int cdseg_linear_wgrad(const float* x, int ldx, const int32_t* xidx, const float
  * nbr_kmajor: the (kvol, m) offset-major kernel map */
 int cdseg_conv_wgrad(const float* x, int ldx, const int32_t* nbr_kmajor, int kvol, const float* dy, int lddy, long m, int cin,
                      int cout, float* dw, float* db, void* stream);
+/* The same two weight gradients on 16-bit operands (training under AMP, train_precision "fp16-amp" / "bf16-amp"): x and dy
+ * are of the build's 16-bit type (bfloat16, or IEEE half in the half build), dw / db stay fp32 and are accumulated into.
+ * Semantics, row(m), the offset-major map and the (cout, kvol, cin) layout are those of the fp32 forms above.  Products of
+ * 16-bit values are exact and every sum is fp32 (v_mfma_f32_32x32x16 accumulators, fp32 atomics for the partial tiles, order
+ * not fixed): no partial sum is rounded to 16 bits.  An inf / NaN in dy (a scaled gradient beyond half's range, cast
+ * without saturation) arrives in the dw rows and the db entry of its column, where a GradScaler finds it.
+ * Row chunks staged row-major in LDS, both operands read with ds_read_b64_tr_b16; a chunk of 64 rows in which the offset
+ * has no live neighbour is skipped.
+ *   CDSEG_ERR_ARG: a pointer that is not 16-byte aligned, or ldx / lddy (in elements) not a multiple of 8.
+ *   CDSEG_ERR_UNSUPPORTED: n, k (cin, cout) not multiples of 16 (a 16-wide shape runs as a zero-padded 32-wide tile).
+ *   m <= 0: CDSEG_OK, nothing written. */
+int cdseg_linear_wgrad16(const void* x, int ldx, const int32_t* xidx, const void* dy, int lddy, long m, int k, int n, float* dw,
+                         int lddw, float* db, void* stream);
+int cdseg_conv_wgrad16(const void* x, int ldx, const int32_t* nbr_kmajor, int kvol, const void* dy, int lddy, long m, int cin,
+                       int cout, float* dw, float* db, void* stream);
 
 #ifdef __cplusplus
 }

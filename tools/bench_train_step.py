@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """One full-width training step (forward under autograd, loss.backward(), AdamW) on a synthetic ScanNet-shaped batch, fp32
-or with a 16-bit attention core (train_precision), on the HIP kernels (cdsegnet_amd/train_graph.py).  Not a BASELINE metric - the reference publishes no training throughput -
+with a 16-bit attention core, or under AMP (16-bit attention core, Linears and sparse convs; train_precision), on the HIP kernels (cdsegnet_amd/train_graph.py).  Not a BASELINE metric - the reference publishes no training throughput -
 a first number for the training row of SURVEY 8(f4).
 usage: python tools/bench_train_step.py [scenes=1] [points=120000] [steps=4] [dataset=scannet|scannet200|nuscenes]
-       [train_precision=fp32|fp16-attn|bf16-attn]"""
+       [train_precision=fp32|fp16-attn|bf16-attn|fp16-amp|bf16-amp]"""
 import os, sys, time
 import numpy as np
 import torch
