@@ -203,6 +203,16 @@ SIGNATURES = {
                                    c_void_p]),
     "cdseg_linear_wgrad16": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_void_p, c_int, c_void_p,
                                      c_void_p]),
+    "cdseg_wgrad_partition": (c_int, [c_long, c_int, c_int, c_int, c_int, POINTER(c_long), POINTER(c_int)]),
+    "cdseg_wgrad_det_ws_bytes": (c_size_t, [c_long, c_int, c_int, c_int, c_int]),
+    "cdseg_linear_wgrad_det": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_void_p, c_int, c_void_p,
+                                       c_int, c_void_p, c_size_t, c_void_p]),
+    "cdseg_conv_wgrad_det": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_long, c_int, c_int, c_void_p, c_void_p,
+                                     c_int, c_void_p, c_size_t, c_void_p]),
+    "cdseg_layernorm_bwd_det_ws_bytes": (c_size_t, [c_long, c_int]),
+    "cdseg_layernorm_bwd_det": (c_int, [c_void_p, c_int, c_void_p, c_float, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
+                                        c_void_p, c_long, c_int, c_void_p, c_size_t, c_void_p]),
+    "cdseg_segment_sum": (c_int, [c_void_p, c_int, c_void_p, c_long, c_int, c_void_p, c_int, c_void_p]),
     "cdseg_prof_enable": (c_int, [c_int]),
     "cdseg_prof_summary": (c_int, [POINTER(ctypes.c_double), POINTER(c_long)]),
     "cdseg_prof_summary_class": (c_int, [c_int, POINTER(ctypes.c_double), POINTER(c_long)]),

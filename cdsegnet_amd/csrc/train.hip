@@ -13,6 +13,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "wgrad_partition.h"
 
 namespace {
 
@@ -281,6 +282,11 @@ constexpr int BW_KV_LDS = 2 * BW_MAXL * 64 + 3 * BW_MAXL * 4;
 // 2 + 4 and 6 MFMAs per tile against 16 + 17 v_exp_f32 and 24 conversions: like the forward, VALU-bound.
 // LDS rows are 32 bytes; the two 16-byte halves are swapped for rows with bit 3 set (conflict-free 16-byte operand reads,
 // the forward's K image).  Every (slot, head, dim) result leaves with one fp32 atomic, as in the fp32 form.
+// Reproducibility (both forms, any blockIdx.z split): the buffers start at zero and a row sits in at most TWO slots - the
+// padding plan copies the tail of the previous patch once - so a dq / dk / dv element receives at most two adds, and
+// 0 + a + b = 0 + b + a in fp32: the result does not depend on the order the atomics arrive in
+// (tests/test_gpu_deterministic.py pins this on launches whose rows sit in at most two slots; a plan that put a row into
+// three slots would need a per-row reduce).
 constexpr int B16_WAVES = 8;
 constexpr int B16_IMG = BW_MAXL * 32;  // one 16-bit operand of a patch-head
 constexpr int B16_Q_LDS = 2 * B16_IMG;
@@ -529,13 +535,16 @@ __global__ __launch_bounds__(B16_WAVES * 64, 4) void attn_bwd16_kv_kernel(AttnBw
 // and block (the first version issued one atomic per element onto C addresses: 82 of a 450 ms training step).
 constexpr int LNB_ROWS = 16, LNB_MAXC = 512;
 
-__global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ gamma,
-                                                            float eps, const float* __restrict__ dy, int lddy, float* dx, int lddx,
-                                                            int accumulate, float* dgamma, float* dbeta, long m, int c) {
+// DET (deterministic form, c <= LNB_MAXC): the block's (dgamma, dbeta) partial rows go to ws[block][2][c] with plain stores;
+// layernorm_det_reduce_kernel adds them by ascending block index.  The in-block part is the same in both forms.
+template <bool DET>
+__device__ __forceinline__ void layernorm_bwd_body(const float* __restrict__ x, int ldx, const float* __restrict__ gamma, float eps,
+                                                   const float* __restrict__ dy, int lddy, float* dx, int lddx, int accumulate,
+                                                   float* dgamma, float* dbeta, long m, int c, float* ws) {
   __shared__ float red[2][4][LNB_MAXC];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long row0 = ((long)blockIdx.x * 4 + wave) * LNB_ROWS;
-  const bool sums = (dgamma || dbeta) && c <= LNB_MAXC;
+  const bool sums = DET || ((dgamma || dbeta) && c <= LNB_MAXC);
   float pg[LNB_MAXC / 64], pb[LNB_MAXC / 64];
 #pragma unroll
   for (int t = 0; t < LNB_MAXC / 64; ++t) pg[t] = pb[t] = 0.f;
@@ -593,9 +602,42 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
   for (int j = threadIdx.x; j < c; j += 256) {
     const float g = (red[0][0][j] + red[0][1][j]) + (red[0][2][j] + red[0][3][j]);
     const float b = (red[1][0][j] + red[1][1][j]) + (red[1][2][j] + red[1][3][j]);
-    if (dgamma) atomicAdd(dgamma + j, g);
-    if (dbeta) atomicAdd(dbeta + j, b);
+    if constexpr (DET) {
+      float* o = ws + (long)blockIdx.x * 2 * c + j;
+      o[0] = g; o[c] = b;
+    } else {
+      if (dgamma) atomicAdd(dgamma + j, g);
+      if (dbeta) atomicAdd(dbeta + j, b);
+    }
   }
+}
+
+__global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ gamma,
+                                                            float eps, const float* __restrict__ dy, int lddy, float* dx, int lddx,
+                                                            int accumulate, float* dgamma, float* dbeta, long m, int c) {
+  layernorm_bwd_body<false>(x, ldx, gamma, eps, dy, lddy, dx, lddx, accumulate, dgamma, dbeta, m, c, nullptr);
+}
+
+__global__ __launch_bounds__(256) void layernorm_bwd_det_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ gamma,
+                                                                float eps, const float* __restrict__ dy, int lddy, float* dx, int lddx,
+                                                                int accumulate, long m, int c, float* ws) {
+  layernorm_bwd_body<true>(x, ldx, gamma, eps, dy, lddy, dx, lddx, accumulate, nullptr, nullptr, m, c, ws);
+}
+
+// Thread i < c: column i of dgamma, thread c + j: column j of dbeta: t = p[0]; t += p[1]; ... by ascending block index, then ONE add onto
+// the existing content.  The loads of a column are independent of each other (only the adds are a chain).
+__global__ __launch_bounds__(64) void layernorm_det_reduce_kernel(const float* __restrict__ ws, long nblocks, int c, float* dgamma,
+                                                                  float* dbeta) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= 2 * c) return;
+  float* out = i < c ? dgamma : dbeta;
+  if (!out) return;
+  const float* p = ws + i;
+  float t = p[0];
+#pragma unroll 16
+  for (long b = 1; b < nblocks; ++b) t += p[b * 2 * c];
+  const int j = i < c ? i : i - c;
+  out[j] = out[j] + t;
 }
 
 // ---- exact (erf) GELU backward on the pre-activation: dx = dy * (Phi(u) + u phi(u))
@@ -622,7 +664,11 @@ struct WgradP {
   int splits, dw_off_stride;           // blockIdx.z = offset * splits + split; offset o adds o * dw_off_stride to dw
 };
 
-__global__ __launch_bounds__(256) void wgrad_kernel(WgradP p) {
+// DET (deterministic form): the block's partial dW tile goes to ws_dw[blockIdx.z][N][K] and its db partial to
+// ws_db[split][N] with plain stores (every element of both is written by exactly one thread: a split without live rows
+// stores zeros); wgrad_det_reduce_kernel adds them in ascending split order.  Same tiling, loop and row partition.
+template <bool DET>
+__device__ __forceinline__ void wgrad_body(const WgradP& p, float* ws_dw, float* ws_db) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i16 = lane & 15, kq = lane >> 4;
   const int n0 = blockIdx.x * 64 + wave * 16, k0 = blockIdx.y * 64;
@@ -662,12 +708,52 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradP p) {
   for (int t = 0; t < 4; ++t) {
     if (!kt_ok[t]) continue;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) atomicAdd(dw + (long)(n0 + 4 * kq + r) * p.lddw + k0 + 16 * t + i16, acc[t][r]);
+    for (int r = 0; r < 4; ++r) {
+      if constexpr (DET) ws_dw[((long)blockIdx.z * p.N + n0 + 4 * kq + r) * p.K + k0 + 16 * t + i16] = acc[t][r];
+      else atomicAdd(dw + (long)(n0 + 4 * kq + r) * p.lddw + k0 + 16 * t + i16, acc[t][r]);
+    }
   }
   if (p.db && blockIdx.y == 0 && off == 0) {
     bsum += __shfl_xor(bsum, 16, 64);
     bsum += __shfl_xor(bsum, 32, 64);
-    if (lane < 16) atomicAdd(p.db + n0 + lane, bsum);
+    if (lane < 16) {
+      if constexpr (DET) ws_db[(long)blockIdx.z * p.N + n0 + lane] = bsum;  // (off == 0: blockIdx.z is the split)
+      else atomicAdd(p.db + n0 + lane, bsum);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void wgrad_kernel(WgradP p) { wgrad_body<false>(p, nullptr, nullptr); }
+__global__ __launch_bounds__(256) void wgrad_det_kernel(WgradP p, float* ws_dw, float* ws_db) { wgrad_body<true>(p, ws_dw, ws_db); }
+
+// The fixed-order reduce of both deterministic weight gradients (fp32 and 16-bit operands leave the same fp32 partials):
+// one thread per dW element (offset, n, k), then per db element:  t = p[0]; t += p[1]; ... by ascending split index, then ONE
+// add onto the existing content (dw / db keep their accumulate-into contract).  No block waits for another: this is a launch
+// of its own behind the partial kernel on the same stream.
+struct WgradReduceP {
+  const float* ws_dw; const float* ws_db; float* dw; float* db;
+  int N, K, lddw, splits, noff, dw_off_stride;
+};
+
+__global__ __launch_bounds__(256) void wgrad_det_reduce_kernel(WgradReduceP r) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  const long nk = (long)r.N * r.K, total = nk * r.noff;
+  if (i < total) {
+    const long off = i / nk, e = i - off * nk;
+    const int n = (int)(e / r.K), k = (int)(e - (long)n * r.K);
+    const float* p = r.ws_dw + off * r.splits * nk + e;
+    float t = p[0];
+#pragma unroll 8
+    for (int s = 1; s < r.splits; ++s) t += p[s * nk];
+    float* o = r.dw + off * r.dw_off_stride + (long)n * r.lddw + k;
+    *o = *o + t;
+  } else if (r.db && i < total + r.N) {
+    const int n = (int)(i - total);
+    const float* p = r.ws_db + n;
+    float t = p[0];
+#pragma unroll 8
+    for (int s = 1; s < r.splits; ++s) t += p[(long)s * r.N];
+    r.db[n] = r.db[n] + t;
   }
 }
 
@@ -693,8 +779,8 @@ struct Wgrad16P {
   int splits, dw_off_stride;
 };
 
-template <int TN, int TK>
-__global__ __launch_bounds__(256) void wgrad16_kernel(Wgrad16P p) {
+template <int TN, int TK, bool DET>
+__device__ __forceinline__ void wgrad16_body(const Wgrad16P& p, float* ws_dw, float* ws_db) {
   constexpr int IMG = (TN + TK) * W16_SUB;               // one buffer: TN sub-images of dY, then TK of X
   constexpr int CN = TN * 4, CK = TK * 4;                // 16-byte column chunks per staged row
   constexpr int RN = 256 / CN, RK = 256 / CK;            // rows a pass of the block's 256 threads covers
@@ -809,7 +895,10 @@ __global__ __launch_bounds__(256) void wgrad16_kernel(Wgrad16P p) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int nn = nb + (r & 3) + 8 * (r >> 2);
-      if (nn < p.N) atomicAdd(dw + (long)nn * p.lddw + kk, acc[j][r]);
+      if (nn < p.N) {
+        if constexpr (DET) ws_dw[((long)blockIdx.z * p.N + nn) * p.K + kk] = acc[j][r];
+        else atomicAdd(dw + (long)nn * p.lddw + kk, acc[j][r]);
+      }
     }
   }
   if (want_db) {  // (block-uniform) the threads' column sums: one fp32 sum per column in LDS, one atomic per column
@@ -821,8 +910,35 @@ __global__ __launch_bounds__(256) void wgrad16_kernel(Wgrad16P p) {
     if (tid < 32 * TN && n0 + tid < p.N) {
       float s = 0.f;
       for (int r = 0; r < RN; ++r) s += red[r * (32 * TN) + tid];
-      atomicAdd(p.db + n0 + tid, s);
+      if constexpr (DET) ws_db[(long)blockIdx.z * p.N + n0 + tid] = s;  // (off == 0: blockIdx.z is the split)
+      else atomicAdd(p.db + n0 + tid, s);
     }
+  }
+}
+
+template <int TN, int TK>
+__global__ __launch_bounds__(256) void wgrad16_kernel(Wgrad16P p) { wgrad16_body<TN, TK, false>(p, nullptr, nullptr); }
+
+// deterministic form (see wgrad_body): partial tiles and db partials to the workspace, reduced by wgrad_det_reduce_kernel
+template <int TN, int TK>
+__global__ __launch_bounds__(256) void wgrad16_det_kernel(Wgrad16P p, float* ws_dw, float* ws_db) {
+  wgrad16_body<TN, TK, true>(p, ws_dw, ws_db);
+}
+
+// ---- segment sum: out[j] = sum of src rows seg_start[j] .. seg_start[j + 1] - 1 in ascending row order, fp32: the backward
+//      of the unpooling gather child[cluster] (children of a pooled row are contiguous in the plan's physical order) without
+//      atomics.  A wave covers 64 / cw coarse rows x cw columns (cw = 16, 32 or 64 lanes per row: coalesced row reads).
+__global__ __launch_bounds__(256) void segment_sum_kernel(const float* __restrict__ src, int ld, const int32_t* __restrict__ seg,
+                                                          long m, int c, float* __restrict__ out, int ldo, int cw) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int rpw = 64 / cw;
+  const long j = ((long)blockIdx.x * 4 + wave) * rpw + lane / cw;
+  if (j >= m) return;
+  const int a = seg[j], b = seg[j + 1];
+  for (int col = lane % cw; col < c; col += cw) {
+    float t = 0.f;
+    for (int i = a; i < b; ++i) t += src[(long)i * ld + col];
+    out[j * ldo + col] = t;
   }
 }
 
@@ -910,17 +1026,29 @@ extern "C" int cdseg_gelu_bwd(const float* u, const float* dy, float* dx, long n
   return CDSEG_OK;
 }
 
-static int launch_wgrad(WgradP p, int noff, hipStream_t stream) {
-  const int tiles = cdiv(p.N, 64) * cdiv(p.K, 64) * noff;
-  long splits = (2048 + tiles - 1) / tiles;     // ~8 blocks per CU
-  const long max_splits = (p.M + 1023) / 1024;  // at least 1024 rows per block: 4096 atomics per tile
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  p.rows_per_split = ((p.M + splits - 1) / splits + 3) & ~3L;
-  splits = (p.M + p.rows_per_split - 1) / p.rows_per_split;
-  p.splits = (int)splits;
-  hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)cdiv(p.N, 64), (unsigned)cdiv(p.K, 64), (unsigned)(splits * noff)), dim3(256), 0,
-                     stream, p);
+// Row partition: a function of the shape only (csrc/wgrad_partition.h: no device query), shared by the default and the
+// deterministic launches and reported by cdseg_wgrad_partition.
+static void launch_wgrad_reduce(const float* ws_dw, const float* ws_db, float* dw, float* db, int N, int K, int lddw, int splits,
+                                int noff, int dw_off_stride, hipStream_t stream) {
+  WgradReduceP r;
+  r.ws_dw = ws_dw; r.ws_db = ws_db; r.dw = dw; r.db = db; r.N = N; r.K = K; r.lddw = lddw; r.splits = splits; r.noff = noff;
+  r.dw_off_stride = dw_off_stride;
+  const long threads = (long)N * K * noff + N;
+  hipLaunchKernelGGL(wgrad_det_reduce_kernel, dim3((unsigned)cdiv(threads, 256)), dim3(256), 0, stream, r);
+}
+
+static int launch_wgrad(WgradP p, int noff, hipStream_t stream, float* ws = nullptr) {
+  const cdseg_wgrad::Partition q = cdseg_wgrad::partition_f32(p.M, p.N, p.K, noff);
+  p.rows_per_split = q.rows_per_split;
+  p.splits = q.splits;
+  const dim3 grid((unsigned)cdiv(p.N, 64), (unsigned)cdiv(p.K, 64), (unsigned)(q.splits * noff));
+  if (ws) {
+    float* ws_db = ws + (size_t)noff * q.splits * p.N * p.K;
+    hipLaunchKernelGGL(wgrad_det_kernel, grid, dim3(256), 0, stream, p, ws, ws_db);
+    launch_wgrad_reduce(ws, ws_db, p.dw, p.db, p.N, p.K, p.lddw, q.splits, noff, p.dw_off_stride, stream);
+  } else {
+    hipLaunchKernelGGL(wgrad_kernel, grid, dim3(256), 0, stream, p);
+  }
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
 }
@@ -946,37 +1074,33 @@ extern "C" int cdseg_conv_wgrad(const float* x, int ldx, const int32_t* nbr_kmaj
 }
 
 template <int TN, int TK>
-static void launch_wgrad16_tile(const Wgrad16P& p, int noff, hipStream_t stream) {
-  hipLaunchKernelGGL((wgrad16_kernel<TN, TK>), dim3((unsigned)cdiv(p.N, 32 * TN), (unsigned)cdiv(p.K, 32 * TK), (unsigned)(p.splits * noff)),
-                     dim3(256), 0, stream, p);
+static void launch_wgrad16_tile(const Wgrad16P& p, int noff, hipStream_t stream, float* ws_dw, float* ws_db) {
+  const dim3 grid((unsigned)cdiv(p.N, 32 * TN), (unsigned)cdiv(p.K, 32 * TK), (unsigned)(p.splits * noff));
+  if (ws_dw) hipLaunchKernelGGL((wgrad16_det_kernel<TN, TK>), grid, dim3(256), 0, stream, p, ws_dw, ws_db);
+  else hipLaunchKernelGGL((wgrad16_kernel<TN, TK>), grid, dim3(256), 0, stream, p);
 }
 
 // Tile: the narrowest of 32 / 64 / 128 columns that covers N (K), so the narrow stages read dY and X once (C = 32: dW 96 x 32
 // is one tile); 128 x 128 would need 64 KiB of LDS, the deep stages take 128 x 64.  Rows are split over the grid as in
-// launch_wgrad: ~2 blocks per CU, at least 512 rows (8 chunks) per block so a tile's atomics stay rare next to its loads.
-static int launch_wgrad16(Wgrad16P p, int noff, hipStream_t stream) {
-  const int tn = p.N > 64 ? 4 : p.N > 32 ? 2 : 1;
-  int tk = p.K > 64 ? 4 : p.K > 32 ? 2 : 1;
-  if (tn == 4 && tk == 4) tk = 2;
-  const long tiles = (long)cdiv(p.N, 32 * tn) * cdiv(p.K, 32 * tk) * noff;
-  long splits = (512 + tiles - 1) / tiles;
-  const long max_splits = (p.M + 511) / 512;
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  p.rows_per_split = ((p.M + splits - 1) / splits + W16_ROWS - 1) / W16_ROWS * W16_ROWS;
-  splits = (p.M + p.rows_per_split - 1) / p.rows_per_split;
-  if (splits * noff > 65535) return CDSEG_ERR_UNSUPPORTED;
-  p.splits = (int)splits;
-  switch (tn * 8 + tk) {
-    case 1 * 8 + 1: launch_wgrad16_tile<1, 1>(p, noff, stream); break;
-    case 1 * 8 + 2: launch_wgrad16_tile<1, 2>(p, noff, stream); break;
-    case 1 * 8 + 4: launch_wgrad16_tile<1, 4>(p, noff, stream); break;
-    case 2 * 8 + 1: launch_wgrad16_tile<2, 1>(p, noff, stream); break;
-    case 2 * 8 + 2: launch_wgrad16_tile<2, 2>(p, noff, stream); break;
-    case 2 * 8 + 4: launch_wgrad16_tile<2, 4>(p, noff, stream); break;
-    case 4 * 8 + 1: launch_wgrad16_tile<4, 1>(p, noff, stream); break;
-    default: launch_wgrad16_tile<4, 2>(p, noff, stream); break;
+// launch_wgrad: ~2 blocks per CU, at least 512 rows (8 chunks) per block so a tile's atomics stay rare next to its loads
+// (cdseg_wgrad::partition_16).
+static int launch_wgrad16(Wgrad16P p, int noff, hipStream_t stream, float* ws = nullptr) {
+  const cdseg_wgrad::Partition q = cdseg_wgrad::partition_16(p.M, p.N, p.K, noff);
+  if (q.splits < 0) return CDSEG_ERR_UNSUPPORTED;
+  p.rows_per_split = q.rows_per_split;
+  p.splits = q.splits;
+  float* ws_db = ws ? ws + (size_t)noff * q.splits * p.N * p.K : nullptr;
+  switch (q.tn * 8 + q.tk) {
+    case 1 * 8 + 1: launch_wgrad16_tile<1, 1>(p, noff, stream, ws, ws_db); break;
+    case 1 * 8 + 2: launch_wgrad16_tile<1, 2>(p, noff, stream, ws, ws_db); break;
+    case 1 * 8 + 4: launch_wgrad16_tile<1, 4>(p, noff, stream, ws, ws_db); break;
+    case 2 * 8 + 1: launch_wgrad16_tile<2, 1>(p, noff, stream, ws, ws_db); break;
+    case 2 * 8 + 2: launch_wgrad16_tile<2, 2>(p, noff, stream, ws, ws_db); break;
+    case 2 * 8 + 4: launch_wgrad16_tile<2, 4>(p, noff, stream, ws, ws_db); break;
+    case 4 * 8 + 1: launch_wgrad16_tile<4, 1>(p, noff, stream, ws, ws_db); break;
+    default: launch_wgrad16_tile<4, 2>(p, noff, stream, ws, ws_db); break;
   }
+  if (ws) launch_wgrad_reduce(ws, ws_db, p.dw, p.db, p.N, p.K, p.lddw, q.splits, noff, p.dw_off_stride, stream);
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
 }
@@ -1007,4 +1131,95 @@ extern "C" int cdseg_conv_wgrad16(const void* x, int ldx, const int32_t* nbr_kma
   p.dy = (const bf16_t*)dy; p.x = (const bf16_t*)x; p.xidx = nbr_kmajor; p.dw = dw; p.db = db; p.M = m; p.N = cout; p.K = cin;
   p.lddy = lddy; p.ldx = ldx; p.lddw = kvol * cin; p.idx_stride = m; p.dw_off_stride = cin;
   return launch_wgrad16(p, kvol, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------ deterministic forms
+// Fixed summation order (include/cdseg.h): partial results to a caller-provided workspace with plain stores, then a reduce
+// launch that adds them by ascending split / block index and adds the total ONCE onto dw / db / dgamma / dbeta.
+extern "C" int cdseg_wgrad_partition(long m, int n, int k, int kvol, int dtype, long* rows_per_split, int* splits) {
+  if (dtype != CDSEG_F32 && dtype != CDSEG_BF16) return CDSEG_ERR_UNSUPPORTED;
+  if (m < 0 || n <= 0 || k <= 0 || kvol <= 0) return CDSEG_ERR_ARG;
+  const cdseg_wgrad::Partition q = dtype == CDSEG_F32 ? cdseg_wgrad::partition_f32(m, n, k, kvol) : cdseg_wgrad::partition_16(m, n, k, kvol);
+  if (q.splits < 0) return CDSEG_ERR_UNSUPPORTED;
+  if (rows_per_split) *rows_per_split = q.rows_per_split;
+  if (splits) *splits = q.splits;
+  return CDSEG_OK;
+}
+
+extern "C" size_t cdseg_wgrad_det_ws_bytes(long m, int n, int k, int kvol, int dtype) {
+  long rows = 0;
+  int splits = 0;
+  if (cdseg_wgrad_partition(m, n, k, kvol, dtype, &rows, &splits) != CDSEG_OK) return 0;
+  return cdseg_wgrad::det_ws_floats(n, k, kvol, splits) * sizeof(float);
+}
+
+static int wgrad_det(const void* x, int ldx, const int32_t* xidx, int kvol, const void* dy, int lddy, long m, int k, int n, float* dw,
+                     int lddw, long idx_stride, int dw_off_stride, float* db, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  if (dtype != CDSEG_F32 && dtype != CDSEG_BF16) return CDSEG_ERR_UNSUPPORTED;
+  if (dtype == CDSEG_BF16) {
+    if (!wgrad16_args_ok(x, ldx, xidx, dy, lddy, dw, db)) return CDSEG_ERR_ARG;
+  } else if (!x || !dy || !dw || ((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dw | (uintptr_t)db | (uintptr_t)xidx) & 3) != 0)) {
+    return CDSEG_ERR_ARG;
+  }
+  if (((uintptr_t)ws & 15) != 0) return CDSEG_ERR_ARG;
+  if ((n & 15) || (k & 15)) return CDSEG_ERR_UNSUPPORTED;
+  long rows = 0;
+  int splits = 0;
+  const int st = cdseg_wgrad_partition(m, n, k, kvol, dtype, &rows, &splits);
+  if (st != CDSEG_OK) return st;
+  if (!ws || ws_bytes < cdseg_wgrad::det_ws_floats(n, k, kvol, splits) * sizeof(float)) return CDSEG_ERR_WORKSPACE;
+  if (dtype == CDSEG_BF16) {
+    Wgrad16P p;
+    p.dy = (const bf16_t*)dy; p.x = (const bf16_t*)x; p.xidx = xidx; p.dw = dw; p.db = db; p.M = m; p.N = n; p.K = k; p.lddy = lddy;
+    p.ldx = ldx; p.lddw = lddw; p.idx_stride = idx_stride; p.dw_off_stride = dw_off_stride;
+    return launch_wgrad16(p, kvol, (hipStream_t)stream, (float*)ws);
+  }
+  WgradP p;
+  p.dy = (const float*)dy; p.x = (const float*)x; p.xidx = xidx; p.dw = dw; p.db = db; p.M = m; p.N = n; p.K = k; p.lddy = lddy;
+  p.ldx = ldx; p.lddw = lddw; p.idx_stride = idx_stride; p.dw_off_stride = dw_off_stride;
+  return launch_wgrad(p, kvol, (hipStream_t)stream, (float*)ws);
+}
+
+extern "C" int cdseg_linear_wgrad_det(const void* x, int ldx, const int32_t* xidx, const void* dy, int lddy, long m, int k, int n,
+                                      float* dw, int lddw, float* db, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  if (m <= 0 || n <= 0 || k <= 0) return CDSEG_OK;
+  return wgrad_det(x, ldx, xidx, 1, dy, lddy, m, k, n, dw, lddw, 0, 0, db, dtype, ws, ws_bytes, stream);
+}
+
+extern "C" int cdseg_conv_wgrad_det(const void* x, int ldx, const int32_t* nbr_kmajor, int kvol, const void* dy, int lddy, long m,
+                                    int cin, int cout, float* dw, float* db, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  if (m <= 0 || kvol <= 0 || cin <= 0 || cout <= 0) return CDSEG_OK;
+  if (!nbr_kmajor) return CDSEG_ERR_ARG;
+  return wgrad_det(x, ldx, nbr_kmajor, kvol, dy, lddy, m, cin, cout, dw, kvol * cin, m, cin, db, dtype, ws, ws_bytes, stream);
+}
+
+extern "C" size_t cdseg_layernorm_bwd_det_ws_bytes(long m, int c) { return cdseg_wgrad::ln_det_ws_floats(m, c) * sizeof(float); }
+
+extern "C" int cdseg_layernorm_bwd_det(const float* x, int ldx, const float* gamma, float eps, const float* dy, int lddy, float* dx,
+                                       int lddx, int accumulate, float* dgamma, float* dbeta, long m, int c, void* ws, size_t ws_bytes,
+                                       void* stream) {
+  if (m <= 0 || c <= 0) return CDSEG_OK;
+  if (!x || !gamma || !dy || !dx) return CDSEG_ERR_ARG;
+  if (c > LNB_MAXC) return CDSEG_ERR_UNSUPPORTED;  // (the default form's per-element-atomic path: no fixed order)
+  if (((uintptr_t)ws & 3) != 0) return CDSEG_ERR_ARG;
+  if (!ws || ws_bytes < cdseg_layernorm_bwd_det_ws_bytes(m, c)) return CDSEG_ERR_WORKSPACE;
+  const long nblocks = cdseg_wgrad::ln_blocks(m);
+  hipLaunchKernelGGL(layernorm_bwd_det_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, x, ldx, gamma, eps, dy, lddy,
+                     dx, lddx, accumulate, m, c, (float*)ws);
+  if (dgamma || dbeta)
+    hipLaunchKernelGGL(layernorm_det_reduce_kernel, dim3((unsigned)cdiv(2 * c, 64)), dim3(64), 0, (hipStream_t)stream, (const float*)ws,
+                       nblocks, c, dgamma, dbeta);
+  CDSEG_CHECK_LAUNCH();
+  return CDSEG_OK;
+}
+
+extern "C" int cdseg_segment_sum(const float* src, int ld, const int32_t* seg_start, long m, int c, float* out, int ldo, void* stream) {
+  if (m <= 0 || c <= 0) return CDSEG_OK;
+  if (!src || !seg_start || !out) return CDSEG_ERR_ARG;
+  const int cw = c <= 16 ? 16 : c <= 32 ? 32 : 64;
+  const long rows_per_block = 4 * (64 / cw);
+  hipLaunchKernelGGL(segment_sum_kernel, dim3((unsigned)cdiv(m, rows_per_block)), dim3(256), 0, (hipStream_t)stream, src, ld, seg_start, m,
+                     c, out, ldo, cw);
+  CDSEG_CHECK_LAUNCH();
+  return CDSEG_OK;
 }

@@ -430,6 +430,10 @@ class DefaultSegmentorV2(nn.Module):
         # and sparse conv (forward, data gradient, weight gradient) on 16-bit products with fp32 accumulation and fp32 outputs;
         # read at every forward(), anything else raises ValueError there
         self.train_precision = "fp32"
+        # training backward with a fixed fp32 summation order (bit-reproducible gradients; cdsegnet_amd/train_graph.py):
+        # None (default) = follow torch.are_deterministic_algorithms_enabled() | True | False; read at every forward(),
+        # not part of the state_dict
+        self.train_deterministic = None
         self._lanes = {}
         self.noise_source = "torch_cpu"  # "torch_cpu" replays the reference's CPU-generator draws | "device"
         # noise_level jitter: "torch_cpu" = the CPU-run reference's draw order (golden vectors) | "device" = device

@@ -1179,12 +1179,20 @@ def attention_bwd(q, k, v, q_gidx, kv_gidx, widx, patch_start, patch_start_host,
                                   dk.stride(0), dv.stride(0), code, _ptr(ws), ws.numel(), _stream()), "attention_bwd")
 
 
-def layernorm_bwd(x, gamma, dy, dx, accumulate=False, eps=1e-5, dgamma=None, dbeta=None):
-    """dx (=, or += with accumulate) of y = LayerNorm(x) * gamma + beta; fp32."""
+def layernorm_bwd(x, gamma, dy, dx, accumulate=False, eps=1e-5, dgamma=None, dbeta=None, deterministic=False):
+    """dx (=, or += with accumulate) of y = LayerNorm(x) * gamma + beta; fp32.  deterministic: dgamma / dbeta are summed in a
+    fixed order (block partials in a workspace from torch's allocator, added by ascending block index; rows up to 512 wide)."""
     _need_gpu(x, dy)
-    check(_lib.load().cdseg_layernorm_bwd(_ptr(x), x.stride(0), _ptr(gamma), float(eps), _ptr(dy), dy.stride(0), _ptr(dx),
+    lib = _lib.load()
+    if deterministic:
+        ws = torch.empty(max(16, lib.cdseg_layernorm_bwd_det_ws_bytes(x.shape[0], x.shape[1])), dtype=torch.uint8, device=x.device)
+        check(lib.cdseg_layernorm_bwd_det(_ptr(x), x.stride(0), _ptr(gamma), float(eps), _ptr(dy), dy.stride(0), _ptr(dx),
                                           dx.stride(0), int(bool(accumulate)), _ptr(dgamma), _ptr(dbeta), x.shape[0],
-                                          x.shape[1], _stream()), "layernorm_bwd")
+                                          x.shape[1], _ptr(ws), ws.numel(), _stream()), "layernorm_bwd (deterministic)")
+        return dx
+    check(lib.cdseg_layernorm_bwd(_ptr(x), x.stride(0), _ptr(gamma), float(eps), _ptr(dy), dy.stride(0), _ptr(dx),
+                                  dx.stride(0), int(bool(accumulate)), _ptr(dgamma), _ptr(dbeta), x.shape[0],
+                                  x.shape[1], _stream()), "layernorm_bwd")
     return dx
 
 
@@ -1211,10 +1219,40 @@ def _wgrad_operands(what, x, dy, dw, db):
     return True
 
 
-def linear_wgrad(x, dy, dw, db=None, xidx=None):
+def det_kw(deterministic):
+    """Keyword of the gradient reductions (`linear_wgrad`, `conv_wgrad`, `layernorm_bwd`): passed only when the fixed summation
+    order is asked for, so that the default call is what it was."""
+    return {"deterministic": True} if deterministic else {}
+
+
+class WgradPartition(tuple):
+    """(rows_per_split, splits) of a weight-gradient launch: split s covers rows s * rows_per_split .. (the last may be shorter)."""
+    __slots__ = ()
+    rows_per_split = property(lambda self: self[0])
+    splits = property(lambda self: self[1])
+
+
+def wgrad_partition(m, n, k, kvol=1, dtype=torch.float32):
+    """Row partition of the weight-gradient launch for dy (m, n), x (., k), kvol kernel offsets (1: the Linear form) and operands
+    of `dtype` (fp32, or a 16-bit type): a function of the shape only (host code, no GPU needed, the same in both builds)."""
+    rows, splits = ctypes.c_long(0), ctypes.c_int(0)
+    code = F32 if dtype == torch.float32 else BF16
+    check(_lib.load().cdseg_wgrad_partition(int(m), int(n), int(k), int(kvol), code, ctypes.byref(rows), ctypes.byref(splits)),
+          "wgrad_partition")
+    return WgradPartition((rows.value, splits.value))
+
+
+def _wgrad_ws(lib, m, n, k, kvol, lp, device):
+    nbytes = lib.cdseg_wgrad_det_ws_bytes(int(m), int(n), int(k), int(kvol), BF16 if lp else F32)
+    return torch.empty(max(16, nbytes), dtype=torch.uint8, device=device)
+
+
+def linear_wgrad(x, dy, dw, db=None, xidx=None, deterministic=False):
     """dw (N, K view, any row stride) += dy^T x[xidx or arange] and db (N) += column sums of dy (cdseg_linear_wgrad).
     xidx (M) int32 with -1 = no row: one kernel offset of a submanifold conv.  x and dy share a dtype: fp32, or the active
-    build's 16-bit type (cdseg_linear_wgrad16: exact products, fp32 sums); dw / db are fp32 either way."""
+    build's 16-bit type (cdseg_linear_wgrad16: exact products, fp32 sums); dw / db are fp32 either way.
+    deterministic: the same kernels with a fixed summation order (cdseg_linear_wgrad_det: the row splits of `wgrad_partition`
+    leave partial tiles in a workspace from torch's allocator, a second launch adds them by ascending split index)."""
     _need_gpu(x, dy, dw)
     lp = _wgrad_operands("linear_wgrad", x, dy, dw, db)
     assert dy.stride(1) == 1 and x.stride(1) == 1 and dw.stride(1) == 1
@@ -1222,16 +1260,21 @@ def linear_wgrad(x, dy, dw, db=None, xidx=None):
     k = x.shape[1]
     assert tuple(dw.shape) == (n, k) and (xidx is None or (xidx.dtype == torch.int32 and xidx.numel() == m))
     lib = _lib.load()
+    if deterministic:
+        ws = _wgrad_ws(lib, m, n, k, 1, lp, dw.device)
+        check(lib.cdseg_linear_wgrad_det(_ptr(x), x.stride(0), _ptr(xidx), _ptr(dy), dy.stride(0), m, k, n, _ptr(dw), dw.stride(0),
+                                         _ptr(db), BF16 if lp else F32, _ptr(ws), ws.numel(), _stream()), "linear_wgrad (deterministic)")
+        return dw
     fn = lib.cdseg_linear_wgrad16 if lp else lib.cdseg_linear_wgrad
     check(fn(_ptr(x), x.stride(0), _ptr(xidx), _ptr(dy), dy.stride(0), m, k, n, _ptr(dw), dw.stride(0), _ptr(db), _stream()),
           "linear_wgrad")
     return dw
 
 
-def conv_wgrad(x, nbr_kmajor, dy, dw3, db=None):
+def conv_wgrad(x, nbr_kmajor, dy, dw3, db=None, deterministic=False):
     """dw3 (Cout, kvol, Cin) += the weight gradient of a submanifold conv over all kernel offsets (one launch), db += the
     bias gradient; nbr_kmajor (kvol, M) int32 offset-major kernel map.  fp32 (cdseg_conv_wgrad), or x and dy of the active
-    build's 16-bit type with fp32 dw3 / db (cdseg_conv_wgrad16)."""
+    build's 16-bit type with fp32 dw3 / db (cdseg_conv_wgrad16).  deterministic: as in `linear_wgrad` (cdseg_conv_wgrad_det)."""
     _need_gpu(x, dy, dw3)
     lp = _wgrad_operands("conv_wgrad", x, dy, dw3, db)
     kvol, m = nbr_kmajor.shape
@@ -1239,7 +1282,23 @@ def conv_wgrad(x, nbr_kmajor, dy, dw3, db=None):
     assert kv == kvol and dw3.is_contiguous() and dy.stride(1) == 1 and x.stride(1) == 1
     assert nbr_kmajor.dtype == torch.int32 and nbr_kmajor.is_contiguous() and dy.shape == (m, cout) and x.shape[1] == cin
     lib = _lib.load()
+    if deterministic:
+        ws = _wgrad_ws(lib, m, cout, cin, kvol, lp, dw3.device)
+        check(lib.cdseg_conv_wgrad_det(_ptr(x), x.stride(0), _ptr(nbr_kmajor), kvol, _ptr(dy), dy.stride(0), m, cin, cout, _ptr(dw3),
+                                       _ptr(db), BF16 if lp else F32, _ptr(ws), ws.numel(), _stream()), "conv_wgrad (deterministic)")
+        return dw3
     fn = lib.cdseg_conv_wgrad16 if lp else lib.cdseg_conv_wgrad
     check(fn(_ptr(x), x.stride(0), _ptr(nbr_kmajor), kvol, _ptr(dy), dy.stride(0), m, cin, cout, _ptr(dw3), _ptr(db), _stream()),
           "conv_wgrad")
     return dw3
+
+
+def segment_sum(src, seg_start, m):
+    """out (m, C) fp32: out[j] = sum of src rows seg_start[j] .. seg_start[j + 1] - 1, added in ascending row order
+    (cdseg_segment_sum): the backward of a gather whose duplicates are contiguous, without atomics."""
+    _need_gpu(src, seg_start)
+    assert src.dtype == torch.float32 and src.stride(1) == 1 and seg_start.dtype == torch.int32 and seg_start.numel() >= m + 1
+    out = torch.empty((m, src.shape[1]), dtype=torch.float32, device=src.device)
+    check(_lib.load().cdseg_segment_sum(_ptr(src), src.stride(0), _ptr(seg_start), int(m), src.shape[1], _ptr(out), out.stride(0),
+                                        _stream()), "segment_sum")
+    return out

@@ -19,6 +19,7 @@ import weakref
 import torch
 
 from . import ops
+from .ops import det_kw as _det_kw
 
 
 class BlockTape:
@@ -84,48 +85,49 @@ def _derived(src, kind):
     return t
 
 
-def _wgrad(w, grads, key, x, dyy):
+def _wgrad(w, grads, key, x, dyy, det=False):
     dw = torch.zeros_like(w[key + ".w"])
     db = torch.zeros_like(w[key + ".b"]) if w.get(key + ".b") is not None else None
-    ops.linear_wgrad(x, dyy, dw, db)
+    ops.linear_wgrad(x, dyy, dw, db, **_det_kw(det))
     grads[key + ".w"] = dw
     if db is not None:
         grads[key + ".b"] = db
 
 
-def _ln_bwd(w, grads, key, x, dyy, dx, accumulate):
+def _ln_bwd(w, grads, key, x, dyy, dx, accumulate, det=False):
     if grads is None:
         return ops.layernorm_bwd(x, w[key + ".g"], dyy, dx, accumulate=accumulate)
     c = x.shape[1]
     dg = torch.zeros(c, dtype=torch.float32, device=x.device)
     db = torch.zeros(c, dtype=torch.float32, device=x.device)
-    ops.layernorm_bwd(x, w[key + ".g"], dyy, dx, accumulate=accumulate, dgamma=dg, dbeta=db)
+    ops.layernorm_bwd(x, w[key + ".g"], dyy, dx, accumulate=accumulate, dgamma=dg, dbeta=db, **_det_kw(det))
     grads[key + ".g"], grads[key + ".b"] = dg, db
     return dx
 
 
-def _tail_backward(w, pre, t, dy, grads):
+def _tail_backward(w, pre, t, dy, grads, det=False):
     """Shared by both slices (caller holds the stream binding).  grads: None, or a dict that receives the gradients of
     the tail's parameters (Linears: dW = dY^T X by cdseg_linear_wgrad, LayerNorms: d gamma / d beta); activations the
-    inference kernels fuse away (LN outputs, GELU output) are recomputed."""
+    inference kernels fuse away (LN outputs, GELU output) are recomputed.  det: parameter gradients in a fixed summation
+    order (the `_det` entry points; the attention backward is order-independent as it is, csrc/train.hip)."""
     n, c = t.x0.shape
     wt = lambda k: _derived(w[k], "T")  # noqa: E731 - dX = dY W is the inference GEMM on the transposed weight
     # y = x1 + fc2(GELU(u)):  d g = dy W2 ; d u = d g * GELU'(u) ; d h2 = d u W1
     if grads is not None:
         h2 = torch.empty_like(t.x1)
         ops.layernorm(t.x1, w[pre + ".norm2.g"], w[pre + ".norm2.b"], h2)
-        _wgrad(w, grads, pre + ".fc2", _lin(h2, w[pre + ".fc1.w"], w[pre + ".fc1.b"], act=ops.ACT_GELU), dy)
+        _wgrad(w, grads, pre + ".fc2", _lin(h2, w[pre + ".fc1.w"], w[pre + ".fc1.b"], act=ops.ACT_GELU), dy, det)
     dg = _lin(dy, wt(pre + ".fc2.w"), None)
     du = ops.gelu_bwd(t.u, dg)
     if grads is not None:
-        _wgrad(w, grads, pre + ".fc1", h2, du)
+        _wgrad(w, grads, pre + ".fc1", h2, du, det)
     dh2 = _lin(du, wt(pre + ".fc1.w"), None)
     # x1 feeds the residual and LN2:  d x1 = dy + LN2'(x1)^T d h2
     dx1 = dy.clone()
-    _ln_bwd(w, grads, pre + ".norm2", t.x1, dh2, dx1, True)
+    _ln_bwd(w, grads, pre + ".norm2", t.x1, dh2, dx1, True, det)
     # x1 = x0 + proj(o):  d o = d x1 Wp
     if grads is not None:
-        _wgrad(w, grads, pre + ".proj", t.o, dx1)
+        _wgrad(w, grads, pre + ".proj", t.o, dx1, det)
     do = _lin(dx1, wt(pre + ".proj.w"), None)
     # attention core: gradients land at the gathered qkv rows
     dqkv = torch.zeros((n, 3 * c), dtype=torch.float32, device=dy.device)
@@ -135,20 +137,21 @@ def _tail_backward(w, pre, t, dy, grads):
     if grads is not None:  # x0 feeds the residual and LN1 -> qkv
         h1 = torch.empty_like(t.x0)
         ops.layernorm(t.x0, w[pre + ".norm1.g"], w[pre + ".norm1.b"], h1)
-        _wgrad(w, grads, pre + ".qkv", h1, dqkv)
+        _wgrad(w, grads, pre + ".qkv", h1, dqkv, det)
         dh1 = _lin(dqkv, wt(pre + ".qkv.w"), None)
         dx0 = dx1.clone()
-        _ln_bwd(w, grads, pre + ".norm1", t.x0, dh1, dx0, True)
+        _ln_bwd(w, grads, pre + ".norm1", t.x0, dh1, dx0, True, det)
     return dict(d_qkv=dqkv, d_o=do, d_x1=dx1, d_u=du, d_x0=dx0)
 
 
-def block_tail_backward(w, pre, t, dy, param_grads=False):
+def block_tail_backward(w, pre, t, dy, param_grads=False, deterministic=False):
     """Backward of `block_tail_forward`: dy (N, C) is the gradient of y.  Returns dict(d_qkv, d_o, d_x1, d_u) and, with
-    param_grads, also d_x0 and grads = {parameter name: gradient} of the tail's twelve parameter tensors."""
+    param_grads, also d_x0 and grads = {parameter name: gradient} of the tail's twelve parameter tensors.
+    deterministic: the parameter gradients are summed in a fixed order (bit-reproducible)."""
     ops.bind_stream()
     try:
         grads = {} if param_grads else None
-        out = _tail_backward(w, pre, t, dy, grads)
+        out = _tail_backward(w, pre, t, dy, grads, deterministic)
     finally:
         ops.unbind_stream()
     if param_grads:
@@ -182,9 +185,11 @@ def block_forward(w, pre, x_in, nbr_kmajor, gidx, widx, patch_start, patch_start
     return t_full
 
 
-def block_backward(w, pre, tape, dy):
+def block_backward(w, pre, tape, dy, deterministic=False):
     """Backward of `block_forward`.  Returns (d_x_in, d_x_conv or None, grads) with grads[name] for every parameter of the
-    Block under the engine's names (pre + '.cpe0.w' (Cout, 27 * Cin), '.cpe1.w', '.cpe2.g', '.norm1.g', '.qkv.w', ...)."""
+    Block under the engine's names (pre + '.cpe0.w' (Cout, 27 * Cin), '.cpe1.w', '.cpe2.g', '.norm1.g', '.qkv.w', ...).
+    deterministic: as in `block_tail_backward`."""
+    det = deterministic
     t = tape["tail"]
     n, c = t.x0.shape
     dev = dy.device
@@ -193,11 +198,11 @@ def block_backward(w, pre, tape, dy):
     ops.bind_stream()
     try:
         wt = lambda k: _derived(w[k], "T")  # noqa: E731
-        dx0 = _tail_backward(w, pre, t, dy, grads)["d_x0"]
+        dx0 = _tail_backward(w, pre, t, dy, grads, det)["d_x0"]
         # ---- CPE: x0 = x_in + LN(z), z = Linear(yc), yc = conv(x_conv)
         dz = torch.empty_like(dx0)
-        _ln_bwd(w, grads, pre + ".cpe2", tape["z"], dx0, dz, False)
-        _wgrad(w, grads, pre + ".cpe1", tape["yc"], dz)
+        _ln_bwd(w, grads, pre + ".cpe2", tape["z"], dx0, dz, False, det)
+        _wgrad(w, grads, pre + ".cpe1", tape["yc"], dz, det)
         dyc = _lin(dz, wt(pre + ".cpe1.w"), None)
         wc = w[pre + ".cpe0.w"]
         cout, cin = wc.shape[0], wc.shape[1] // 27
@@ -205,7 +210,7 @@ def block_backward(w, pre, tape, dy):
         dbc = torch.zeros_like(w[pre + ".cpe0.b"]) if w.get(pre + ".cpe0.b") is not None else None
         dw3 = dwc.view(cout, 27, cin)
         nbr = tape["nbr"]
-        ops.conv_wgrad(tape["x_conv"], nbr, dyc, dw3, dbc)  # 27 gathered dY^T X in one launch
+        ops.conv_wgrad(tape["x_conv"], nbr, dyc, dw3, dbc, **_det_kw(det))  # 27 gathered dY^T X in one launch
         grads[pre + ".cpe0.w"] = dwc
         if dbc is not None:
             grads[pre + ".cpe0.b"] = dbc

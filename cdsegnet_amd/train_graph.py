@@ -31,6 +31,22 @@ Linear's OUTPUT to fp16; here the outputs stay fp32 (operand rounding and fp32 a
 statistics), GELU between them, the swish timestep MLP on B rows, row masks of stochastic depth, q_sample, the two
 (C -> classes) heads, and the criteria (cdsegnet_amd.losses).  All integer work - serialization, pooling structure,
 kernel maps, padded patch plans - is the inference engine's plan (Engine.build_plan), shared with the inference path.
+
+Deterministic mode (`model.train_deterministic`: None = follow torch.are_deterministic_algorithms_enabled(), True / False
+override; resolved once per forward).  The forward is a function of the seed either way (timesteps, noise and order shuffles
+from torch's CPU generator, stochastic-depth masks from the device generator, the plan is integer work) and is NOT changed by
+the mode.  What the mode changes are the backward reductions that otherwise leave through fp32 atomics in arrival order:
+    weight gradients of every Linear / sparse conv   ops.linear_wgrad / ops.conv_wgrad(deterministic=True): split partials in a
+                                                     workspace, added by ascending split index (ops.wgrad_partition)
+    LayerNorm dgamma / dbeta                         ops.layernorm_bwd(deterministic=True): block partials, ascending block index
+    unpooling gather child[cluster]                  `_GatherRuns`: backward = ops.segment_sum over the contiguous children
+    Mix3D fold point[k][rep]                         `_GatherRuns` after a stable sort of rep
+Everything else on the step is already order-fixed: the permutation gathers (perm0, inv0, ref_order) have unique indices;
+`_SceneRows` sums contiguous rows and `_SegmentMax` selects one child, neither with atomics; the attention backward adds at most
+two values onto a zeroed element (a row sits in at most two slots), which commutes; cdseg_gemm's split-K has no atomics;
+train-mode BatchNorm and the criteria are torch ops that are deterministic or raise / warn under torch's flag.  Limit: the two
+(C -> classes) heads and the timestep MLP are torch GEMMs (rocBLAS), which torch pins to atomic-free kernels only under
+torch.use_deterministic_algorithms(True); `train_deterministic = True` alone does not reach into them.
 """
 import warnings
 
@@ -41,6 +57,7 @@ from . import engine as _engine
 from . import _lib
 from ._lib import DuplicateVoxelsError
 from . import ops
+from .ops import det_kw as _det_kw  # (by name: tests swap `ops` for the CPU emulation, which has no such helper)
 from .losses import build_criteria
 
 
@@ -52,12 +69,51 @@ def _f32(shape, like):
     return torch.empty(shape, dtype=torch.float32, device=like.device)
 
 
+def resolve_deterministic(model):
+    """model.train_deterministic: None = torch.are_deterministic_algorithms_enabled(), True / False override."""
+    d = getattr(model, "train_deterministic", None)
+    if d is None:
+        return bool(torch.are_deterministic_algorithms_enabled())
+    if not isinstance(d, bool):
+        raise ValueError(f"train_deterministic must be None, True or False, not {d!r}")
+    return d
+
+
 # ------------------------------------------------------------------------------------------ autograd functions
+class _GatherRuns(torch.autograd.Function):
+    """y = x[idx] where the rows that read the same source row form one contiguous run (deterministic mode): seg (m + 1) int32
+    are the run starts - directly for the unpooling gather child[cluster] (the children of a pooled row are contiguous in the
+    plan's physical order: the seg of `_SegmentMax`), or of the rows taken in the order `perm` (the Mix3D fold: a stable sort
+    of rep).  The backward adds a run's rows in ascending order (ops.segment_sum) where torch's index backward uses atomics."""
+
+    @staticmethod
+    def forward(ctx, x, idx, seg, perm):
+        ctx.save_for_backward(seg, perm) if perm is not None else ctx.save_for_backward(seg)
+        ctx.m = x.shape[0]
+        return x[idx]
+
+    @staticmethod
+    def backward(ctx, dy):
+        seg = ctx.saved_tensors[0]
+        dy = dy.float()
+        if len(ctx.saved_tensors) > 1:
+            dy = dy[ctx.saved_tensors[1]]
+        return ops.segment_sum(_c(dy), seg, ctx.m), None, None, None
+
+
+def fold_runs(rep, m):
+    """(perm, seg) for `_GatherRuns` of x[rep]: perm = stable sort of rep, seg = run starts of the sorted values (m + 1, int32)."""
+    perm = torch.sort(rep, stable=True).indices
+    seg = torch.zeros(m + 1, dtype=torch.int32, device=rep.device)
+    seg[1:] = torch.bincount(rep, minlength=m).cumsum(0).to(torch.int32)
+    return perm, seg
+
+
 class _SubMConv(torch.autograd.Function):
     """y = bias + sum_o W_o x[nbr[o]] (spconv.SubMConv3d; ref call sites ptv3.py:356, 647, 1106, 1118)."""
 
     @staticmethod
-    def forward(ctx, x, w5, b, nbr):
+    def forward(ctx, x, w5, b, nbr, det=False):
         cout, cin = w5.shape[0], w5.shape[-1]
         kvol = nbr.shape[0]
         cp = (cin + 15) // 16 * 16  # the weight-gradient kernel works on 16-channel groups (stems: 6 -> 16)
@@ -72,6 +128,7 @@ class _SubMConv(torch.autograd.Function):
         ops.gemm(x, w, y, bias=b, nbr=nbr, kvol=kvol, nbr_kmajor=True, cache=cp == cin)
         ctx.save_for_backward(x, w, nbr)
         ctx.meta = (cin, cp, kvol, b is not None, tuple(w5.shape))
+        ctx.det = _det_kw(det)
         return y
 
     @staticmethod
@@ -82,7 +139,7 @@ class _SubMConv(torch.autograd.Function):
         dy = _c(dy)
         dw3 = torch.zeros((cout, kvol, cp), dtype=torch.float32, device=dy.device)
         db = torch.zeros(cout, dtype=torch.float32, device=dy.device) if has_b else None
-        ops.conv_wgrad(x, nbr, dy, dw3, db)
+        ops.conv_wgrad(x, nbr, dy, dw3, db, **ctx.det)
         dw5 = dw3[:, :, :cin].reshape(wshape)
         dx = None
         if ctx.needs_input_grad[0]:
@@ -92,17 +149,18 @@ class _SubMConv(torch.autograd.Function):
             dxp = _f32((x.shape[0], cp), dy)
             ops.gemm(dy, wt, dxp, nbr=nbr, kvol=kvol, nbr_kmajor=True, cache=False)  # wt: a per-call temporary
             dx = dxp[:, :cin]
-        return dx, dw5, db, None
+        return dx, dw5, db, None, None
 
 
 class _Linear(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w, b):
+    def forward(ctx, x, w, b, det=False):
         x, w = _c(x), _c(w)
         y = _f32((x.shape[0], w.shape[0]), x)
         ops.gemm(x, w, y, bias=b)
         ctx.save_for_backward(x, w)
         ctx.has_b = b is not None
+        ctx.det = _det_kw(det)
         return y
 
     @staticmethod
@@ -115,8 +173,8 @@ class _Linear(torch.autograd.Function):
             ops.gemm(dy, _c(w.t()), dx, cache=False)  # the transposed copy is a per-call temporary
         dw = torch.zeros_like(w)
         db = torch.zeros(w.shape[0], dtype=torch.float32, device=dy.device) if ctx.has_b else None
-        ops.linear_wgrad(x, dy, dw, db)
-        return dx, dw, db
+        ops.linear_wgrad(x, dy, dw, db, **ctx.det)
+        return dx, dw, db, None
 
 
 class _SubMConv16(torch.autograd.Function):
@@ -128,7 +186,7 @@ class _SubMConv16(torch.autograd.Function):
     The 16-bit weight copies are per-call temporaries (cache=False: no cache entry may pin them)."""
 
     @staticmethod
-    def forward(ctx, x, w5, b, nbr, variant):
+    def forward(ctx, x, w5, b, nbr, variant, det=False):
         t16 = ops.LP_DTYPES[variant]
         cout, cin = w5.shape[0], w5.shape[-1]
         kvol = nbr.shape[0]
@@ -144,6 +202,7 @@ class _SubMConv16(torch.autograd.Function):
             ops.gemm(x16, w16, y, bias=b, nbr=nbr, kvol=kvol, nbr_kmajor=True, cache=False)
         ctx.save_for_backward(x16, w16, nbr)
         ctx.meta = (cin, cp, kvol, b is not None, tuple(w5.shape), variant)
+        ctx.det = _det_kw(det)
         return y
 
     @staticmethod
@@ -156,13 +215,13 @@ class _SubMConv16(torch.autograd.Function):
         db = torch.zeros(cout, dtype=torch.float32, device=dy.device) if has_b else None
         dx = None
         with _lib.use(variant):
-            ops.conv_wgrad(x16, nbr, dy16, dw3, db)
+            ops.conv_wgrad(x16, nbr, dy16, dw3, db, **ctx.det)
             if ctx.needs_input_grad[0]:
                 wt = _c(w16.view(cout, kvol, cp).flip(1).permute(2, 1, 0)).view(cp, kvol * cout)
                 dxp = _f32((x16.shape[0], cp), dy)
                 ops.gemm(dy16, wt, dxp, nbr=nbr, kvol=kvol, nbr_kmajor=True, cache=False)
                 dx = dxp[:, :cin]
-        return dx, dw3[:, :, :cin].reshape(wshape), db, None, None
+        return dx, dw3[:, :, :cin].reshape(wshape), db, None, None, None
 
 
 class _Linear16(torch.autograd.Function):
@@ -170,7 +229,7 @@ class _Linear16(torch.autograd.Function):
     accumulation, fp32 y / dx / dw / db; the saved input is the 16-bit copy.  See _SubMConv16 for the casts."""
 
     @staticmethod
-    def forward(ctx, x, w, b, variant):
+    def forward(ctx, x, w, b, variant, det=False):
         t16 = ops.LP_DTYPES[variant]
         with _lib.use(variant):
             x16 = ops.cast(_c(x), t16)
@@ -179,6 +238,7 @@ class _Linear16(torch.autograd.Function):
             ops.gemm(x16, w16, y, bias=b, cache=False)
         ctx.save_for_backward(x16, w16)
         ctx.meta = (b is not None, variant)
+        ctx.det = _det_kw(det)
         return y
 
     @staticmethod
@@ -193,37 +253,38 @@ class _Linear16(torch.autograd.Function):
             if ctx.needs_input_grad[0]:
                 dx = _f32(x16.shape, dy)
                 ops.gemm(dy16, _c(w16.t()), dx, cache=False)
-            ops.linear_wgrad(x16, dy16, dw, db)
-        return dx, dw, db, None
+            ops.linear_wgrad(x16, dy16, dw, db, **ctx.det)
+        return dx, dw, db, None, None
 
 
-def linear(x, mod, variant=None):
+def linear(x, mod, variant=None, det=False):
     """nn.Linear on the library's GEMMs when both widths are multiples of 16 (every Linear of the trunk); the two heads
     (C -> classes / c_in) and the B-row timestep MLP are plain torch.  variant "f16" / "bf16": 16-bit products on that build
-    of the library (the AMP step), None: exact fp32."""
+    of the library (the AMP step), None: exact fp32.  det: the weight gradient in a fixed summation order."""
     w, b = mod.weight, mod.bias
     if w.shape[0] % 16 or w.shape[1] % 16 or x.shape[0] < 1:
         return F.linear(x, w, b)
     if variant is not None:
-        return _Linear16.apply(x, w, b, variant)
-    return _Linear.apply(x, w, b)
+        return _Linear16.apply(x, w, b, variant, det)
+    return _Linear.apply(x, w, b, det)
 
 
-def subm_conv(x, w5, b, nbr, variant=None):
-    """Submanifold conv on the offset-major kernel map; variant as in `linear`."""
+def subm_conv(x, w5, b, nbr, variant=None, det=False):
+    """Submanifold conv on the offset-major kernel map; variant and det as in `linear`."""
     if variant is not None:
-        return _SubMConv16.apply(x, w5, b, nbr, variant)
-    return _SubMConv.apply(x, w5, b, nbr)
+        return _SubMConv16.apply(x, w5, b, nbr, variant, det)
+    return _SubMConv.apply(x, w5, b, nbr, det)
 
 
 class _LayerNorm(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, g, b, eps):
+    def forward(ctx, x, g, b, eps, det=False):
         x = _c(x)
         y = torch.empty_like(x)
         ops.layernorm(x, g, b, y, eps=eps)
         ctx.save_for_backward(x, g)
         ctx.eps = eps
+        ctx.det = _det_kw(det)
         return y
 
     @staticmethod
@@ -233,12 +294,12 @@ class _LayerNorm(torch.autograd.Function):
         dx = torch.empty_like(x)
         dg = torch.zeros_like(g)
         db = torch.zeros_like(g)
-        ops.layernorm_bwd(x, g, dy, dx, accumulate=False, eps=ctx.eps, dgamma=dg, dbeta=db)
-        return dx, dg, db, None
+        ops.layernorm_bwd(x, g, dy, dx, accumulate=False, eps=ctx.eps, dgamma=dg, dbeta=db, **ctx.det)
+        return dx, dg, db, None, None
 
 
-def layernorm(x, mod):
-    return _LayerNorm.apply(x, mod.weight, mod.bias, float(mod.eps))
+def layernorm(x, mod, det=False):
+    return _LayerNorm.apply(x, mod.weight, mod.bias, float(mod.eps), det)
 
 
 TRAIN_PRECISIONS = {"fp32": None, "fp16-attn": "f16", "bf16-attn": "bf16",  # train_precision -> library build of the attention core
@@ -405,6 +466,7 @@ class TrainGraph:
         self.model = model
         self.attn_variant = None  # library build of the attention core, from model.train_precision at every forward
         self.mm_variant = None    # library build of the Linears and sparse convs ("-amp" modes), None = exact fp32
+        self.det = False          # fixed-order gradient reductions, from model.train_deterministic at every forward
         self.eng = _engine.Engine(model, "fp32")  # the plan builder (never prepared: no second copy of the weights)
         self.criteria = build_criteria(model.criteria_cfg, model.loss_type, model.task_num)
 
@@ -428,11 +490,17 @@ class TrainGraph:
         return torch.empty((st.x.shape[0], 1), dtype=torch.float32, device=st.x.device).bernoulli_(keep) / keep
 
     def _cpe(self, lv, x, seq):
-        y = subm_conv(x, seq[0].weight, seq[0].bias, lv.nbr(seq[0].kernel_size, True), self.mm_variant)
-        return layernorm(linear(y, seq[1], self.mm_variant), seq[2])
+        y = subm_conv(x, seq[0].weight, seq[0].bias, lv.nbr(seq[0].kernel_size, True), self.mm_variant, self.det)
+        return self._ln(self._lin(y, seq[1]), seq[2])
+
+    def _lin(self, x, mod):
+        return linear(x, mod, self.mm_variant, self.det)
+
+    def _ln(self, x, mod):
+        return layernorm(x, mod, self.det)
 
     def _mlp(self, h, mlp):
-        return linear(F.gelu(linear(h, mlp.fc1, self.mm_variant)), mlp.fc2, self.mm_variant)
+        return self._lin(F.gelu(self._lin(h, mlp.fc1)), mlp.fc2)
 
     def _block(self, st, mod, name, t_scene, masks):
         """ref: ptv3.py:399-428."""
@@ -444,15 +512,15 @@ class TrainGraph:
             x = x + _SceneRows.apply(F.linear(t_scene, mod.t_mlp.weight, mod.t_mlp.bias), lv.batch.long(), list(lv.offs_host))
         att = mod.attn
         c = x.shape[1]
-        qkv = linear(layernorm(x, mod.norm1[0]), att.qkv, self.mm_variant)
+        qkv = self._lin(self._ln(x, mod.norm1[0]), att.qkv)
         gidx, widx = lv.slots(st.curves[att.order_index], att.patch_size, att.enable_flash)
         patch_start, max_len = lv.pad(att.patch_size, att.enable_flash)[4:6]
         psh = lv.pad_host(att.patch_size, att.enable_flash)[3].tolist()
         o = attention_core(self.attn_variant, qkv, None, c, gidx, gidx, widx, patch_start, psh, att.num_heads, max_len, att.scale)
-        a = linear(o, att.proj, self.mm_variant)
+        a = self._lin(o, att.proj)
         m = self._mask(st, name + ".drop_path.0", mod.drop_prob, masks)
         x = x + (a if m is None else a * m)
-        h = self._mlp(layernorm(x, mod.norm2[0]), mod.mlp[0])
+        h = self._mlp(self._ln(x, mod.norm2[0]), mod.mlp[0])
         m = self._mask(st, name + ".drop_path.0", mod.drop_prob, masks)
         st.x = x + (h if m is None else h * m)
         return st
@@ -461,14 +529,14 @@ class TrainGraph:
         """ref: ptv3.py:633-663.  inv0: caller row -> physical row (the reference's level-0 order is the caller's)."""
         lv = plan.levels[0]
         x = feat[plan.perm0.long()]
-        y = subm_conv(x, emb.stem.conv.weight, None, lv.nbr(emb.stem.conv.kernel_size, True), self.mm_variant)
+        y = subm_conv(x, emb.stem.conv.weight, None, lv.nbr(emb.stem.conv.kernel_size, True), self.mm_variant, self.det)
         return _St(lv, _bn_gelu(y, emb.stem.norm), curves, inv0)
 
     def _pooling(self, plan, st, down, cum_to, perm):
         """ref: ptv3.py:464-555."""
         fine, coarse = st.level, plan.levels[cum_to]
         cluster, seg = plan.link(fine.cum, cum_to)
-        y = _SegmentMax.apply(linear(st.x, down.proj, self.mm_variant), seg, cluster, coarse.n)
+        y = _SegmentMax.apply(self._lin(st.x, down.proj), seg, cluster, coarse.n)
         curves = st.curves if perm is None else [st.curves[int(j)] for j in perm]
         order = coarse.order(st.curves[0])  # the reference numbers the pooled points by unique(code[0]) (ptv3.py:489)
         if order is None:
@@ -479,9 +547,9 @@ class TrainGraph:
         """ref: ptv3.py:597-630."""
         parent = st.parent
         fine, coarse = parent.level, st.level
-        cluster, _ = plan.link(fine.cum, coarse.cum)
-        child = _bn_gelu(linear(st.x, up.proj[0], self.mm_variant), up.proj[1])
-        par = _bn_gelu(linear(parent.x, up.proj_skip[0], self.mm_variant), up.proj_skip[1])
+        cluster, seg = plan.link(fine.cum, coarse.cum)
+        child = _bn_gelu(self._lin(st.x, up.proj[0]), up.proj[1])
+        par = _bn_gelu(self._lin(parent.x, up.proj_skip[0]), up.proj_skip[1])
         out = _St(fine, None, parent.curves, parent.ref_order, parent=parent.parent)
         out.conv = par  # what the next Block's CPE conv reads: the skip feature before scaling and merging
         f = 2 ** -0.5 if up.skip_connection_scale else 1.0
@@ -489,11 +557,14 @@ class TrainGraph:
             f *= 0.8 ** (int(up.skip_connection_scale_i) - 1)
         if f != 1.0:
             par = par * f
-        gathered = child[cluster.long()]
+        if self.det:  # the index backward would add a pooled row's (up to eight) children with atomics
+            gathered = _GatherRuns.apply(child, cluster.long(), seg[:coarse.n + 1], None)
+        else:
+            gathered = child[cluster.long()]
         if up.skip_connection_mode == "add":
             out.x = par + gathered
         else:
-            out.x = linear(torch.cat([par, gathered], dim=-1), up.proj_cat[0], self.mm_variant)
+            out.x = self._lin(torch.cat([par, gathered], dim=-1), up.proj_cat[0])
         return out
 
     def _cross_block(self, nst, cst, cb, masks):
@@ -503,23 +574,23 @@ class TrainGraph:
             raise _engine.CdsegError("cross attention needs the same number of c- and n-branch bottleneck points per batch element")
         xq = nst.x + self._cpe(lv, nst.x, cb.q_cpe)
         xkv = cst.x + self._cpe(clv, cst.x, cb.kv_cpe)
-        hq, hkv = layernorm(xq, cb.q_norm1[0]), layernorm(xkv, cb.kv_norm1[0])
+        hq, hkv = self._ln(xq, cb.q_norm1[0]), self._ln(xkv, cb.kv_norm1[0])
         cst.x = hkv  # the kv point leaves the block holding its normed feature (modules.py:68-73)
         att = cb.attn
         cq = xq.shape[1]
-        q = linear(hq, att.q, self.mm_variant)
-        kv = linear(hkv, att.kv, self.mm_variant)
+        q = self._lin(hq, att.q)
+        kv = self._lin(hkv, att.kv)
         K = att.q_patch_size
         q_gidx, widx = lv.slots(nst.curves[att.order_index], K, att.enable_flash)
         kv_gidx, _ = clv.slots(cst.curves[att.order_index], K, att.enable_flash)
         patch_start, max_len = lv.pad(K, att.enable_flash)[4:6]
         psh = lv.pad_host(K, att.enable_flash)[3].tolist()
         o = attention_core(self.attn_variant, q, kv, cq, q_gidx, kv_gidx, widx, patch_start, psh, att.num_heads, max_len, att.scale)
-        a = linear(o, att.proj, self.mm_variant)
+        a = self._lin(o, att.proj)
         name = "backbone._tm_dec0.cross_block2.drop_path.0"
         m = self._mask(nst, name, cb.drop_prob, masks)
         x = xq + cb.tm_feat * (a if m is None else a * m)
-        h = self._mlp(layernorm(x, cb.q_norm2[0]), cb.mlp[0])
+        h = self._mlp(self._ln(x, cb.q_norm2[0]), cb.mlp[0])
         m = self._mask(nst, name, cb.drop_prob, masks)
         nst.x = x + (h if m is None else h * m)
 
@@ -542,6 +613,7 @@ class TrainGraph:
             raise ValueError(f"train_precision must be one of {sorted(TRAIN_PRECISIONS)}, not {tp!r}")
         self.attn_variant = TRAIN_PRECISIONS[tp]
         self.mm_variant = TRAIN_PRECISIONS[tp] if tp.endswith("-amp") else None
+        self.det = resolve_deterministic(self.model)
         if feat_is_cuda(input_dict):
             with torch.autocast(device_type="cuda", enabled=False):
                 return self._forward(input_dict, draws)
@@ -669,9 +741,13 @@ class TrainGraph:
         point["n_pred"] = n_phys[inv0]
         if rep is not None:  # folded duplicates: back to the caller's N rows (and its offsets, which the criteria sample by)
             point["offset"] = offset_in
+            runs = fold_runs(rep, n) if self.det else None
             for k in ("n_pred", "c_pred", "c_target"):
                 if point.get(k) is not None:
-                    point[k] = point[k][rep]
+                    if runs is not None and point[k].requires_grad:
+                        point[k] = _GatherRuns.apply(point[k], rep, runs[1], runs[0])
+                    else:
+                        point[k] = point[k][rep]
         point["n_target"] = input_dict["segment"]
         loss = self.criteria(point)
         return dict(loss=loss, n_pred=point["n_pred"], c_pred=point.get("c_pred"), c_target=point.get("c_target"))

@@ -639,6 +639,38 @@ int cdseg_linear_wgrad16(const void* x, int ldx, const int32_t* xidx, const void
 int cdseg_conv_wgrad16(const void* x, int ldx, const int32_t* nbr_kmajor, int kvol, const void* dy, int lddy, long m, int cin,
                        int cout, float* dw, float* db, void* stream);
 
+/* ------------------------------------------------------------------ deterministic training (fixed-order gradient reductions)
+ * Opt-in forms of the reductions above whose fp32 summation order is FIXED, so that two runs of a training step give the
+ * same bits.  The default entry points are unchanged.  Contract of the order:
+ *   weight gradient   same tiling, main loop and row partition as the default form (dtype CDSEG_F32: the fp32 kernel,
+ *                     CDSEG_BF16: the 16-bit kernel of this build).  Split s of the rows (cdseg_wgrad_partition) leaves its
+ *                     partial dW tile and db partial in the workspace with plain stores (a split without live rows stores
+ *                     zeros); a second launch computes  t = p[0]; t += p[1]; ... by ascending split index  and then
+ *                     dw = dw + t, db = db + t_b: ONE add onto the existing content (accumulate-into, as above).
+ *   LayerNorm         dx as the default form.  A 64-row block sums dgamma / dbeta as the default form does (per-wave
+ *                     registers, the fixed 4-wave tree) and stores its partial row; a second launch adds the rows by
+ *                     ascending block index, then dgamma = dgamma + t, dbeta = dbeta + t.  c <= 512, wider rows:
+ *                     CDSEG_ERR_UNSUPPORTED (the default form handles them with per-element atomics).
+ *   segment sum       out[j] = sum_i src[i], i = seg_start[j] .. seg_start[j + 1] - 1 ascending (out is overwritten; an empty
+ *                     run gives 0): the backward of the unpooling gather child[cluster], whose children are contiguous.
+ * No block waits for another; the library allocates nothing.  Status codes, checked before any launch:
+ *   CDSEG_ERR_WORKSPACE    ws NULL or ws_bytes below the matching _ws_bytes query.
+ *   CDSEG_ERR_ARG          CDSEG_BF16: as the 16-bit forms above (16-byte aligned pointers, ldx / lddy multiples of 8);
+ *                          CDSEG_F32: a NULL or not 4-byte aligned operand; ws not 16-byte aligned.
+ *   CDSEG_ERR_UNSUPPORTED  another dtype; n, k (cin, cout) not multiples of 16.
+ * The partition query is host only: the launch rule is a function of (m, n, k, kvol, dtype) alone (kvol = 1: the Linear form)
+ * and never asks the device.  It returns the rows per split (the last split may be shorter) and the number of splits. */
+int cdseg_wgrad_partition(long m, int n, int k, int kvol, int dtype, long* rows_per_split, int* splits);
+size_t cdseg_wgrad_det_ws_bytes(long m, int n, int k, int kvol, int dtype);
+int cdseg_linear_wgrad_det(const void* x, int ldx, const int32_t* xidx, const void* dy, int lddy, long m, int k, int n, float* dw,
+                           int lddw, float* db, int dtype, void* ws, size_t ws_bytes, void* stream);
+int cdseg_conv_wgrad_det(const void* x, int ldx, const int32_t* nbr_kmajor, int kvol, const void* dy, int lddy, long m, int cin,
+                         int cout, float* dw, float* db, int dtype, void* ws, size_t ws_bytes, void* stream);
+size_t cdseg_layernorm_bwd_det_ws_bytes(long m, int c);
+int cdseg_layernorm_bwd_det(const float* x, int ldx, const float* gamma, float eps, const float* dy, int lddy, float* dx, int lddx,
+                            int accumulate, float* dgamma, float* dbeta, long m, int c, void* ws, size_t ws_bytes, void* stream);
+int cdseg_segment_sum(const float* src, int ld, const int32_t* seg_start, long m, int c, float* out, int ldo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
