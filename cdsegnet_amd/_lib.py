@@ -213,6 +213,11 @@ SIGNATURES = {
     "cdseg_layernorm_bwd_det": (c_int, [c_void_p, c_int, c_void_p, c_float, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
                                         c_void_p, c_long, c_int, c_void_p, c_size_t, c_void_p]),
     "cdseg_segment_sum": (c_int, [c_void_p, c_int, c_void_p, c_long, c_int, c_void_p, c_int, c_void_p]),
+    "cdseg_seg_loss_ws_bytes": (c_size_t, [c_long, c_int]),
+    "cdseg_seg_loss_fwd": (c_int, [c_void_p, c_int, c_void_p, c_long, c_int, c_long, c_int, c_void_p, POINTER(c_int32), c_void_p,
+                                   c_void_p, c_void_p, c_size_t, c_void_p]),
+    "cdseg_seg_loss_bwd": (c_int, [c_void_p, c_int, c_void_p, c_long, c_int, c_long, POINTER(c_int32), c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_int, c_void_p]),
     "cdseg_prof_enable": (c_int, [c_int]),
     "cdseg_prof_summary": (c_int, [POINTER(ctypes.c_double), POINTER(c_long)]),
     "cdseg_prof_summary_class": (c_int, [c_int, POINTER(ctypes.c_double), POINTER(c_long)]),

@@ -112,17 +112,19 @@ class Criteria:
             self.criteria.append(_TYPES[t](**c))
         self.loss_type, self.task_num = loss_type, task_num
 
-    def __call__(self, point):
-        if not self.criteria:
+    def __call__(self, point, criteria=None):
+        """criteria: the callables to combine, `self.criteria` unless a subclass substitutes some (FusedCriteria)."""
+        criteria = self.criteria if criteria is None else criteria
+        if not criteria:
             return point
         mode = point["loss_mode"]
         if mode == "eval" or self.loss_type == "EW":
             loss = 0.0
-            for c in self.criteria:
+            for c in criteria:
                 loss = loss + c(point)
             return loss
         if mode == "train" and self.loss_type == "GLS":
-            parts = [c(point) for c in self.criteria]
+            parts = [c(point) for c in criteria]
             if self.task_num == 1:
                 loss = parts[0] + parts[1]
             elif self.task_num == 2 and self.task_num != len(parts):
@@ -133,5 +135,93 @@ class Criteria:
         return 0.0  # (builder.py:27: any other combination leaves the sum at its initial value)
 
 
-def build_criteria(cfg, loss_type="EW", task_num=2):
+TRAIN_LOSSES = ("torch", "fused")  # model.train_loss
+
+
+class _SegLossFn(torch.autograd.Function):
+    """(ce, lovasz) of logits / labels on the HIP kernels of csrc/loss.hip (ops.seg_loss, ops.seg_loss_bwd).  `plan` is the
+    host side of the one read (ops.seg_loss_plan), made by the caller because it decides whether there is a fused form."""
+
+    @staticmethod
+    def forward(ctx, logits, plan):
+        from . import ops
+        ce, lovasz, saved = ops.seg_loss(logits, plan["labels"], plan["ignore_index"], plan)
+        ctx.save_for_backward(logits, saved["labels"], saved["coef"])
+        ctx.plan = plan
+        return ce, lovasz
+
+    @staticmethod
+    def backward(ctx, g_ce, g_lovasz):
+        from . import ops
+        logits, labels, coef = ctx.saved_tensors
+        return ops.seg_loss_bwd(logits, dict(ctx.plan, labels=labels, coef=coef), g_ce, g_lovasz), None
+
+
+class _Scaled:
+    """Stands in a fused pair's slot of the criteria list: the precomputed term times the criterion's loss_weight."""
+
+    def __init__(self, value, loss_weight):
+        self.value, self.loss_weight = value, loss_weight
+
+    def __call__(self, point):
+        return self.value * self.loss_weight
+
+
+class FusedCriteria(Criteria):
+    """`Criteria` whose cross-entropy and Lovasz terms come from ONE fused HIP loss (model.train_loss = "fused") when
+      - the list holds exactly one plain CrossEntropyLoss (no weight, label_smoothing 0, reduction "mean") and one LovaszLoss on
+        the same pred / target with the same ignore_index, and that ignore_index is truthy (with 0 / None the reference's
+        cross entropy does not filter while its Lovasz term does: the two terms then see different rows),
+      - both tensors are on the device, fp32 logits (N, C) and int64 labels, within the kernels' limits (N < 2^24, C <= 256),
+      - the batch has a valid row;
+    anything else takes the torch path of `Criteria`, silently and bit for bit.  The MSE term, the EW / GLS combination and the
+    loss_weights stay torch ops.  Sort ties: descending error, then ascending row index (include/cdseg.h)."""
+
+    def _pair(self):
+        ces = [c for c in self.criteria if type(c) is CrossEntropyLoss]
+        lvs = [c for c in self.criteria if type(c) is LovaszLoss]
+        if len(ces) != 1 or len(lvs) != 1:
+            return None
+        ce, lv = ces[0], lvs[0]
+        if ce.weight is not None or ce.label_smoothing != 0.0 or ce.reduction != "mean":
+            return None
+        if (ce.pred, ce.target) != (lv.pred, lv.target) or not ce.ignore_index or ce.ignore_index != lv.ignore_index:
+            return None
+        return ce, lv
+
+    def _fused_terms(self, point):
+        pair = self._pair()
+        if pair is None:
+            return None
+        ce, lv = pair
+        pred, target = point.get(ce.pred), point.get(ce.target)
+        if not (torch.is_tensor(pred) and torch.is_tensor(target) and pred.is_cuda and target.is_cuda):
+            return None
+        if pred.dtype != torch.float32 or target.dtype != torch.int64 or pred.dim() != 2 or target.shape != pred.shape[:1]:
+            return None
+        if pred.shape[0] == 0 or pred.shape[0] >= 1 << 24 or pred.shape[1] > 256:
+            return None
+        from . import ops
+        logits = pred if pred.stride(1) == 1 else pred.contiguous()
+        plan = ops.seg_loss_plan(logits, target, int(ce.ignore_index))
+        if plan is None:  # no valid row: torch's own nan / 0 stand
+            return None
+        v_ce, v_lv = _SegLossFn.apply(logits, plan)
+        return {id(ce): _Scaled(v_ce, ce.loss_weight), id(lv): _Scaled(v_lv, lv.loss_weight)}
+
+    def __call__(self, point):
+        if not self.criteria:
+            return point
+        terms = self._fused_terms(point)
+        if terms is None:
+            return super().__call__(point)
+        return super().__call__(point, [terms.get(id(c), c) for c in self.criteria])
+
+
+def build_criteria(cfg, loss_type="EW", task_num=2, train_loss="torch"):
+    """train_loss "torch" (default): the torch criteria, as ever; "fused": FusedCriteria."""
+    if train_loss not in TRAIN_LOSSES:
+        raise ValueError(f"train_loss must be one of {TRAIN_LOSSES}, not {train_loss!r}")
+    if train_loss == "fused":
+        return FusedCriteria(cfg, loss_type=loss_type, task_num=task_num)
     return Criteria(cfg, loss_type=loss_type, task_num=task_num)

@@ -434,6 +434,11 @@ class DefaultSegmentorV2(nn.Module):
         # None (default) = follow torch.are_deterministic_algorithms_enabled() | True | False; read at every forward(),
         # not part of the state_dict
         self.train_deterministic = None
+        # the two label terms of the criteria (cross entropy + Lovasz): "torch" (default: cdsegnet_amd/losses.py's torch ops) |
+        # "fused": one HIP loss, forward and backward, where the configured pair allows it (losses.FusedCriteria; sort ties by
+        # ascending row index); read at every forward() and by the loss of inference(eval=True), anything else raises
+        # ValueError there; not part of the state_dict
+        self.train_loss = "torch"
         self._lanes = {}
         self.noise_source = "torch_cpu"  # "torch_cpu" replays the reference's CPU-generator draws | "device"
         # noise_level jitter: "torch_cpu" = the CPU-run reference's draw order (golden vectors) | "device" = device
@@ -477,7 +482,7 @@ class DefaultSegmentorV2(nn.Module):
             # c_pred and contributes 0.0, losses/misc.py:53-54): cross entropy + Lovasz, summed whatever the loss_type
             from .losses import build_criteria
             point = dict(n_pred=logits, n_target=input_dict["segment"], loss_mode="eval")
-            return dict(loss=build_criteria(self.criteria_cfg, self.loss_type, self.task_num)(point), seg_logits=logits)
+            return dict(loss=build_criteria(self.criteria_cfg, self.loss_type, self.task_num, getattr(self, "train_loss", "torch"))(point), seg_logits=logits)
         return dict(seg_logits=logits)
 
     @torch.no_grad()
@@ -577,7 +582,7 @@ class DefaultSegmentorV2(nn.Module):
         if eval:  # ref: default.py:361-367
             from .losses import build_criteria
             point = dict(n_pred=logits, n_target=input_dict["segment"], loss_mode="eval")
-            return dict(loss=build_criteria(self.criteria_cfg, self.loss_type, self.task_num)(point), seg_logits=logits)
+            return dict(loss=build_criteria(self.criteria_cfg, self.loss_type, self.task_num, getattr(self, "train_loss", "torch"))(point), seg_logits=logits)
         return dict(seg_logits=logits)
 
     def forward(self, input_dict, draws=None):

@@ -1302,3 +1302,66 @@ def segment_sum(src, seg_start, m):
     check(_lib.load().cdseg_segment_sum(_ptr(src), src.stride(0), _ptr(seg_start), int(m), src.shape[1], _ptr(out), out.stride(0),
                                         _stream()), "segment_sum")
     return out
+
+
+# ------------------------------------------------------------------ fused segmentation loss (csrc/loss.hip)
+def seg_loss_plan(logits, labels, ignore_index):
+    """The fused loss's ONE host read: the label histogram of the valid rows (cdseg_seg_loss_fwd phase 0).  Returns the plan
+    `seg_loss` needs - dict(labels, ignore_index, hist_host, n_valid, present) - or None for a batch without a valid row (no
+    fused form: the caller's torch path produces the reference's nan / 0).  Labels outside [0, C) other than ignore_index raise."""
+    _need_gpu(logits, labels)
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise _lib.CdsegError("seg_loss: logits must be fp32 (N, C) with contiguous rows")
+    n, c = logits.shape
+    if labels.dtype != torch.int64 or labels.shape != (n,):
+        raise _lib.CdsegError("seg_loss: labels must be int64 (N)")
+    labels = labels.contiguous()
+    ign = int(ignore_index)
+    hist = torch.empty(c + 1, dtype=torch.int32, device=logits.device)
+    check(_lib.load().cdseg_seg_loss_fwd(_ptr(logits), logits.stride(0), _ptr(labels), n, c, ign, 0, _ptr(hist), None, None, None,
+                                         None, 0, _stream()), "seg_loss (histogram)")
+    hist_list = hist.tolist()  # the one host read
+    if hist_list[c]:
+        raise _lib.CdsegError(f"seg_loss: {hist_list[c]} labels outside [0, {c}) that are not ignore_index = {ign}")
+    n_valid, present = sum(hist_list[:c]), sum(1 for v in hist_list[:c] if v)
+    if n_valid == 0:
+        return None
+    return dict(labels=labels, ignore_index=ign, hist_host=(ctypes.c_int32 * (c + 1))(*hist_list), n_valid=n_valid, present=present)
+
+
+def seg_loss(logits, labels, ignore_index, plan=None):
+    """Cross entropy + multi-class Lovasz-Softmax (classes present, whole batch) of fp32 logits (N, C; any row stride) and int64
+    labels in a handful of launches (cdseg_seg_loss_fwd; definition and tie rule - descending error, ascending row index - in
+    include/cdseg.h).  Returns (ce, lovasz, saved): two 0-dim fp32 tensors and what `seg_loss_bwd` needs (the plan + coef).
+    plan: from `seg_loss_plan` on the same tensors (made here when None); a batch without a valid row gives (None, None, None)."""
+    if plan is None:
+        plan = seg_loss_plan(logits, labels, ignore_index)
+        if plan is None:
+            return None, None, None
+    _need_gpu(logits)
+    n, c = logits.shape
+    lib = _lib.load()
+    out = torch.empty(2, dtype=torch.float32, device=logits.device)
+    coef = torch.empty((n, plan["present"]), dtype=torch.float32, device=logits.device)
+    ws = torch.empty(max(16, lib.cdseg_seg_loss_ws_bytes(n, c)), dtype=torch.uint8, device=logits.device)
+    check(lib.cdseg_seg_loss_fwd(_ptr(logits), logits.stride(0), _ptr(plan["labels"]), n, c, plan["ignore_index"], 1, None,
+                                 plan["hist_host"], _ptr(out), _ptr(coef), _ptr(ws), ws.numel(), _stream()), "seg_loss")
+    return out[0], out[1], dict(plan, coef=coef)
+
+
+def seg_loss_bwd(logits, saved, g_ce, g_lovasz):
+    """dlogits (N, C) fp32 = g_ce * dCE/dlogits + g_lovasz * dLovasz/dlogits in one launch (cdseg_seg_loss_bwd); g_* are 0-dim
+    fp32 device tensors or None (= 0); `saved` from `seg_loss` on the same logits."""
+    _need_gpu(logits)
+    n, c = logits.shape
+    gs = []
+    for g in (g_ce, g_lovasz):
+        if g is not None:
+            _need_gpu(g)
+            g = g.reshape(1).to(torch.float32).contiguous()
+        gs.append(g)
+    dlogits = torch.empty((n, c), dtype=torch.float32, device=logits.device)
+    check(_lib.load().cdseg_seg_loss_bwd(_ptr(logits), logits.stride(0), _ptr(saved["labels"]), n, c, saved["ignore_index"],
+                                         saved["hist_host"], _ptr(saved["coef"]), _ptr(gs[0]), _ptr(gs[1]), _ptr(dlogits),
+                                         dlogits.stride(0), _stream()), "seg_loss_bwd")
+    return dlogits

@@ -47,6 +47,11 @@ two values onto a zeroed element (a row sits in at most two slots), which commut
 train-mode BatchNorm and the criteria are torch ops that are deterministic or raise / warn under torch's flag.  Limit: the two
 (C -> classes) heads and the timestep MLP are torch GEMMs (rocBLAS), which torch pins to atomic-free kernels only under
 torch.use_deterministic_algorithms(True); `train_deterministic = True` alone does not reach into them.
+
+Fused loss (`model.train_loss = "fused"`, default "torch"; read at every forward): the cross-entropy and Lovasz terms of the
+criteria, forward and backward, on the kernels of csrc/loss.hip (losses.FusedCriteria -> ops.seg_loss / ops.seg_loss_bwd) instead
+of torch's per-class sort loop.  Its sums run in a fixed order whatever `train_deterministic` says, and the Lovasz sort breaks
+ties by ascending row index, where torch's unstable sort leaves the order (and with it the gradient of tied rows) open.
 """
 import warnings
 
@@ -58,7 +63,7 @@ from . import _lib
 from ._lib import DuplicateVoxelsError
 from . import ops
 from .ops import det_kw as _det_kw  # (by name: tests swap `ops` for the CPU emulation, which has no such helper)
-from .losses import build_criteria
+from .losses import TRAIN_LOSSES, build_criteria
 
 
 def _c(t):
@@ -302,6 +307,14 @@ def layernorm(x, mod, det=False):
     return _LayerNorm.apply(x, mod.weight, mod.bias, float(mod.eps), det)
 
 
+def resolve_train_loss(model):
+    """model.train_loss: "torch" (default) or "fused" (losses.FusedCriteria); anything else raises."""
+    tl = getattr(model, "train_loss", "torch")
+    if tl not in TRAIN_LOSSES:
+        raise ValueError(f"train_loss must be one of {sorted(TRAIN_LOSSES)}, not {tl!r}")
+    return tl
+
+
 TRAIN_PRECISIONS = {"fp32": None, "fp16-attn": "f16", "bf16-attn": "bf16",  # train_precision -> library build of the attention core
                     "fp16-amp": "f16", "bf16-amp": "bf16"}                   # (-amp: of the Linears and sparse convs too)
 
@@ -469,6 +482,8 @@ class TrainGraph:
         self.det = False          # fixed-order gradient reductions, from model.train_deterministic at every forward
         self.eng = _engine.Engine(model, "fp32")  # the plan builder (never prepared: no second copy of the weights)
         self.criteria = build_criteria(model.criteria_cfg, model.loss_type, model.task_num)
+        self.fused_criteria = None  # losses.FusedCriteria, built when model.train_loss first says "fused"
+        self.train_loss = "torch"   # from model.train_loss at every forward
 
     # ---------------------------------------------------------------------------------------- pieces
     def _mask(self, st, name, rate, masks):
@@ -614,6 +629,7 @@ class TrainGraph:
         self.attn_variant = TRAIN_PRECISIONS[tp]
         self.mm_variant = TRAIN_PRECISIONS[tp] if tp.endswith("-amp") else None
         self.det = resolve_deterministic(self.model)
+        self.train_loss = resolve_train_loss(self.model)
         if feat_is_cuda(input_dict):
             with torch.autocast(device_type="cuda", enabled=False):
                 return self._forward(input_dict, draws)
@@ -749,5 +765,10 @@ class TrainGraph:
                     else:
                         point[k] = point[k][rep]
         point["n_target"] = input_dict["segment"]
-        loss = self.criteria(point)
+        if self.train_loss == "fused":
+            if self.fused_criteria is None:
+                self.fused_criteria = build_criteria(self.model.criteria_cfg, self.model.loss_type, self.model.task_num, "fused")
+            loss = self.fused_criteria(point)
+        else:
+            loss = self.criteria(point)
         return dict(loss=loss, n_pred=point["n_pred"], c_pred=point.get("c_pred"), c_target=point.get("c_target"))

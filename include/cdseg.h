@@ -671,6 +671,44 @@ int cdseg_layernorm_bwd_det(const float* x, int ldx, const float* gamma, float e
                             int accumulate, float* dgamma, float* dbeta, long m, int c, void* ws, size_t ws_bytes, void* stream);
 int cdseg_segment_sum(const float* src, int ld, const int32_t* seg_start, long m, int c, float* out, int ldo, void* stream);
 
+/* ------------------------------------------------------------------ fused segmentation loss (csrc/loss.hip)
+ * ref: losses/misc.py:95-132 (CrossEntropyLoss, reduction "mean"), losses/lovasz.py:118-165, 210-265 (multi-class
+ * Lovasz-Softmax over the classes present, whole batch).  logits (n, c) fp32 with row stride ldl, labels (n) int64.
+ *   valid rows: label != ignore_index (n_valid of them);  p = softmax(logits) per row, fp32
+ *   CE = -(1 / n_valid) sum_valid log p[i, y_i]
+ *   per present class c (a distinct label among the valid rows, P of them): fg_i = [y_i == c], err_i = |fg_i - p[i, c]| over
+ *     the valid rows, sorted by err DESCENDING, TIES BY ASCENDING ROW INDEX (the reference leaves the tie order to an unstable
+ *     sort; this rule makes the gradient a function of the input);  F_k / B_k = inclusive foreground / background counts,
+ *     T = sum fg, jac_k = 1 - (T - F_k) / (T + B_k), d_0 = jac_0, d_k = jac_k - jac_{k-1}, L_c = sum_k err_(k) d_k
+ *   Lovasz = (1 / P) sum_c L_c
+ *   backward (jac is a constant, as in the reference): coef[i, c] = -+ d_rank(i, c) / P (- on foreground rows),
+ *     dCE / dlogit[i, j] = (p_ij - [j == y_i]) / n_valid,  dLovasz / dlogit[i, j] = p_ij (coef_ij - sum_k coef_ik p_ik);
+ *     ignored rows get zeros.
+ * Two phases around the caller's ONE host read:
+ *   phase 0  hist (c + 1 int32, device) <- rows per class over the valid rows; hist[c] = labels outside [0, c) that are not
+ *            ignore_index (a caller error).  Needs logits / labels / hist only.
+ *   phase 1  hist_host = the caller's host copy of hist.  out[0] = CE, out[1] = Lovasz (device floats);
+ *            coef (n, P) fp32, row stride P: column r = the r-th present class in ascending class order; rows of ignored
+ *            points are not written.  ws from cdseg_seg_loss_ws_bytes(n, c) (sized for P = c), 16-byte aligned.
+ * cdseg_seg_loss_bwd: dlogits (n, c; row stride lddl) = g_ce[0] * dCE + g_lovasz[0] * dLovasz, one launch that recomputes p;
+ *   g_ce / g_lovasz are DEVICE floats (NULL = 0), hist_host and coef as in phase 1.
+ * Every float sum runs in an order fixed by the shape (no float atomics): equal inputs give equal bits.
+ * Status codes, checked before any launch:
+ *   CDSEG_ERR_ARG          NULL / misaligned pointer, n <= 0, c <= 0, ld < c, another phase; hist_host with hist_host[c] != 0,
+ *                          counts beyond n or NO valid row (the empty batch has no fused form: nan / 0 are the caller's)
+ *   CDSEG_ERR_UNSUPPORTED  n >= 2^24 or c > 256 (the 64-bit sort key: 8 bits class rank, 31 bits error, 24 bits row, 1 bit fg)
+ *   CDSEG_ERR_WORKSPACE    ws NULL, ws_bytes below the query, or (phase 1) below what the sort of the n x P keys needs.
+ *   CDSEG_ERR_LAUNCH       (phase 1, before any launch) the sort's storage query failed - no device.
+ * cdseg_seg_loss_ws_bytes asks rocPRIM on the current device; without a device the sort's share cannot be sized and is left
+ * out (a lower bound). */
+size_t cdseg_seg_loss_ws_bytes(long n, int c);
+int cdseg_seg_loss_fwd(const float* logits, int ldl, const int64_t* labels, long n, int c, long ignore_index, int phase,
+                       int32_t* hist, const int32_t* hist_host, float* out, float* coef, void* ws, size_t ws_bytes,
+                       void* stream);
+int cdseg_seg_loss_bwd(const float* logits, int ldl, const int64_t* labels, long n, int c, long ignore_index,
+                       const int32_t* hist_host, const float* coef, const float* g_ce, const float* g_lovasz, float* dlogits,
+                       int lddl, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

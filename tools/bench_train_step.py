@@ -3,8 +3,9 @@
 with a 16-bit attention core, or under AMP (16-bit attention core, Linears and sparse convs; train_precision), on the HIP kernels (cdsegnet_amd/train_graph.py).  Not a BASELINE metric - the reference publishes no training throughput -
 a first number for the training row of SURVEY 8(f4).
 usage: python tools/bench_train_step.py [scenes=1] [points=120000] [steps=4] [dataset=scannet|scannet200|nuscenes]
-       [train_precision=fp32|fp16-attn|bf16-attn|fp16-amp|bf16-amp] [det]
-A trailing `det` sets train_deterministic = True (fixed-order gradient reductions: bit-reproducible steps)."""
+       [train_precision=fp32|fp16-attn|bf16-attn|fp16-amp|bf16-amp] [det] [fused]
+A trailing `det` sets train_deterministic = True (fixed-order gradient reductions: bit-reproducible steps), a trailing `fused`
+sets train_loss = "fused" (cross entropy + Lovasz on the HIP loss kernels instead of the torch criteria)."""
 import os, sys, time
 import numpy as np
 import torch
@@ -20,7 +21,8 @@ points = int(sys.argv[2]) if len(sys.argv) > 2 else 120000
 steps = int(sys.argv[3]) if len(sys.argv) > 3 else 4
 dataset = sys.argv[4] if len(sys.argv) > 4 else "scannet"
 train_precision = sys.argv[5] if len(sys.argv) > 5 else "fp32"
-deterministic = len(sys.argv) > 6 and sys.argv[6] == "det"
+deterministic = "det" in sys.argv[6:]
+fused = "fused" in sys.argv[6:]
 dev = torch.device("cuda")
 cfg = configs.cdsegnet_config(dataset)
 cfg["criteria"] = [dict(type="MSELoss", loss_weight=1.0, ignore_index=-1, batch_sample_point=-1),
@@ -31,6 +33,8 @@ model.load_state_dict(fill_state_dict(model.state_dict(), seed=0), strict=True)
 model = model.to(dev).train()
 model.train_precision = train_precision
 model.train_deterministic = deterministic
+if fused:
+    model.train_loss = "fused"
 sc = synth.collate([(synth.lidar_scene(i, points) if dataset == "nuscenes" else synth.room_scene(i, points)) for i in range(scenes)])
 inp = {k: torch.as_tensor(sc[k]).to(dev) for k in ("coord", "grid_coord", "feat", "offset")}
 inp["segment"] = (torch.as_tensor(np.asarray(sc["segment"]).astype(np.int64)) % cfg["num_classes"]).to(dev)
@@ -56,6 +60,6 @@ for it in range(steps + 1):
     if it:
         times.append((t1 - t0, t2 - t1, t3 - t2))
 t = np.median(np.array(times), axis=0) * 1e3
-print(f"training step, {dataset}, full width, {train_precision}{', deterministic' if deterministic else ''}, {scenes} scene(s), {n} points: forward {t[0]:.1f} ms, backward {t[1]:.1f} ms, "
+print(f"training step, {dataset}, full width, {train_precision}{', deterministic' if deterministic else ''}{', fused loss' if fused else ''}, {scenes} scene(s), {n} points: forward {t[0]:.1f} ms, backward {t[1]:.1f} ms, "
       f"AdamW {t[2]:.1f} ms = {t.sum():.1f} ms/step = {n / t.sum() * 1e3 / 1e6:.2f} M points/s; peak memory "
       f"{torch.cuda.max_memory_allocated() / 2**30:.1f} GiB; loss over the steps {[round(v, 4) for v in losses]}")
