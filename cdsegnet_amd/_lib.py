@@ -96,6 +96,18 @@ class PlanFinishIO(Structure):
     ]
 
 
+class OptTensor(Structure):
+    _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("p16", c_void_p), ("step", c_void_p),
+                ("n", c_long), ("group", c_int), ("flags", c_int)]
+
+
+class OptGroup(Structure):
+    _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("weight_decay", ctypes.c_double)]
+
+
+OPT_CLIP, OPT_SKIP = 1, 2  # cdseg_opt_tensor.flags
+
 # name -> (restype, argtypes); every symbol include/cdseg.h declares
 SIGNATURES = {
     "cdseg_abi_version": (c_int, []),
@@ -218,6 +230,12 @@ SIGNATURES = {
                                    c_void_p, c_void_p, c_size_t, c_void_p]),
     "cdseg_seg_loss_bwd": (c_int, [c_void_p, c_int, c_void_p, c_long, c_int, c_long, POINTER(c_int32), c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_int, c_void_p]),
+    "cdseg_opt_chunks": (c_int, [POINTER(c_long), c_int, POINTER(c_int32), POINTER(c_long)]),
+    "cdseg_opt_ws_bytes": (c_size_t, [c_int, c_long]),
+    "cdseg_grad_norm": (c_int, [POINTER(OptTensor), c_int, c_void_p, c_long, c_void_p, c_float, c_void_p, c_void_p, c_size_t,
+                                c_void_p]),
+    "cdseg_adamw_step": (c_int, [POINTER(OptTensor), c_int, POINTER(OptGroup), c_int, c_void_p, c_long, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_size_t, c_void_p]),
     "cdseg_prof_enable": (c_int, [c_int]),
     "cdseg_prof_summary": (c_int, [POINTER(ctypes.c_double), POINTER(c_long)]),
     "cdseg_prof_summary_class": (c_int, [c_int, POINTER(ctypes.c_double), POINTER(c_long)]),

@@ -41,6 +41,15 @@ def register_into(registry=None, force=True):
     return registry
 
 
+def register_optimizers(registry, force=True):
+    """Register ``"FusedAdamW"`` (cdsegnet_amd/optim.py) into a Pointcept-style ``OPTIMIZERS`` registry - the caller passes
+    ``pointcept.utils.optimizer.OPTIMIZERS`` in; ``optimizer = dict(type="FusedAdamW", lr=..., weight_decay=...)`` then goes
+    through the reference's ``build_optimizer`` (``param_dicts`` included) unchanged.  Returns the registry."""
+    from .optim import FusedAdamW
+    registry.register_module(name="FusedAdamW", force=force, module=FusedAdamW)
+    return registry
+
+
 class _PostImport(importlib.abc.MetaPathFinder):
     """Runs `callback` once, right after module `target` has been executed."""
 

@@ -11,8 +11,9 @@ ref: pointcept/models/default.py:424-493 (DefaultSegmentorV2.forward: q_sample, 
 `block_tail_backward` returns d y / d qkv contracted with an upstream gradient (and the gradients of every tensor on
 the way).  Second slice: `block_forward` / `block_backward` - the WHOLE Block (CPE conv -> Linear -> LayerNorm in front
 of the tail) with the gradient of its input and of every parameter (weights, biases, LayerNorm affine, the 27-offset
-conv kernel).  Scope: one Block in eval mode (DropPath = identity); pooling / unpooling, the loss and the
-optimizer are the next steps of SURVEY 8(f4)'s training row; gradient all-reduce: cdsegnet_amd.dist.GradBucketer.
+conv kernel).  Scope: one Block in eval mode (DropPath = identity); the whole step - pooling / unpooling,
+the loss - is cdsegnet_amd/train_graph.py, the optimizer step cdsegnet_amd/optim.py (FusedAdamW); gradient all-reduce:
+cdsegnet_amd.dist.GradBucketer.
 """
 import weakref
 

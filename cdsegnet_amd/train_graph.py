@@ -64,6 +64,7 @@ from ._lib import DuplicateVoxelsError
 from . import ops
 from .ops import det_kw as _det_kw  # (by name: tests swap `ops` for the CPU emulation, which has no such helper)
 from .losses import TRAIN_LOSSES, build_criteria
+from .optim import shadow16 as _shadow16
 
 
 def _c(t):
@@ -188,7 +189,10 @@ class _SubMConv16(torch.autograd.Function):
     build, like the inference path), the weight likewise; forward, data gradient and weight gradient are cdseg_gemm /
     cdseg_conv_wgrad16 on 16-bit operands with fp32 accumulation and fp32 outputs.  The 16-bit x is what the backward keeps.
     dy is cast WITHOUT saturation (torch's cast): a scaled gradient beyond half's range must reach the GradScaler as inf.
-    The 16-bit weight copies are per-call temporaries (cache=False: no cache entry may pin them)."""
+    The 16-bit weight copy is a per-call temporary (cache=False: no cache entry may pin it), unless an optimizer keeps a current
+    copy (optim.shadow16: FusedAdamW(shadow16=...)); then w16 is a view of the optimizer's buffer, saved for the backward like
+    the temporary - every such view shares one version counter, which the optimizer's step moves, so a backward that ran
+    after the step that rewrote its saved copy is an autograd error, not a silent use of the new weights."""
 
     @staticmethod
     def forward(ctx, x, w5, b, nbr, variant, det=False):
@@ -202,7 +206,8 @@ class _SubMConv16(torch.autograd.Function):
             w3 = F.pad(w3, (0, cp - cin))
         with _lib.use(variant):
             x16 = ops.cast(_c(x), t16)
-            w16 = ops.cast(_c(w3).reshape(cout, kvol * cp), t16)
+            w16 = _shadow16(w5, t16) if cp == cin else None  # the optimizer's current 16-bit copy (optim.FusedAdamW), if any
+            w16 = ops.cast(_c(w3).reshape(cout, kvol * cp), t16) if w16 is None else w16.reshape(cout, kvol * cp)
             y = _f32((x.shape[0], cout), x)
             ops.gemm(x16, w16, y, bias=b, nbr=nbr, kvol=kvol, nbr_kmajor=True, cache=False)
         ctx.save_for_backward(x16, w16, nbr)
@@ -238,7 +243,9 @@ class _Linear16(torch.autograd.Function):
         t16 = ops.LP_DTYPES[variant]
         with _lib.use(variant):
             x16 = ops.cast(_c(x), t16)
-            w16 = ops.cast(_c(w), t16)
+            w16 = _shadow16(w, t16)  # the optimizer's current 16-bit copy (optim.FusedAdamW), if any
+            if w16 is None:
+                w16 = ops.cast(_c(w), t16)
             y = _f32((x.shape[0], w.shape[0]), x)
             ops.gemm(x16, w16, y, bias=b, cache=False)
         ctx.save_for_backward(x16, w16)

@@ -709,6 +709,84 @@ int cdseg_seg_loss_bwd(const float* logits, int ldl, const int64_t* labels, long
                        const int32_t* hist_host, const float* coef, const float* g_ce, const float* g_lovasz, float* dlogits,
                        int lddl, void* stream);
 
+/* ------------------------------------------------------------------ fused optimizer step (csrc/optim.hip)
+ * ref: engines/train.py:216-271 (run_step: scaler.unscale_, clip_grad_norm_, scaler.step(optimizer)) on torch.optim.AdamW.
+ * One tensor table describes the parameters; a work list cuts them into chunks of at most CDSEG_OPT_CHUNK elements (a
+ * chunk never spans two tensors), one 256-thread block per chunk, grid-strided beyond 2048 blocks.
+ *   tensor table   host array of `count` entries.  p, m, v: fp32, updated in place; g: fp32, READ ONLY; step: the tensor's
+ *                  step counter, ONE device float; p16: the 16-bit copy of p in THIS BUILD's 16-bit type (NULL = none);
+ *                  group: index into the group array; flags: CDSEG_OPT_CLIP = g counts towards the clipped norm and is
+ *                  clipped, CDSEG_OPT_SKIP = the tensor takes no part in this call (no gradient: nothing of it is read or
+ *                  written, its pointers must still be valid addresses).  Every entry validates and copies the table into
+ *                  the caller's workspace with ONE host-to-device copy on the caller's stream; after it returns the library
+ *                  holds no host pointer.  The copy is hipMemcpyAsync: from PAGEABLE host memory the runtime stages the
+ *                  bytes before the call returns, so the caller may rewrite the table at once (as cdseg_plan_finish's pad
+ *                  table); a caller that passes PINNED memory must keep the table unchanged until the stream has passed
+ *                  the copy.
+ *   groups         host array, passed on BY VALUE (at most CDSEG_OPT_MAX_GROUPS).  Doubles: 1 - beta2 formed from a float
+ *                  beta2 = 0.999 is off by 1.3e-5 relative; the kernel forms every derived constant in fp64 and rounds once.
+ *   chunk list     cdseg_opt_chunks (host only; a function of the sizes alone): chunks_host[2 k] = tensor index,
+ *                  chunks_host[2 k + 1] = start element, tensors and starts ascending; chunks_host NULL = count only.
+ *                  The caller uploads the list once; the entries below take the DEVICE copy (chunks_dev) and check that
+ *                  nchunks is the count of the table's sizes.  A list entry that points outside the table is never followed.
+ * cdseg_grad_norm: one read of the gradients.  inv_scale = fp32(1 / double(grad_scale[0])) (grad_scale: device float, NULL =
+ *   1), as GradScaler.unscale_ forms it.  Per chunk: a lane adds (g inv_scale)^2 over its elements by ascending index in
+ *   fp32, the lanes go through the fixed 64-wide wave tree and the block's waves by ascending wave index in fp64; the block
+ *   stores its partial (0 for a tensor without CDSEG_OPT_CLIP) and its non-finite flag (any inf / nan in the raw g, over ALL
+ *   tensors that take part) with plain stores.  A second, single-block launch adds the partials by ascending chunk index
+ *   (lane t the chunks [t L, (t + 1) L), L = ceil(nchunks / 256), then lane 0 the 256 lane sums by ascending lane), fp64.
+ *   out (3 device floats): out[0] = norm, out[1] = clip_coef = min(1, max_norm / (norm + 1e-6)) in fp32 (torch's
+ *   clip_grad_norm_), out[2] = 1 if a gradient is non-finite else 0.  Equal inputs give equal bits.
+ * cdseg_adamw_step: a first launch advances step[0] += 1 of every tensor that takes part; the main launch, per element
+ *     g' = (g * inv_scale) * clip_coef      (each factor only where its pointer is given; clip_coef only with CDSEG_OPT_CLIP)
+ *     m  = fma(1 - beta1, g', beta1 * m)
+ *     v  = fma((1 - beta2) * g', g', beta2 * v)
+ *     p  = fma(-lr / (1 - beta1^t), m / (sqrt(v) / sqrt(1 - beta2^t) + eps), p * (1 - lr * weight_decay))
+ *     p16 = cast16(p)                       (the rounding of cdseg_cast of this build: saturating in the IEEE-half build)
+ *   every operation rounded once in fp32 (correctly rounded division and square root, no contraction beyond the fma written
+ *   here); t = step[0] after the advance; the constants are formed in fp64 once per block and tensor and rounded to fp32.
+ *   grad_scale, found_inf, clip_coef: device floats (each may be NULL), never read on the host.  With found_inf[0] != 0
+ *   NOTHING is written: p, m, v, p16 and step keep their bits.  found_inf is the CALLER's flag (GradScaler.step produces it
+ *   with a pass of its own over every gradient before it calls the optimizer); out[2] of cdseg_grad_norm is not consulted.  16-byte loads / stores where p, g, m, v and p16 of a tensor
+ *   are 16-byte aligned, a scalar path otherwise (uniform per block); same bits on either path.
+ * Status codes, checked before any launch or copy:
+ *   CDSEG_ERR_ARG          NULL table / groups / chunks_dev / out; count <= 0; an entry with a NULL or not 4-byte aligned
+ *                          p / g / m / v / step, an odd p16, n <= 0, unknown flag bits, a group index outside [0, ngroups);
+ *                          ngroups <= 0; lr, eps, weight_decay < 0 or a beta outside [0, 1); max_norm < 0; nchunks that is not
+ *                          the chunk count of the table; a scale / flag / coefficient pointer not 4-byte aligned; ws not
+ *                          16-byte aligned.
+ *   CDSEG_ERR_UNSUPPORTED  n >= 2^31 (chunk starts are int32); more than CDSEG_OPT_MAX_GROUPS groups.
+ *   CDSEG_ERR_WORKSPACE    ws NULL or ws_bytes below cdseg_opt_ws_bytes(count, nchunks). */
+#define CDSEG_OPT_CHUNK 8192
+#define CDSEG_OPT_MAX_GROUPS 16
+#define CDSEG_OPT_CLIP 1
+#define CDSEG_OPT_SKIP 2
+typedef struct cdseg_opt_tensor {
+  float* p;
+  const float* g;
+  float* m;
+  float* v;
+  void* p16;
+  float* step;
+  long n;
+  int group;
+  int flags;
+} cdseg_opt_tensor;
+typedef struct cdseg_opt_group {
+  double lr;
+  double beta1;
+  double beta2;
+  double eps;
+  double weight_decay;
+} cdseg_opt_group;
+int cdseg_opt_chunks(const long* n_host, int count, int32_t* chunks_host, long* nchunks);
+size_t cdseg_opt_ws_bytes(int count, long nchunks);
+int cdseg_grad_norm(const cdseg_opt_tensor* tensors_host, int count, const int32_t* chunks_dev, long nchunks,
+                    const float* grad_scale, float max_norm, float* out, void* ws, size_t ws_bytes, void* stream);
+int cdseg_adamw_step(const cdseg_opt_tensor* tensors_host, int count, const cdseg_opt_group* groups_host, int ngroups,
+                     const int32_t* chunks_dev, long nchunks, const float* grad_scale, const float* found_inf,
+                     const float* clip_coef, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

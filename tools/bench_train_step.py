@@ -3,9 +3,11 @@
 with a 16-bit attention core, or under AMP (16-bit attention core, Linears and sparse convs; train_precision), on the HIP kernels (cdsegnet_amd/train_graph.py).  Not a BASELINE metric - the reference publishes no training throughput -
 a first number for the training row of SURVEY 8(f4).
 usage: python tools/bench_train_step.py [scenes=1] [points=120000] [steps=4] [dataset=scannet|scannet200|nuscenes]
-       [train_precision=fp32|fp16-attn|bf16-attn|fp16-amp|bf16-amp] [det] [fused]
+       [train_precision=fp32|fp16-attn|bf16-attn|fp16-amp|bf16-amp] [det] [fused] [fusedopt] [shadow]
 A trailing `det` sets train_deterministic = True (fixed-order gradient reductions: bit-reproducible steps), a trailing `fused`
-sets train_loss = "fused" (cross entropy + Lovasz on the HIP loss kernels instead of the torch criteria)."""
+sets train_loss = "fused" (cross entropy + Lovasz on the HIP loss kernels instead of the torch criteria), a trailing `fusedopt`
+takes cdsegnet_amd.optim.FusedAdamW in torch.optim.AdamW's place, and `shadow` (with `fusedopt` under an AMP precision) lets it
+keep the 16-bit weight copies the forward multiplies with."""
 import os, sys, time
 import numpy as np
 import torch
@@ -23,6 +25,10 @@ dataset = sys.argv[4] if len(sys.argv) > 4 else "scannet"
 train_precision = sys.argv[5] if len(sys.argv) > 5 else "fp32"
 deterministic = "det" in sys.argv[6:]
 fused = "fused" in sys.argv[6:]
+fusedopt = "fusedopt" in sys.argv[6:]
+shadow = "shadow" in sys.argv[6:]
+if shadow and not (fusedopt and train_precision.endswith("-amp")):
+    sys.exit("`shadow` needs `fusedopt` and an AMP train_precision (the fp32 step multiplies with the fp32 weights)")
 dev = torch.device("cuda")
 cfg = configs.cdsegnet_config(dataset)
 cfg["criteria"] = [dict(type="MSELoss", loss_weight=1.0, ignore_index=-1, batch_sample_point=-1),
@@ -40,8 +46,13 @@ inp = {k: torch.as_tensor(sc[k]).to(dev) for k in ("coord", "grid_coord", "feat"
 inp["segment"] = (torch.as_tensor(np.asarray(sc["segment"]).astype(np.int64)) % cfg["num_classes"]).to(dev)
 n = inp["feat"].shape[0]
 named = dict(model.named_parameters())
-opt = torch.optim.AdamW([dict(params=[p for k, p in named.items() if "block" not in k], lr=0.002),
-                         dict(params=[p for k, p in named.items() if "block" in k], lr=0.0002)], lr=0.002, weight_decay=0.05)
+groups = [dict(params=[p for k, p in named.items() if "block" not in k], lr=0.002),
+          dict(params=[p for k, p in named.items() if "block" in k], lr=0.0002)]
+if fusedopt:
+    from cdsegnet_amd.optim import FusedAdamW
+    opt = FusedAdamW(groups, lr=0.002, weight_decay=0.05, shadow16={"fp16-amp": "f16", "bf16-amp": "bf16"}[train_precision] if shadow else None)
+else:
+    opt = torch.optim.AdamW(groups, lr=0.002, weight_decay=0.05)
 times, losses = [], []
 for it in range(steps + 1):
     torch.cuda.synchronize()
@@ -60,6 +71,6 @@ for it in range(steps + 1):
     if it:
         times.append((t1 - t0, t2 - t1, t3 - t2))
 t = np.median(np.array(times), axis=0) * 1e3
-print(f"training step, {dataset}, full width, {train_precision}{', deterministic' if deterministic else ''}{', fused loss' if fused else ''}, {scenes} scene(s), {n} points: forward {t[0]:.1f} ms, backward {t[1]:.1f} ms, "
+print(f"training step, {dataset}, full width, {train_precision}{', deterministic' if deterministic else ''}{', fused loss' if fused else ''}{', FusedAdamW' if fusedopt else ''}{' + 16-bit weight copies' if shadow else ''}, {scenes} scene(s), {n} points: forward {t[0]:.1f} ms, backward {t[1]:.1f} ms, "
       f"AdamW {t[2]:.1f} ms = {t.sum():.1f} ms/step = {n / t.sum() * 1e3 / 1e6:.2f} M points/s; peak memory "
       f"{torch.cuda.max_memory_allocated() / 2**30:.1f} GiB; loss over the steps {[round(v, 4) for v in losses]}")
