@@ -533,6 +533,7 @@ __global__ __launch_bounds__(B16_WAVES * 64, 4) void attn_bwd16_kv_kernel(AttnBw
 // ---- LayerNorm backward: dx = (1/sigma) (dyg - mean(dyg) - xhat mean(dyg xhat)), dyg = dy * gamma.  One wave per row, 16 rows
 // per wave; d gamma / d beta are summed over the block's 64 rows in registers + LDS and leave with ONE atomic per column
 // and block (the first version issued one atomic per element onto C addresses: 82 of a 450 ms training step).
+// Rows wider than LNB_MAXC (no layer of the model has them) get the same block sums in passes of LNB_MAXC columns.
 constexpr int LNB_ROWS = 16, LNB_MAXC = 512;
 
 // DET (deterministic form, c <= LNB_MAXC): the block's (dgamma, dbeta) partial rows go to ws[block][2][c] with plain stores;
@@ -542,9 +543,11 @@ __device__ __forceinline__ void layernorm_bwd_body(const float* __restrict__ x, 
                                                    const float* __restrict__ dy, int lddy, float* dx, int lddx, int accumulate,
                                                    float* dgamma, float* dbeta, long m, int c, float* ws) {
   __shared__ float red[2][4][LNB_MAXC];
+  __shared__ float rstat[4][LNB_ROWS][2];  // wide rows: (mean, 1 / sigma) of the wave's rows, for the column passes below
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long row0 = ((long)blockIdx.x * 4 + wave) * LNB_ROWS;
   const bool sums = DET || ((dgamma || dbeta) && c <= LNB_MAXC);
+  const bool wide = !DET && (dgamma || dbeta) && c > LNB_MAXC;
   float pg[LNB_MAXC / 64], pb[LNB_MAXC / 64];
 #pragma unroll
   for (int t = 0; t < LNB_MAXC / 64; ++t) pg[t] = pb[t] = 0.f;
@@ -587,10 +590,43 @@ __device__ __forceinline__ void layernorm_bwd_body(const float* __restrict__ x, 
         const float v = rstd * (dg - a - xh * b);
         float* o = dx + row * lddx + j;
         *o = accumulate ? *o + v : v;
-        if (dgamma) atomicAdd(dgamma + j, gr[j] * xh);  // (rows wider than 512: per-element atomics)
-        if (dbeta) atomicAdd(dbeta + j, gr[j]);
       }
+      if (wide && lane == 0) { rstat[wave][r][0] = mean; rstat[wave][r][1] = rstd; }
     }
+  }
+  if (wide) {  // (block-uniform) rows wider than LNB_MAXC: the block sums of the narrow form, LNB_MAXC columns at a time.
+    // (One atomic per row and element, as this branch used to issue, is a serial fp32 chain of m adds per column: at
+    // m = 777 its error was nine times that of the narrow form - tests/test_gpu_train_fp32.py, layernorm (777, 640).)
+    __syncthreads();
+    const long left = m - row0;
+    const int nrows = left < 0 ? 0 : left < LNB_ROWS ? (int)left : LNB_ROWS;
+    for (int cb = 0; cb < c; cb += LNB_MAXC) {
+#pragma unroll
+      for (int t = 0; t < LNB_MAXC / 64; ++t) pg[t] = pb[t] = 0.f;
+      for (int r = 0; r < nrows; ++r) {
+        const float* xr = x + (row0 + r) * ldx;
+        const float* gr = dy + (row0 + r) * lddy;
+        const float mean = rstat[wave][r][0], rstd = rstat[wave][r][1];
+#pragma unroll
+        for (int t = 0; t < LNB_MAXC / 64; ++t) {
+          const int j = cb + lane + 64 * t;
+          if (j < c) {
+            const float g = gr[j];
+            pg[t] = fmaf(g, (xr[j] - mean) * rstd, pg[t]);
+            pb[t] += g;
+          }
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < LNB_MAXC / 64; ++t) { red[0][wave][lane + 64 * t] = pg[t]; red[1][wave][lane + 64 * t] = pb[t]; }
+      __syncthreads();
+      for (int j = threadIdx.x; j < LNB_MAXC && cb + j < c; j += 256) {
+        if (dgamma) atomicAdd(dgamma + cb + j, (red[0][0][j] + red[0][1][j]) + (red[0][2][j] + red[0][3][j]));
+        if (dbeta) atomicAdd(dbeta + cb + j, (red[1][0][j] + red[1][1][j]) + (red[1][2][j] + red[1][3][j]));
+      }
+      __syncthreads();  // (red is refilled by the next pass)
+    }
+    return;
   }
   if (!sums) return;  // (block-uniform)
 #pragma unroll
@@ -1010,9 +1046,20 @@ extern "C" int cdseg_attention_bwd(const void* q, const void* k, const void* v, 
   return CDSEG_OK;
 }
 
+// The fp32 entry points check what they are given before any launch, like the 16-bit and the deterministic forms: the
+// required pointers are there, and every fp32 pointer (optional ones included; NULL passes) is 4-byte aligned.
+template <typename... P>
+static bool f32_aligned(const P*... ptr) { return ((((uintptr_t)ptr) | ...) & 3) == 0; }
+
+static bool wgrad_args_ok(const float* x, const int32_t* xidx, const float* dy, const float* dw, const float* db) {
+  return x && dy && dw && f32_aligned(x, xidx, dy, dw, db);
+}
+
 extern "C" int cdseg_layernorm_bwd(const float* x, int ldx, const float* gamma, float eps, const float* dy, int lddy, float* dx,
                                    int lddx, int accumulate, float* dgamma, float* dbeta, long m, int c, void* stream) {
   if (m <= 0) return CDSEG_OK;
+  if (c <= 0 || !x || !gamma || !dy || !dx) return CDSEG_ERR_ARG;
+  if (!f32_aligned(x, gamma, dy, dx, dgamma, dbeta)) return CDSEG_ERR_ARG;
   hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((unsigned)cdiv(m, 4 * LNB_ROWS)), dim3(256), 0, (hipStream_t)stream, x, ldx, gamma, eps, dy,
                      lddy, dx, lddx, accumulate, dgamma, dbeta, m, c);
   CDSEG_CHECK_LAUNCH();
@@ -1021,6 +1068,7 @@ extern "C" int cdseg_layernorm_bwd(const float* x, int ldx, const float* gamma, 
 
 extern "C" int cdseg_gelu_bwd(const float* u, const float* dy, float* dx, long n, void* stream) {
   if (n <= 0) return CDSEG_OK;
+  if (!u || !dy || !dx || !f32_aligned(u, dy, dx)) return CDSEG_ERR_ARG;
   hipLaunchKernelGGL(gelu_bwd_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, u, dy, dx, n);
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
@@ -1056,6 +1104,7 @@ static int launch_wgrad(WgradP p, int noff, hipStream_t stream, float* ws = null
 extern "C" int cdseg_linear_wgrad(const float* x, int ldx, const int32_t* xidx, const float* dy, int lddy, long m, int k, int n,
                                   float* dw, int lddw, float* db, void* stream) {
   if (m <= 0 || n <= 0 || k <= 0) return CDSEG_OK;
+  if (!wgrad_args_ok(x, xidx, dy, dw, db)) return CDSEG_ERR_ARG;
   if ((n & 15) || (k & 15)) return CDSEG_ERR_UNSUPPORTED;
   WgradP p;
   p.dy = dy; p.x = x; p.xidx = xidx; p.dw = dw; p.db = db; p.M = m; p.N = n; p.K = k; p.lddy = lddy; p.ldx = ldx; p.lddw = lddw;
@@ -1065,7 +1114,8 @@ extern "C" int cdseg_linear_wgrad(const float* x, int ldx, const int32_t* xidx, 
 
 extern "C" int cdseg_conv_wgrad(const float* x, int ldx, const int32_t* nbr_kmajor, int kvol, const float* dy, int lddy, long m,
                                 int cin, int cout, float* dw, float* db, void* stream) {
-  if (m <= 0 || kvol <= 0) return CDSEG_OK;
+  if (m <= 0 || kvol <= 0 || cin <= 0 || cout <= 0) return CDSEG_OK;
+  if (!nbr_kmajor || !wgrad_args_ok(x, nbr_kmajor, dy, dw, db)) return CDSEG_ERR_ARG;
   if ((cin & 15) || (cout & 15)) return CDSEG_ERR_UNSUPPORTED;
   WgradP p;
   p.dy = dy; p.x = x; p.xidx = nbr_kmajor; p.dw = dw; p.db = db; p.M = m; p.N = cout; p.K = cin; p.lddy = lddy; p.ldx = ldx;

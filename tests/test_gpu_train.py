@@ -164,7 +164,7 @@ def test_linear_wgrad_kernel_plain_and_gathered():
     assert float(wide[:, :K].abs().max()) == 0.0 and float(wide[:, 2 * K:].abs().max()) == 0.0
 
 
-@pytest.mark.parametrize("npts,H", [(900, 2), (2300, 4)])
+@pytest.mark.parametrize("npts,H", [(900, 2), (2300, 4), (700, 16), (700, 32)])  # (700: C = 256 / 512, one padded patch)
 def test_whole_block_backward_vs_oracle(npts, H):
     """CPE conv + Linear + LayerNorm + attention + MLP of one Block: gradient of the input and of every parameter against
     torch autograd on the oracle restatement (real kernel map of a synthetic scene, real padded patch plan)."""
@@ -186,13 +186,18 @@ def test_whole_block_backward_vs_oracle(npts, H):
     order, inverse = perm[pad], unpad[inv]
     pre = "blk"
     sd = {}
+    # Matrices keep the gain they have at C = 64 (factor 1, the same values as before, up to there).  With 0.3 N(0, 1) at
+    # C = 256 / 512 the scores reach |s| ~ 50 and |y| ~ 200 - 400, and the oracle, which is itself fp32, then misses its own
+    # fp64 restatement by 1.2e-3 / 3.4e-3 in the forward (measured on the CPU): the absolute 1e-3 below would test the oracle.
+    # With the factor its own error is 1e-4 at every width, as at (2300, 4).
+    wide = min(1.0, (64 / C) ** 0.5)
     for k, shape in ((".cpe.0.weight", (C, 3, 3, 3, C)), (".cpe.0.bias", (C,)), (".cpe.1.weight", (C, C)), (".cpe.1.bias", (C,)),
                      (".cpe.2.weight", (C,)), (".cpe.2.bias", (C,)),
                      (".norm1.0.weight", (C,)), (".norm1.0.bias", (C,)), (".attn.qkv.weight", (3 * C, C)), (".attn.qkv.bias", (3 * C,)),
                      (".attn.proj.weight", (C, C)), (".attn.proj.bias", (C,)), (".norm2.0.weight", (C,)), (".norm2.0.bias", (C,)),
                      (".mlp.0.fc1.weight", (4 * C, C)), (".mlp.0.fc1.bias", (4 * C,)), (".mlp.0.fc2.weight", (C, 4 * C)),
                      (".mlp.0.fc2.bias", (C,))):
-        scale = {1: 0.1, 2: 0.3, 5: 0.3 / 27 ** 0.5}[len(shape)]
+        scale = {1: 0.1, 2: 0.3 * wide, 5: 0.3 * wide / 27 ** 0.5}[len(shape)]
         sd[pre + k] = (rng.standard_normal(shape) * scale + (1.0 if k.endswith(".weight") and len(shape) == 1 else 0.0)).astype(np.float32)
     x_in = rng.standard_normal((n, C)).astype(np.float32)
     dy = rng.standard_normal((n, C)).astype(np.float32)
@@ -219,14 +224,15 @@ def test_whole_block_backward_vs_oracle(npts, H):
              "B.norm2.g": ".norm2.0.weight", "B.norm2.b": ".norm2.0.bias", "B.fc1.w": ".mlp.0.fc1.weight", "B.fc1.b": ".mlp.0.fc1.bias",
              "B.fc2.w": ".mlp.0.fc2.weight", "B.fc2.b": ".mlp.0.fc2.bias"}
     assert set(grads) == set(names)
-    worst = 0.0
+    worst, worst_name = 0.0, None
     for mine, ref in names.items():
         r = rg[pre + ref].reshape(grads[mine].shape)
         e = float((grads[mine].cpu() - r).abs().max()) / max(1.0, float(r.abs().max()))
-        worst = max(worst, e)
+        if e > worst:
+            worst, worst_name = e, mine
         assert e < 1e-3, (mine, e)
-    print(f"[measure] whole Block backward vs oracle autograd n={n} H={H}: forward {ey:.3e}, d_x_in rel {ex:.3e}, "
-          f"worst parameter gradient rel {worst:.3e} (18 tensors incl. the 27-offset conv kernel)")
+    print(f"[measure] whole Block backward vs oracle autograd n={n} H={H} C={C}: forward {ey:.3e}, d_x_in rel {ex:.3e}, "
+          f"worst parameter gradient rel {worst:.3e} at {worst_name} (18 tensors incl. the 27-offset conv kernel)")
     assert ey < 1e-3 and ex < 1e-3
 
 
