@@ -159,6 +159,18 @@ SIGNATURES = {
     "cdseg_fragment_select": (c_int, [c_void_p, c_void_p, c_long, c_int, c_void_p, c_void_p]),
     "cdseg_softmax_vote": (c_int, [c_void_p, c_int, c_void_p, c_long, c_int, c_void_p, c_int, c_void_p]),
     "cdseg_argmax_rows": (c_int, [c_void_p, c_int, c_long, c_int, c_void_p, c_void_p]),
+    "cdseg_tt_bbox": (c_int, [c_void_p, c_int, c_long, c_void_p, c_void_p]),
+    "cdseg_tt_affine": (c_int, [c_void_p, c_int, c_long, c_int, POINTER(ctypes.c_double), c_void_p, POINTER(ctypes.c_double), c_int,
+                                ctypes.c_double, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "cdseg_tt_jitter": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_double, ctypes.c_double, c_long, c_void_p]),
+    "cdseg_tt_blur3": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "cdseg_tt_elastic": (c_int, [c_void_p, c_long, c_void_p, POINTER(c_int), POINTER(ctypes.c_double), POINTER(ctypes.c_double),
+                                 POINTER(ctypes.c_double), ctypes.c_double, c_void_p]),
+    "cdseg_tt_color": (c_int, [c_void_p, c_long, c_void_p, ctypes.c_double, c_int, POINTER(ctypes.c_double), c_void_p, c_int,
+                               ctypes.c_double, c_void_p]),
+    "cdseg_tt_voxel_pick": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
+    "cdseg_tt_dist_key": (c_int, [c_void_p, c_long, c_long, c_void_p, c_void_p]),
+    "cdseg_rand_int": (c_int, [c_void_p, c_long, c_uint64, c_uint64, c_void_p, ctypes.c_uint32, c_void_p]),
     "cdseg_knn": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_long, c_int, c_int, POINTER(c_float), c_float,
                           c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "cdseg_knn1_ws_bytes": (c_size_t, [c_long]),

@@ -1365,3 +1365,115 @@ def seg_loss_bwd(logits, saved, g_ce, g_lovasz):
                                          saved["hist_host"], _ptr(saved["coef"]), _ptr(gs[0]), _ptr(gs[1]), _ptr(dlogits),
                                          dlogits.stride(0), _stream()), "seg_loss_bwd")
     return dlogits
+
+
+# ------------------------------------------------------------------ train-time pipeline ops (csrc/traintime.hip)
+TT_CENTER_NONE, TT_CENTER_HOST, TT_CENTER_BBOX, TT_CENTER_SHIFT_Z, TT_CENTER_SHIFT_XY = 0, 1, 2, 3, 4  # include/cdseg.h
+
+
+def _d3(v, n=3):
+    return None if v is None else (ctypes.c_double * n)(*[float(x) for x in v])
+
+
+def tt_bbox(xyz):
+    """(6,) float64 on the device: [min x y z, max x y z] of an (n,3) float32 / float64 array (n >= 1)."""
+    _need_gpu(xyz)
+    assert xyz.dtype in (torch.float32, torch.float64) and xyz.dim() == 2 and xyz.shape[1] == 3 and xyz.shape[0] > 0
+    xyz = xyz.contiguous()
+    ws = torch.empty(12, dtype=torch.float64, device=xyz.device)
+    check(_lib.load().cdseg_tt_bbox(_ptr(xyz), 1 if xyz.dtype == torch.float64 else 0, xyz.shape[0], _ptr(ws), _stream()),
+          "tt_bbox")
+    return ws[6:]
+
+
+def tt_affine(xyz, center=TT_CENTER_NONE, center3=None, bbox=None, rot=None, add_back=False, scale=None, flipx=False,
+              flipy=False, out_dtype=torch.float64):
+    """((xyz - c) R^T [+ c]) [* scale], flips: one pass in float64 without fused multiply-adds (include/cdseg.h).
+    xyz (n,3) float32 / float64; rot: 3x3 nested floats or None; -> a new (n,3) tensor of out_dtype."""
+    _need_gpu(xyz, bbox)
+    assert xyz.dtype in (torch.float32, torch.float64) and out_dtype in (torch.float32, torch.float64)
+    xyz = xyz.contiguous()
+    n = xyz.shape[0]
+    out = torch.empty((n, 3), dtype=out_dtype, device=xyz.device)
+    r = None if rot is None else (ctypes.c_double * 9)(*[float(v) for row in rot for v in row])
+    check(_lib.load().cdseg_tt_affine(_ptr(xyz), 1 if xyz.dtype == torch.float64 else 0, n, int(center), _d3(center3), _ptr(bbox),
+                                      r, 1 if add_back else 0, float(scale if scale is not None else 1.0),
+                                      1 if scale is not None else 0, 1 if flipx else 0, 1 if flipy else 0, _ptr(out),
+                                      1 if out_dtype == torch.float64 else 0, _stream()), "tt_affine")
+    return out
+
+
+def tt_jitter(coord, z, sigma, clip):
+    """coord (n,3) float64 += clip(sigma * z), in place; z (n,3) float32 or float64."""
+    _need_gpu(coord, z)
+    assert coord.dtype == torch.float64 and coord.is_contiguous() and z.dtype in (torch.float32, torch.float64)
+    z = z.contiguous()
+    assert z.numel() == coord.numel()
+    check(_lib.load().cdseg_tt_jitter(_ptr(coord), _ptr(z), 1 if z.dtype == torch.float64 else 0, float(sigma), float(clip),
+                                      coord.shape[0], _stream()), "tt_jitter")
+    return coord
+
+
+def tt_blur(noise):
+    """The reference's smoothing of an elastic noise grid (d0,d1,d2,3) float32: box filter along x, y, z, twice."""
+    _need_gpu(noise)
+    assert noise.dtype == torch.float32 and noise.dim() == 4 and noise.shape[3] == 3
+    src, bufs = noise.contiguous(), (torch.empty_like(noise), torch.empty_like(noise))  # the input grid is left as it is
+    d0, d1, d2 = (int(v) for v in noise.shape[:3])
+    lib = _lib.load()
+    for k in range(6):
+        dst = bufs[k & 1]
+        check(lib.cdseg_tt_blur3(_ptr(src), d0, d1, d2, k % 3, _ptr(dst), _stream()), "tt_blur3")
+        src = dst
+    return src
+
+
+def tt_elastic(coord, noise, start, step, stop, magnitude):
+    """coord (n,3) float64 += trilinear(noise)(coord) * magnitude, in place; noise (d0,d1,d2,3) float32 (blurred)."""
+    _need_gpu(coord, noise)
+    assert coord.dtype == torch.float64 and coord.is_contiguous() and noise.dtype == torch.float32 and noise.is_contiguous()
+    dims = (ctypes.c_int * 3)(*[int(v) for v in noise.shape[:3]])
+    check(_lib.load().cdseg_tt_elastic(_ptr(coord), coord.shape[0], _ptr(noise), dims, _d3(start), _d3(step), _d3(stop),
+                                       float(magnitude), _stream()), "tt_elastic")
+    return coord
+
+
+def tt_color(color, bbox=None, blend=None, tr=None, noise=None, noise_mul=0.0):
+    """The colour chain on (n,3) float32 in place: auto contrast (bbox, blend), translation (tr), jitter (noise)."""
+    _need_gpu(color, bbox, noise)
+    assert color.dtype == torch.float32 and color.is_contiguous()
+    if noise is not None:
+        assert noise.dtype in (torch.float32, torch.float64) and noise.numel() == color.numel()
+        noise = noise.contiguous()
+    check(_lib.load().cdseg_tt_color(_ptr(color), color.shape[0], _ptr(bbox), float(blend if blend is not None else 0.0),
+                                     1 if blend is not None else 0, _d3(tr), _ptr(noise),
+                                     1 if (noise is not None and noise.dtype == torch.float64) else 0, float(noise_mul),
+                                     _stream()), "tt_color")
+    return color
+
+
+def tt_voxel_pick(idx_sort, seg_start, m, r):
+    """Raw row of member r[v] % count[v] of every voxel v; r (m,) int64 >= 0."""
+    _need_gpu(idx_sort, seg_start, r)
+    assert r.dtype == torch.int64 and r.numel() >= int(m)
+    out = torch.empty(int(m), dtype=torch.int32, device=idx_sort.device)
+    check(_lib.load().cdseg_tt_voxel_pick(_ptr(idx_sort), _ptr(seg_start), int(m), _ptr(r.contiguous()), _ptr(out), _stream()),
+          "tt_voxel_pick")
+    return out
+
+
+def tt_dist_key(coord, center):
+    """Sort keys (n,) int64 of the float64 squared distances of coord (n,3) float64 to its row `center`."""
+    _need_gpu(coord)
+    assert coord.dtype == torch.float64 and coord.is_contiguous()
+    key = torch.empty(coord.shape[0], dtype=torch.int64, device=coord.device)
+    check(_lib.load().cdseg_tt_dist_key(_ptr(coord), coord.shape[0], int(center), _ptr(key), _stream()), "tt_dist_key")
+    return key
+
+
+def rand_int(n, seed, offset, device, bound=0, bound_dev=None):
+    """n Philox integers (int64): raw 32-bit words, or reduced modulo `bound` / the device int32 `bound_dev`."""
+    out = torch.empty(int(n), dtype=torch.int64, device=device)
+    check(_lib.load().cdseg_rand_int(_ptr(out), int(n), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), _ptr(bound_dev),
+                                     int(bound), _stream()), "rand_int")
+    return out

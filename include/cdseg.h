@@ -331,6 +331,50 @@ int cdseg_softmax_vote(const float* logits, int ldl, const int32_t* idx, long m,
 /* out[i] = first arg-max of row i.  ref: engines/test.py:278 */
 int cdseg_argmax_rows(const float* x, int ldx, long n, int c, int32_t* out, void* stream);
 
+/* ------------------------------------------------------------------ train-time pipeline
+ * ref: configs/{scannet,scannet200,nuscenes}/CDSegNet.py data.train / data.val transform lists, datasets/transform.py.
+ * Coordinates and normals are FLOAT64 (n,3) between the first transform and GridSample; every float64 operation is one
+ * correctly rounded add / multiply / divide in the documented order, never a fused multiply-add, so the results are
+ * bit-equal to a numpy restatement of the same operations.  `*_host` arguments are read on the host at the call. */
+#define CDSEG_TT_CENTER_NONE 0     /* no translation */
+#define CDSEG_TT_CENTER_HOST 1     /* center3_host */
+#define CDSEG_TT_CENTER_BBOX 2     /* ((min + max) / 2) of all three axes of bbox6_dev: RandomRotate(center=None) :245-247 */
+#define CDSEG_TT_CENTER_SHIFT_Z 3  /* CenterShift(apply_z=True) :148-151: [(xmin+xmax)/2, (ymin+ymax)/2, zmin] */
+#define CDSEG_TT_CENTER_SHIFT_XY 4 /* CenterShift(apply_z=False): [(xmin+xmax)/2, (ymin+ymax)/2, 0] */
+/* bounding box of an (n,3) float32 / float64 array; ws12: 96 bytes of device memory, doubles ws12[6..11] receive
+ * [min x y z, max x y z] (ws12 + 6 is the `bbox6_dev` of the calls below) */
+int cdseg_tt_bbox(const void* xyz, int is_f64, long n, void* ws12, void* stream);
+/* t = in - c ; rot9_host (row-major R) given: t_j = (t0 R[j][0] + t1 R[j][1]) + t2 R[j][2] ; add_back: t += c ;
+ * apply_scale: t *= scale ; flipx / flipy: negate.  CenterShift :142-155, RandomRotate :230-255, RandomScale :303-309,
+ * RandomFlip :317-328; normals use center = NONE.  in / out float32 or float64 (out may alias in when the types agree). */
+int cdseg_tt_affine(const void* in, int in_f64, long n, int center, const double* center3_host, const double* bbox6_dev,
+                    const double* rot9_host, int add_back, double scale, int apply_scale, int flipx, int flipy, void* out,
+                    int out_f64, void* stream);
+/* RandomJitter :338-346: coord[i] += min(max(sigma z[i], -clip), clip); z (n,3) float32 or float64 normals */
+int cdseg_tt_jitter(double* coord, const void* z, int z_f64, double sigma, double clip, long n, void* stream);
+/* ElasticDistortion :742-784.  blur3: one zero-padded 3-tap box pass along `axis` of a (d0,d1,d2,3) float32 grid
+ * (float64 accumulation left to right with the float32 weight 1/3, rounded to float32); in != out.
+ * elastic: coord += trilinear(noise, coord) * magnitude on the axes ax_a(k) = k < d_a - 1 ? k step_a + start_a : stop_a
+ * (numpy.linspace), corner weights ((w_x w_y) w_z) summed in itertools.product order, fill value 0 outside the axes. */
+int cdseg_tt_blur3(const float* in, int d0, int d1, int d2, int axis, float* out, void* stream);
+int cdseg_tt_elastic(double* coord, long n, const float* noise, const int* dims3_host, const double* start3_host,
+                     const double* step3_host, const double* stop3_host, double magnitude, void* stream);
+/* colour chain on (n,3) float32 in place, each stage optional (:385-431): contrast - float32 blend with
+ * (c - lo) * (255 / (hi - lo)), lo / hi from bbox6_dev; tr3_host - c = f32(clip(tr + c, 0, 255)) in float64;
+ * noise (n,3) float32 / float64 - c = f32(clip(noise * noise_mul + c, 0, 255)) in float64.  contrast blends
+ * f32(1 - blend) * c + f32(blend) * contrast in float32 */
+int cdseg_tt_color(float* color, long n, const double* bbox6_dev, double blend, int contrast, const double* tr3_host,
+                   const void* noise, int noise_f64, double noise_mul, void* stream);
+/* GridSample(mode="train") :834-838: out[v] = idx_sort[seg_start[v] + r[v] % count_v], r (m) int64 >= 0 */
+int cdseg_tt_voxel_pick(const int32_t* idx_sort, const int32_t* seg_start, long m, const int64_t* r, int32_t* out,
+                        void* stream);
+/* SphereCrop :1012: key[i] = bit image of the float64 (dx dx + dy dy) + dz dz to row `center` (sorts like the distance) */
+int cdseg_tt_dist_key(const double* coord, long n, long center, int64_t* key, void* stream);
+/* integer companion of cdseg_randn, the same Philox4x32-10 stream: out[4 t + i] = word i of counter (t, offset) under
+ * key seed, reduced modulo *bound_dev (device int32, if given) or bound (0: the raw 32-bit word) */
+int cdseg_rand_int(int64_t* out, long n, uint64_t seed, uint64_t offset, const int32_t* bound_dev, uint32_t bound,
+                   void* stream);
+
 /* ------------------------------------------------------------------ evaluator
  * ref: engines/hooks/evaluator.py:132-140 (pointops.knn_query(1, ...) label transfer), utils/misc.py:52-65 (IoU counts).
  * Exact 1-NN of every query among the reference points of the same batch element (lowest index on ties, like the
