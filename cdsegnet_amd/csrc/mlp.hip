@@ -8,6 +8,7 @@
 #include <cstdlib>
 
 #include <atomic>
+#include <type_traits>
 
 #include "common.h"
 
@@ -561,6 +562,296 @@ __global__ __launch_bounds__(4 * BM) void cpe_head_fused_kernel(HeadP p) {
   }
 }
 
+// The 128-row head as a persistent, pipelined kernel (large n): min(tiles, 2 x 256) workgroups of 8 waves walk the row
+// tiles with a grid stride.  Per workgroup, once: Wl and the three Wqkv tiles -> LDS in the swizzled layout of the tile
+// kernel, and bl / the LN vectors / colbias / bqkv -> LDS.  Per tile the y and x rows of the NEXT tile are requested into
+// registers before the first product, so a workgroup always has a tile of reads (48 KB at C = 64) in flight behind the
+// current tile's products and stores.  Products, row statistics and rounding points are those of cpe_head_fused_kernel
+// (bit for bit: tests/test_gpu_cpe_head_stream.py); only where a value waits between two of them differs:
+//   - y sits in the first BM*C*2 bytes of the C tile's region R (dead once the first product is in registers),
+//   - h is written IN PLACE over its own fp32 row of R (a row is read and rewritten by the same four lanes; row stride
+//     CLD*4 bytes = 4 banks per row, so the A-operand reads need no swizzle),
+//   - the q / k / v products are issued back to back into registers, then rounded (+ bias) in the MFMA layout and staged
+//     as 16-bit rows through R: q and k together, then v.
+// Occupancy: 2 workgroups (16 waves) per CU; 108 / 61 VGPRs (C = 64 / 32), no scratch.  LDS map (bytes, C = 64 / 32):
+//   Ws  4*C*C*2        32768 /  8192   Wl, Wq, Wk, Wv
+//   R   128*(C+4)*4    34816 / 18432   y tile | fp32 C tile with h in place | 16-bit q,k rows (stride 4C+8) | v rows (2C+8)
+//   P   9*C*4           2304 /  1152   bl, lnp_g, lnp_b, ln1_g, ln1_b, colbias, bqkv[3C]
+//                      69888 / 27776
+template <int C>
+__global__ __launch_bounds__(512, 4) void cpe_head_stream_kernel(HeadP p) {
+  constexpr int BM = 128, NT = 512;
+  constexpr int NCA = C / 8, TN = C / 32, CLD = C + 4, MAXG = C / 16;
+  constexpr int W_BYTES = C * C * 2, R_BYTES = BM * CLD * 4;
+  constexpr int YPT = BM * NCA / NT;  // 16-byte pieces of a y tile per thread
+  static_assert(BM * (2 * C * 2 + 8) <= R_BYTES, "the staged q + k rows must fit the C tile's region");
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // 4 * W_BYTES + R_BYTES + 9 * C * 4
+  char* Ws = smem;
+  char* R = smem + 4 * W_BYTES;
+  float* Cs = reinterpret_cast<float*>(R);
+  float* P = reinterpret_cast<float*>(smem + 4 * W_BYTES + R_BYTES);
+
+  const int tid0 = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  int tid = tid0;
+
+  // ---- once per workgroup: weights and parameter vectors
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const bf16_t* w = j == 0 ? p.wl : p.wqkv + (long)(j - 1) * C * C;
+    for (int id = tid; id < C * NCA; id += NT) {
+      const int row = id / NCA, ch = id % NCA;
+      *reinterpret_cast<uint4*>(Ws + j * W_BYTES + mlp_lds_off<NCA>(row, ch)) =
+          *reinterpret_cast<const uint4*>(w + (long)row * C + ch * 8);
+    }
+  }
+  for (int c = tid; c < C; c += NT) {
+    P[c] = p.bl[c]; P[C + c] = p.lnp_g[c]; P[2 * C + c] = p.lnp_b[c]; P[3 * C + c] = p.ln1_g[c];
+    P[4 * C + c] = p.ln1_b[c]; P[5 * C + c] = p.colbias ? p.colbias[c] : 0.f;
+  }
+  for (int c = tid; c < 3 * C; c += NT) P[6 * C + c] = p.bqkv[c];
+
+  typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+  u32x4_t ynext[YPT];
+  f32x4_t xnext[MAXG];
+  // Unconditional loads: a row past n (a tile past the last one: every row) reads row n - 1 instead.  Rows are independent
+  // through every phase and a row past n is never stored, so what it holds does not matter.
+  auto fetch = [&](long tile) {
+    const long mb = tile * BM;
+    const int lrow = tid >> 2, part = tid & 3;
+#pragma unroll
+    for (int k = 0; k < YPT; ++k) {
+      const int id = tid + k * NT;
+      const long m = mb + id / NCA < p.n ? mb + id / NCA : p.n - 1;
+      ynext[k] = *reinterpret_cast<const u32x4_t*>(p.y + m * p.ldy + (id % NCA) * 8);
+    }
+    const long mrow = mb + lrow < p.n ? mb + lrow : p.n - 1;
+#pragma unroll
+    for (int i = 0; i < MAXG; ++i) xnext[i] = *reinterpret_cast<const f32x4_t*>(p.x + mrow * p.ldx + 4 * (part + 4 * i));
+  };
+  f32x4_t xres[MAXG];
+  auto stash = [&]() {  // the fetched tile becomes the current one: y -> LDS, the x rows stay in registers
+    asm volatile("" : "+v"(tid));
+#pragma unroll
+    for (int k = 0; k < YPT; ++k) {
+      const int id = tid + k * NT;
+      *reinterpret_cast<u32x4_t*>(R + mlp_lds_off<NCA>(id / NCA, id % NCA)) = ynext[k];
+    }
+#pragma unroll
+    for (int i = 0; i < MAXG; ++i) xres[i] = xnext[i];
+  };
+  // acc = A W_j^T;  A is BM x C in LDS, the 16-byte chunk ch of its row at a_addr(row, ch);  j: 0 = Wl, 1 .. 3 = Wq, Wk, Wv
+  auto mma = [&](auto a_addr, int j, f32x4_t (&acc)[2][TN]) {
+    const int fr = tid & 15, fg = (tid & 63) >> 4;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int t = 0; t < TN; ++t) acc[i][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < NCA / 4; ++kk) {
+      bf16x8_t a[2], b[TN];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) a[i] = *reinterpret_cast<const bf16x8_t*>(a_addr(wm * 32 + i * 16 + fr, 4 * kk + fg));
+#pragma unroll
+      for (int t = 0; t < TN; ++t)
+        b[t] = *reinterpret_cast<const bf16x8_t*>(Ws + j * W_BYTES + mlp_lds_off<NCA>(wn * (C / 2) + t * 16 + fr, 4 * kk + fg));
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int t = 0; t < TN; ++t) acc[i][t] = mfma_16x16x32_bf16(a[i], b[t], acc[i][t]);
+    }
+  };
+  auto y_addr = [&](int row, int ch) { return R + mlp_lds_off<NCA>(row, ch); };
+  auto h_addr = [&](int row, int ch) { return R + row * (CLD * 4) + ch * 16; };
+
+  // One tile.  FULL (all 128 rows < n): no guard anywhere, so the body is straight-line code between its barriers and the
+  // wait for the next tile's rows in stash() counts the tile's own stores issued behind them (vmcnt is in order): the
+  // workgroup never waits for its stores to drain.  With a guarded store on the path the compiler has to wait for all of
+  // them; that form runs only for the ragged last tile.
+  // The thread index is opaque per phase: the addresses derived from it are recomputed where they are used instead of
+  // living in registers across the whole tile (the kernel spilled at C = 64 without this).
+  auto body = [&](auto fullc, long tile) {
+    constexpr bool FULL = decltype(fullc)::value;
+    const long m0 = tile * BM;
+    asm volatile("" : "+v"(tid));
+    fetch(tile + gridDim.x);  // the next tile's rows, in flight behind everything below
+    __syncthreads();          // y of this tile (and, the first time, the weights) visible
+    {
+      f32x4_t acc[2][TN];
+      mma(y_addr, 0, acc);
+      __syncthreads();  // every wave has read y: the C tile may overwrite it
+      const int fr = tid & 15, fg = (tid & 63) >> 4;
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int t = 0; t < TN; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            Cs[(wm * 32 + i * 16 + fg * 4 + r) * CLD + wn * (C / 2) + t * 16 + fr] = acc[i][t][r];
+    }
+    __syncthreads();
+
+    // ---- rows (4 lanes each): + bl, LN_cpe, + x, + t bias -> x ;  LN1 -> h (16-bit, in place over the row's fp32 values)
+    // Every rounding is written out (no implicit contraction).  The tile kernel above and the GEMM epilogue leave the
+    // contraction of these expressions to the compiler, which fuses v - s / C into one fma in the first variance and
+    // nowhere else, a * a + b * b into fma(a, a, b * b), and t * gamma + beta into one fma; in this kernel's straight-line
+    // body it chose differently at C = 64 (x off by an ulp in 4 % of the rows).  Spelled out, the bits are theirs.
+    {
+#pragma clang fp contract(off)
+      asm volatile("" : "+v"(tid));
+      const int lrow = tid >> 2, part = tid & 3;
+      const long m = m0 + lrow;
+      const bool act = FULL || m < p.n;
+      float4 v[MAXG];
+      auto row_stats = [&](auto fusedc, float& mean, float& rstd) {
+#pragma clang fp contract(off)
+        constexpr bool FUSED_DEV = decltype(fusedc)::value;
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < MAXG; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+        s += __shfl_xor(s, 1, 64);
+        s += __shfl_xor(s, 2, 64);
+        mean = s * (1.0f / C);
+        auto dev = [&](float u) { return FUSED_DEV ? __builtin_fmaf(s, -1.0f / C, u) : u - mean; };
+        float q = 0.f;
+#pragma unroll
+        for (int i = 0; i < MAXG; ++i) {
+          const float a = dev(v[i].x), b = dev(v[i].y), c = dev(v[i].z), d = dev(v[i].w);
+          q += __builtin_fmaf(a, a, b * b) + __builtin_fmaf(c, c, d * d);
+        }
+        q += __shfl_xor(q, 1, 64);
+        q += __shfl_xor(q, 2, 64);
+        rstd = 1.0f / sqrtf(__builtin_fmaf(q, 1.0f / C, p.eps));
+      };
+      auto affine = [](float u, float mean, float rstd, float ga, float be) {
+#pragma clang fp contract(off)
+        return __builtin_fmaf((u - mean) * rstd, ga, be);
+      };
+#pragma unroll
+      for (int i = 0; i < MAXG; ++i) {
+        const int cg = part + 4 * i;
+        v[i] = *reinterpret_cast<const float4*>(Cs + lrow * CLD + 4 * cg);
+        const float4 b = *reinterpret_cast<const float4*>(P + 4 * cg);
+        v[i].x += b.x; v[i].y += b.y; v[i].z += b.z; v[i].w += b.w;
+      }
+      float mean, rstd;
+      row_stats(std::true_type{}, mean, rstd);
+#pragma unroll
+      for (int i = 0; i < MAXG; ++i) {
+        const int cg = part + 4 * i;
+        const float4 ga = *reinterpret_cast<const float4*>(P + C + 4 * cg);
+        const float4 be = *reinterpret_cast<const float4*>(P + 2 * C + 4 * cg);
+        v[i].x = affine(v[i].x, mean, rstd, ga.x, be.x);
+        v[i].y = affine(v[i].y, mean, rstd, ga.y, be.y);
+        v[i].z = affine(v[i].z, mean, rstd, ga.z, be.z);
+        v[i].w = affine(v[i].w, mean, rstd, ga.w, be.w);
+        if (act) {
+          const f32x4_t r = xres[i];
+          v[i].x += r.x; v[i].y += r.y; v[i].z += r.z; v[i].w += r.w;
+          if (p.colbias) {
+            const float4 t = *reinterpret_cast<const float4*>(P + 5 * C + 4 * cg);
+            v[i].x += t.x; v[i].y += t.y; v[i].z += t.z; v[i].w += t.w;
+          }
+          *reinterpret_cast<float4*>(p.x + m * p.ldx + 4 * cg) = v[i];
+        } else {
+          v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+      }
+      row_stats(std::false_type{}, mean, rstd);  // (its cross-lane adds need every lane's v: all four lanes have read the row)
+#pragma unroll
+      for (int i = 0; i < MAXG; ++i) {
+        const int cg = part + 4 * i;
+        const float4 ga = *reinterpret_cast<const float4*>(P + 3 * C + 4 * cg);
+        const float4 be = *reinterpret_cast<const float4*>(P + 4 * C + 4 * cg);
+        uint2 u;
+        u.x = pack_bf16x2(affine(v[i].x, mean, rstd, ga.x, be.x), affine(v[i].y, mean, rstd, ga.y, be.y));
+        u.y = pack_bf16x2(affine(v[i].z, mean, rstd, ga.z, be.z), affine(v[i].w, mean, rstd, ga.w, be.w));
+        *reinterpret_cast<uint2*>(h_addr(lrow, cg >> 1) + (cg & 1) * 8) = u;
+      }
+    }
+    __syncthreads();
+
+    // ---- qkv: the three products back to back, then + bias, rounding and the stores through 16-bit rows in R
+    asm volatile("" : "+v"(tid));
+    f32x4_t acc[3][2][TN];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) mma(h_addr, 1 + j, acc[j]);
+    __syncthreads();  // every wave has read h
+    auto emit = [&](auto j0c, auto njc) {  // columns [j0 C, (j0 + nj) C) of qkv
+      constexpr int J0 = decltype(j0c)::value, NJ = decltype(njc)::value;
+      constexpr int S = NJ * C * 2 + 8;  // staged row stride in bytes: rows 4 apart fall 8 banks apart
+      constexpr int PPR = NJ * C / 4;    // 8-byte pieces per row
+      asm volatile("" : "+v"(tid));
+      const int fr = tid & 15, fg = (tid & 63) >> 4;
+#pragma unroll
+      for (int jj = 0; jj < NJ; ++jj) {
+        const int j = J0 + jj;
+        const bool tbf = LP_IS_F16 && j == 2 && p.v_bf16;  // the attention's P V product is bfloat16 in both builds
+#pragma unroll
+        for (int t = 0; t < TN; ++t) {
+          const int col = wn * (C / 2) + t * 16 + fr;
+          const float b = P[6 * C + j * C + col];
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            const f32x4_t a = acc[j][i][t];
+            const uint32_t u01 = tbf ? pack_truebf16x2(a[0] + b, a[1] + b) : pack_bf16x2(a[0] + b, a[1] + b);
+            const uint32_t u23 = tbf ? pack_truebf16x2(a[2] + b, a[3] + b) : pack_bf16x2(a[2] + b, a[3] + b);
+            char* d = R + (wm * 32 + i * 16 + fg * 4) * S + (jj * C + col) * 2;
+            *reinterpret_cast<uint16_t*>(d) = (uint16_t)u01;
+            *reinterpret_cast<uint16_t*>(d + S) = (uint16_t)(u01 >> 16);
+            *reinterpret_cast<uint16_t*>(d + 2 * S) = (uint16_t)u23;
+            *reinterpret_cast<uint16_t*>(d + 3 * S) = (uint16_t)(u23 >> 16);
+          }
+        }
+      }
+      __syncthreads();
+      asm volatile("" : "+v"(tid));
+#pragma unroll
+      for (int k = 0; k < BM * PPR / NT; ++k) {
+        const int item = tid + k * NT, row = item / PPR, pc = item % PPR;
+        const long m = m0 + row;
+        if (FULL || m < p.n)
+          *reinterpret_cast<uint2*>(p.qkv + m * p.ldqkv + J0 * C + 4 * pc) = *reinterpret_cast<const uint2*>(R + row * S + pc * 8);
+      }
+      __syncthreads();  // R is rewritten: by v's rows, then by the next tile's y
+    };
+    emit(std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
+    emit(std::integral_constant<int, 2>{}, std::integral_constant<int, 1>{});
+    if (FULL) stash();
+  };
+
+  const long full_tiles = p.n / BM, tiles = (p.n + BM - 1) / BM;
+  long tile = blockIdx.x;  // (the trip count is uniform per workgroup: every thread meets every barrier)
+  fetch(tile);
+  stash();
+  // (the first tile's x rows are waited for here, not at their first use inside the loop: a wait placed there would
+  // also count, on every later trip, stores of the tile before)
+#pragma unroll
+  for (int i = 0; i < MAXG; ++i) asm volatile("" : "+v"(xres[i]));
+#pragma unroll 1
+  for (; tile < full_tiles; tile += gridDim.x) body(std::true_type{}, tile);
+  if (tile < tiles) body(std::false_type{}, tile);
+}
+
+template <int C>
+int launch_head_stream(const HeadP& p, hipStream_t s) {
+  constexpr int LDS = 4 * C * C * 2 + 128 * (C + 4) * 4 + 9 * C * 4;
+  static std::atomic<bool> attr_done{false};  // (a concurrent first call sets the attribute twice: harmless)
+  if (!attr_done) {
+    if (LDS > 64 * 1024 && hipFuncSetAttribute((const void*)cpe_head_stream_kernel<C>,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
+      return CDSEG_ERR_LAUNCH;
+    attr_done = true;
+  }
+  // two workgroups per CU (C = 64: all that 2 x 70 KB of LDS and 106 VGPRs admit; C = 32 measured no faster with more)
+  static const int per_cu = cdseg_knob("CDSEG_HEAD_STREAM_WGS", 2);
+  const long tiles = (p.n + 127) / 128, cap = 256L * (per_cu < 1 ? 1 : per_cu);
+  const dim3 grid((unsigned)(tiles < cap ? tiles : cap));
+  hipLaunchKernelGGL((cpe_head_stream_kernel<C>), grid, dim3(512), LDS, s, p);
+  return hipGetLastError() == hipSuccess ? CDSEG_OK : CDSEG_ERR_LAUNCH;
+}
+
 }  // namespace
 
 // Supported: bf16, channels 32 or 64; else CDSEG_ERR_UNSUPPORTED.  colbias may be NULL.
@@ -583,6 +874,10 @@ extern "C" int cdseg_cpe_head_fused(const void* y, int ldy, const void* wl, cons
   p.qkv = (bf16_t*)qkv; p.n = n; p.ldy = ldy; p.ldx = ldx; p.ldqkv = ldqkv; p.eps = eps;
   p.v_bf16 = (qkv_flags & CDSEG_ATTN_V_BF16) ? 1 : 0;
   static const int bm = cdseg_knob("CDSEG_HEAD_BM", 128);
+  // CDSEG_HEAD_STREAM = 0: the one-tile-per-workgroup 128-row kernel instead of the persistent one (A/B runs)
+  static const int stream_head = cdseg_knob("CDSEG_HEAD_STREAM", 1);
+  if (bm == 128 && n >= 128 * 512 && stream_head)  // enough 128-row tiles for two persistent workgroups per CU
+    return channels == 32 ? launch_head_stream<32>(p, (hipStream_t)stream) : launch_head_stream<64>(p, (hipStream_t)stream);
   if (bm == 128 && n >= 128 * 512) {  // enough 128-row workgroups to fill the chip twice
     const dim3 grid((unsigned)((n + 127) / 128));
     if (channels == 32) hipLaunchKernelGGL((cpe_head_fused_kernel<32, 128>), grid, dim3(512), 0, (hipStream_t)stream, p);

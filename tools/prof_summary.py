@@ -28,10 +28,18 @@ def main():
     print("\n# per launch shape (grid in threads) for the GEMM / conv / attention kernels")
     rows = list(cur.execute(
         "select name, grid_x, grid_y, count(*), avg(duration), sum(duration) from kernels "
-        "where name like '%gemm_%' or name like '%attn_%' or name like '%conv_ll%' or name like '%stem5%' or name like '%_rr_kernel%' or name like '%fused_kernel%' "
+        "where name like '%gemm_%' or name like '%attn_%' or name like '%conv_ll%' or name like '%stem5%' or name like '%_rr_kernel%' or name like '%fused_kernel%' or name like '%head_stream%' "
         "group by name, grid_x, grid_y order by sum(duration) desc"))
     for n, gx, gy, c, a, s in rows:
         print(f"{c:7d} {s / 1e6 / steps:9.3f} ms/step {a / 1e3:9.2f} us  grid=({gx},{gy})  {short(n)}")
+    # the wide-stage Block head: a persistent grid has one size whatever the rows, so its launch shapes can only be told
+    # apart by their place in a forward - the last forward's launches in dispatch order, for either form of the kernel
+    rows = list(cur.execute("select name, grid_x, duration from kernels where name like '%cpe_head_fused_kernel%' or "
+                            "name like '%cpe_head_stream%' order by start desc limit 12"))[::-1]
+    if rows:
+        print("\n# Block head (csrc/mlp.hip), last 12 launches in dispatch order")
+        for n, gx, d in rows:
+            print(f"{d / 1e3:9.2f} us  grid={gx}  {short(n)}")
     concurrency(db, cur)
 
 
