@@ -242,6 +242,19 @@ SIGNATURES = {
                                    c_void_p, c_void_p, c_size_t, c_void_p]),
     "cdseg_seg_loss_bwd": (c_int, [c_void_p, c_int, c_void_p, c_long, c_int, c_long, POINTER(c_int32), c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_int, c_void_p]),
+    "cdseg_bn_partition": (c_int, [c_long, c_int, POINTER(c_long), POINTER(c_int)]),
+    "cdseg_bn_ws_bytes": (c_size_t, [c_long, c_int]),
+    "cdseg_bn_stats": (c_int, [c_void_p, c_int, c_long, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "cdseg_bn_finish": (c_int, [c_void_p, c_int, ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p]),
+    "cdseg_bn_gelu_fwd": (c_int, [c_void_p, c_int, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                  c_void_p]),
+    "cdseg_bn_gelu_bwd_sums": (c_int, [c_void_p, c_int, c_void_p, c_int, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_size_t, c_void_p]),
+    "cdseg_bn_gelu_bwd_dx": (c_int, [c_void_p, c_int, c_void_p, c_int, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "cdseg_segment_max_arg": (c_int, [c_void_p, c_int, c_void_p, c_long, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "cdseg_segment_max_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_long, c_int, c_void_p, c_int, c_void_p]),
     "cdseg_opt_chunks": (c_int, [POINTER(c_long), c_int, POINTER(c_int32), POINTER(c_long)]),
     "cdseg_opt_ws_bytes": (c_size_t, [c_int, c_long]),
     "cdseg_grad_norm": (c_int, [POINTER(OptTensor), c_int, c_void_p, c_long, c_void_p, c_float, c_void_p, c_void_p, c_size_t,

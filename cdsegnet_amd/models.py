@@ -439,6 +439,11 @@ class DefaultSegmentorV2(nn.Module):
         # ascending row index); read at every forward() and by the loss of inference(eval=True), anything else raises
         # ValueError there; not part of the state_dict
         self.train_loss = "torch"
+        # train-mode BatchNorm1d + GELU sites and the pooling maximum of the training forward: "torch" (default: torch device
+        # ops, statistics of this process's rows) | "fused": the kernels of csrc/norm.hip (fp64 statistics in a fixed order;
+        # nn.SyncBatchNorm modules - convert_sync_batchnorm, cfg.sync_bn - get statistics over all ranks of their process
+        # group); read at every forward(), anything else raises ValueError there; not part of the state_dict
+        self.train_norm = "torch"
         self._lanes = {}
         self.noise_source = "torch_cpu"  # "torch_cpu" replays the reference's CPU-generator draws | "device"
         # noise_level jitter: "torch_cpu" = the CPU-run reference's draw order (golden vectors) | "device" = device

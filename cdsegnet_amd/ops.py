@@ -1304,6 +1304,139 @@ def segment_sum(src, seg_start, m):
     return out
 
 
+# ------------------------------------------------------------------ train-mode BatchNorm + GELU, pooling maximum (csrc/norm.hip)
+BN_WIDTHS = range(16, 513, 16)  # channel counts of the kernels of csrc/norm.hip
+
+
+class BnPartition(tuple):
+    """(rows_per_block, blocks) of the two BatchNorm reduction passes: block b covers rows b * rows_per_block .. (the last may be
+    shorter); the block partials are added by ascending block index."""
+    __slots__ = ()
+    rows_per_block = property(lambda self: self[0])
+    blocks = property(lambda self: self[1])
+
+
+def bn_partition(m, c):
+    """Row partition of `bn_stats` and of the sums of `bn_gelu_bwd` for an (m, c) input: a function of the shape only (host
+    code, no GPU needed, the same in both builds)."""
+    rows, blocks = ctypes.c_long(0), ctypes.c_int(0)
+    check(_lib.load().cdseg_bn_partition(int(m), int(c), ctypes.byref(rows), ctypes.byref(blocks)), "bn_partition")
+    return BnPartition((rows.value, blocks.value))
+
+
+def _bn_rows(what, *ts):
+    """fp32 (rows, c) operands with contiguous rows (any row stride: column slices of wider buffers pass)."""
+    for t in ts:
+        if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.shape != ts[0].shape:
+            raise _lib.CdsegError(f"{what}: fp32 (rows, c) tensors of one shape with contiguous rows")
+
+
+def _a16(t):
+    """A per-channel vector the kernels load 16 bytes at a time: contiguous fp32, 16-byte aligned (a copy only if it is not)."""
+    t = t.detach()
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        t = t.float().contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _bn_ws(lib, m, c, device):
+    return torch.empty(max(16, lib.cdseg_bn_ws_bytes(int(m), int(c))), dtype=torch.uint8, device=device)
+
+
+def bn_stats(x):
+    """Per-channel statistics of fp32 x (m, c): a (2 c + 1) fp64 device tensor [sum x, sum x^2, m], summed in fp64 in an order
+    fixed by (m, c) (cdseg_bn_stats).  Buffers of several row shards merge by plain addition; m = 0 gives zeros."""
+    _need_gpu(x)
+    _bn_rows("bn_stats", x)
+    m, c = x.shape
+    if m == 0:
+        return torch.zeros(2 * c + 1, dtype=torch.float64, device=x.device)
+    lib = _lib.load()
+    stats = torch.empty(2 * c + 1, dtype=torch.float64, device=x.device)
+    ws = _bn_ws(lib, m, c, x.device)
+    check(lib.cdseg_bn_stats(_ptr(x), x.stride(0), m, c, _ptr(stats), _ptr(ws), ws.numel(), _stream()), "bn_stats")
+    return stats
+
+
+def bn_finish(stats, eps, momentum, running_mean=None, running_var=None):
+    """(mean, invstd) fp32 (c) from a (merged) statistics buffer; the row count is read from stats[2 c] on the device.
+    running_mean / running_var (fp32, contiguous) are updated in place like nn.BatchNorm1d (unbiased variance)."""
+    _need_gpu(stats)
+    c = (stats.numel() - 1) // 2
+    assert stats.dtype == torch.float64 and stats.is_contiguous() and stats.numel() == 2 * c + 1
+    for r in (running_mean, running_var):
+        assert r is None or (r.dtype == torch.float32 and r.is_contiguous() and r.numel() == c)
+    mean = torch.empty(c, dtype=torch.float32, device=stats.device)
+    invstd = torch.empty(c, dtype=torch.float32, device=stats.device)
+    check(_lib.load().cdseg_bn_finish(_ptr(stats), c, float(eps), float(momentum), _ptr(mean), _ptr(invstd), _ptr(running_mean),
+                                      _ptr(running_var), _stream()), "bn_finish")
+    return mean, invstd
+
+
+def bn_gelu_fwd(x, mean, invstd, gamma, beta, out=None):
+    """y = GELU(gamma (x - mean) invstd + beta), erf form (cdseg_bn_gelu_fwd); out: a (m, c) fp32 view to write into."""
+    _need_gpu(x)
+    y = torch.empty(x.shape, dtype=torch.float32, device=x.device) if out is None else out
+    _bn_rows("bn_gelu_fwd", x, y)
+    m, c = x.shape
+    check(_lib.load().cdseg_bn_gelu_fwd(_ptr(x), x.stride(0), m, c, _ptr(_a16(mean)), _ptr(_a16(invstd)), _ptr(_a16(gamma)),
+                                        _ptr(_a16(beta)), _ptr(y), y.stride(0), _stream()), "bn_gelu_fwd")
+    return y
+
+
+def bn_gelu_bwd(x, dy, mean, invstd, gamma, beta, count, hook=None, out=None):
+    """Backward of `bn_gelu_fwd` over batch statistics: returns (dx, gsums) with gsums (2 c) fp64 = [sum g, sum g x_hat] over
+    THESE rows (dbeta, dgamma), g = dy GELU'(z) recomputed from x.  count: fp64 device tensor whose first element is the row
+    count behind mean / invstd (a view of the statistics buffer).  hook(gsums) -> the sums dx is formed with (SyncBN: the sums
+    over all ranks); it runs between the two passes, also for m = 0.  out: a (m, c) fp32 view for dx."""
+    _need_gpu(x, dy, count)
+    dx = torch.empty(x.shape, dtype=torch.float32, device=x.device) if out is None else out
+    _bn_rows("bn_gelu_bwd", x, dy, dx)
+    assert count.dtype == torch.float64 and count.numel() >= 1
+    m, c = x.shape
+    lib = _lib.load()
+    mean, invstd, gamma, beta = _a16(mean), _a16(invstd), _a16(gamma), _a16(beta)
+    if m == 0:
+        gsums = torch.zeros(2 * c, dtype=torch.float64, device=x.device)
+    else:
+        gsums = torch.empty(2 * c, dtype=torch.float64, device=x.device)
+        ws = _bn_ws(lib, m, c, x.device)
+        check(lib.cdseg_bn_gelu_bwd_sums(_ptr(x), x.stride(0), _ptr(dy), dy.stride(0), m, c, _ptr(mean), _ptr(invstd), _ptr(gamma),
+                                         _ptr(beta), _ptr(gsums), _ptr(ws), ws.numel(), _stream()), "bn_gelu_bwd (sums)")
+    total = gsums if hook is None else hook(gsums).contiguous()
+    check(lib.cdseg_bn_gelu_bwd_dx(_ptr(x), x.stride(0), _ptr(dy), dy.stride(0), m, c, _ptr(mean), _ptr(invstd), _ptr(gamma),
+                                   _ptr(beta), _ptr(total), _ptr(count), _ptr(dx), dx.stride(0), _stream()), "bn_gelu_bwd (dx)")
+    return dx, gsums
+
+
+def segment_max_arg(y, seg_start, m):
+    """(out, arg): out (m, c) fp32 = per-channel maximum over the rows seg_start[j] .. seg_start[j + 1] - 1 of y (the bits of
+    `segment_max` without scale / shift / activation), arg (m, c) int32 = the first row that holds it (cdseg_segment_max_arg)."""
+    _need_gpu(y, seg_start)
+    _bn_rows("segment_max_arg", y)
+    assert seg_start.dtype == torch.int32 and seg_start.numel() >= m + 1
+    c = y.shape[1]
+    out = torch.empty((m, c), dtype=torch.float32, device=y.device)
+    arg = torch.empty((m, c), dtype=torch.int32, device=y.device)
+    check(_lib.load().cdseg_segment_max_arg(_ptr(y), y.stride(0), _ptr(seg_start), int(m), c, _ptr(out), out.stride(0), _ptr(arg),
+                                            arg.stride(0), _stream()), "segment_max_arg")
+    return out, arg
+
+
+def segment_max_bwd(dout, arg, cluster):
+    """dy (n, c) fp32: dy[i] = dout[cluster[i]] where arg[cluster[i]] == i, else 0, per channel; one launch that writes every
+    element once (cdseg_segment_max_bwd).  cluster (n) int32: the pooled row of every fine row."""
+    _need_gpu(dout, arg, cluster)
+    _bn_rows("segment_max_bwd", dout)
+    assert arg.dtype == torch.int32 and arg.shape == dout.shape and arg.stride(1) == 1
+    assert cluster.dtype == torch.int32 and cluster.is_contiguous()
+    n, c = cluster.numel(), dout.shape[1]
+    dy = torch.empty((n, c), dtype=torch.float32, device=dout.device)
+    check(_lib.load().cdseg_segment_max_bwd(_ptr(dout), dout.stride(0), _ptr(arg), arg.stride(0), _ptr(cluster), n, c, _ptr(dy),
+                                            dy.stride(0), _stream()), "segment_max_bwd")
+    return dy
+
+
 # ------------------------------------------------------------------ fused segmentation loss (csrc/loss.hip)
 def seg_loss_plan(logits, labels, ignore_index):
     """The fused loss's ONE host read: the label histogram of the valid rows (cdseg_seg_loss_fwd phase 0).  Returns the plan

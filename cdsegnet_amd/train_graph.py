@@ -16,6 +16,9 @@ unchanged - and underneath, every product that carries the FLOPs runs on this li
     LayerNorm                                    cdseg_layernorm / cdseg_layernorm_bwd
     serialized (cross) attention                 cdseg_attention / cdseg_attention_bwd (recompute-P, gathered rows)
     segment max of the pooling                   cdseg_segment_max forward; the arg-max mask is recomputed in the backward
+                                                 (train_norm "fused": cdseg_segment_max_arg / cdseg_segment_max_bwd)
+    train-mode BatchNorm1d -> GELU               torch device ops by default; train_norm "fused": cdseg_bn_stats / _finish /
+                                                 cdseg_bn_gelu_fwd, backward cdseg_bn_gelu_bwd_sums / _dx (csrc/norm.hip)
 
 in exact fp32 by default.  The reference never runs its attention core in fp32 on a GPU (`qkv.half()` into flash-attention,
 whose backward is half too): `model.train_precision = "fp16-attn"` / `"bf16-attn"` runs the attention core of every Block
@@ -27,9 +30,9 @@ input and weight rounded once to the 16-bit type, forward and data gradient by c
 gradient by cdseg_linear_wgrad16 / cdseg_conv_wgrad16, fp32 accumulation throughout, the 16-bit input saved for the backward,
 dy cast without saturation so that a GradScaler sees an overflow.  The residual stream, LayerNorm, GELU, BatchNorm sites,
 heads, timestep MLP, criteria, parameters and .grad stay fp32.  ONE difference from torch autocast: autocast also rounds each
-Linear's OUTPUT to fp16; here the outputs stay fp32 (operand rounding and fp32 accumulation are the same).  What stays plain torch device ops: train-mode BatchNorm1d (3 per pooling stage, batch
-statistics), GELU between them, the swish timestep MLP on B rows, row masks of stochastic depth, q_sample, the two
-(C -> classes) heads, and the criteria (cdsegnet_amd.losses).  All integer work - serialization, pooling structure,
+Linear's OUTPUT to fp16; here the outputs stay fp32 (operand rounding and fp32 accumulation are the same).  What stays plain torch device ops: the swish timestep MLP on B rows, row masks of
+stochastic depth, q_sample, the two (C -> classes) heads, the criteria (cdsegnet_amd.losses) - and, in the default
+`train_norm = "torch"`, train-mode BatchNorm1d (3 per pooling stage, batch statistics) with the GELU behind it.  All integer work - serialization, pooling structure,
 kernel maps, padded patch plans - is the inference engine's plan (Engine.build_plan), shared with the inference path.
 
 Deterministic mode (`model.train_deterministic`: None = follow torch.are_deterministic_algorithms_enabled(), True / False
@@ -44,7 +47,8 @@ the mode.  What the mode changes are the backward reductions that otherwise leav
 Everything else on the step is already order-fixed: the permutation gathers (perm0, inv0, ref_order) have unique indices;
 `_SceneRows` sums contiguous rows and `_SegmentMax` selects one child, neither with atomics; the attention backward adds at most
 two values onto a zeroed element (a row sits in at most two slots), which commutes; cdseg_gemm's split-K has no atomics;
-train-mode BatchNorm and the criteria are torch ops that are deterministic or raise / warn under torch's flag.  Limit: the two
+train-mode BatchNorm (default `train_norm`) and the criteria are torch ops that are deterministic or raise / warn under torch's
+flag; with `train_norm = "fused"` the BatchNorm statistics and backward sums are fp64 sums in an order fixed by the shape.  Limit: the two
 (C -> classes) heads and the timestep MLP are torch GEMMs (rocBLAS), which torch pins to atomic-free kernels only under
 torch.use_deterministic_algorithms(True); `train_deterministic = True` alone does not reach into them.
 
@@ -52,6 +56,19 @@ Fused loss (`model.train_loss = "fused"`, default "torch"; read at every forward
 criteria, forward and backward, on the kernels of csrc/loss.hip (losses.FusedCriteria -> ops.seg_loss / ops.seg_loss_bwd) instead
 of torch's per-class sort loop.  Its sums run in a fixed order whatever `train_deterministic` says, and the Lovasz sort breaks
 ties by ascending row index, where torch's unstable sort leaves the order (and with it the gradient of tied rows) open.
+
+Fused norm sites (`model.train_norm = "fused"`, default "torch"; read at every forward): every train-mode BatchNorm1d -> GELU
+site (stems, SerializedPooling.norm, both projections of SerializedUnpooling: 20 in the conditional model) runs as `_BnGelu` on
+the kernels of csrc/norm.hip - per-channel sum x / sum x^2 in fp64 by row blocks whose partials are added by ascending block
+index, one normalise + GELU pass, and a backward that recomputes z from x (saved: x, mean, invstd; no BatchNorm output) in two
+passes: the fp64 sums of g and g x_hat, then dx.  The pooling maximum keeps its arg-max (`_SegmentMaxArg`: the first maximal
+child, torch_scatter's rule) and its backward is one launch.  nn.SyncBatchNorm modules (the reference trainer's
+convert_sync_batchnorm under cfg.sync_bn, engines/train.py:275-276) get statistics over all ranks of their process group: one
+all_gather of the (2 c + 1) fp64 buffer in the forward and one of the (2 c) sums in the backward, each added in rank order
+(`gather_ranks`); dgamma / dbeta stay this rank's sums, averaged with every other gradient by dist.GradSync.  In the default
+mode such modules normalise with this rank's rows only, and say so once.  Eval mode, widths that are no multiple of 16 up to
+512, momentum = None and modules without affine parameters take the torch path in either mode; a CPU tensor in the fused mode
+raises like every other op of the library.  These sites are fp32 in every train_precision.
 """
 import warnings
 
@@ -438,11 +455,119 @@ def _swish(x):  # ptv3.py:30-31
     return x * torch.sigmoid(x)
 
 
-def _bn_gelu(x, bn):
+TRAIN_NORMS = ("torch", "fused")
+_NORM_WIDTHS = range(16, 513, 16)  # channel counts of the kernels of csrc/norm.hip
+
+
+def resolve_train_norm(model):
+    """model.train_norm: "torch" (default) or "fused" (`_BnGelu`, `_SegmentMaxArg`); anything else raises."""
+    tn = getattr(model, "train_norm", "torch")
+    if tn not in TRAIN_NORMS:
+        raise ValueError(f"train_norm must be one of {sorted(TRAIN_NORMS)}, not {tn!r}")
+    return tn
+
+
+def merge_shards(parts):
+    """Statistics / backward-sum buffers of several row shards -> the buffer of all rows: plain fp64 addition in list order."""
+    t = parts[0].clone()
+    for p in parts[1:]:
+        t += p
+    return t
+
+
+def gather_ranks(buf, group):
+    """The cross-rank step of SyncBN: ONE all_gather of this rank's fp64 buffer, added in rank order (`merge_shards`) - the
+    same bits on every rank, no all-reduce whose order the backend picks."""
+    dist = torch.distributed
+    parts = [torch.empty_like(buf) for _ in range(dist.get_world_size(group))]
+    dist.all_gather(parts, buf.contiguous(), group=group)
+    return merge_shards(parts)
+
+
+def sync_group(bn):
+    """(process group,) when `bn` is an nn.SyncBatchNorm whose group spans more than one rank of an initialised
+    torch.distributed (group None = the default group), else None: statistics over this process's rows."""
+    if not isinstance(bn, torch.nn.SyncBatchNorm):
+        return None
+    dist = torch.distributed
+    if not (dist.is_available() and dist.is_initialized()):
+        return None
+    group = getattr(bn, "process_group", None)
+    return (group,) if dist.get_world_size(group) > 1 else None
+
+
+class _BnGelu(torch.autograd.Function):
+    """nn.BatchNorm1d (training) -> GELU on the kernels of csrc/norm.hip (`model.train_norm = "fused"`): fp64 statistics in a
+    fixed order, one fused normalise + GELU pass; the backward recomputes z from x (saved: x, mean, invstd and the 2 c + 1
+    statistics, no BatchNorm output).  group (from `sync_group`): the statistics and the backward sums are gathered over the
+    ranks (`gather_ranks`), a rank without rows takes part with zeros.  dgamma / dbeta are THIS rank's sums (averaging them is
+    the gradient synchronisation's job, as with torch's SyncBatchNorm).  Running buffers and num_batches_tracked are updated
+    like the module would.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, bn, group):
+        x = _c(x)
+        m, c = x.shape
+        stats = ops.bn_stats(x)
+        if group is not None:
+            stats = gather_ranks(stats, group[0])
+        elif m <= 1:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+        mean, invstd = ops.bn_finish(stats, bn.eps, bn.momentum, bn.running_mean, bn.running_var)
+        if bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
+        y = ops.bn_gelu_fwd(x, mean, invstd, gamma, beta)
+        ctx.save_for_backward(x, mean, invstd, gamma, beta, stats)
+        ctx.group = group
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mean, invstd, gamma, beta, stats = ctx.saved_tensors
+        c = x.shape[1]
+        group = ctx.group
+        hook = None if group is None else (lambda g: gather_ranks(g, group[0]))
+        dx, gs = ops.bn_gelu_bwd(x, _c(dy.float()), mean, invstd, gamma, beta, stats[2 * c:], hook=hook)
+        return dx, gs[c:].float(), gs[:c].float(), None, None
+
+
+class _SegmentMaxArg(torch.autograd.Function):
+    """`_SegmentMax` with the arg-max kept (`model.train_norm = "fused"`): the forward writes the first maximal child of every
+    (pooled row, channel) next to the maximum, the backward is one launch over the fine rows (saved: arg int32 and cluster,
+    neither y nor out)."""
+
+    @staticmethod
+    def forward(ctx, y, seg, cluster, m):
+        out, arg = ops.segment_max_arg(_c(y), seg, m)
+        ctx.save_for_backward(arg, cluster)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        arg, cluster = ctx.saved_tensors
+        return ops.segment_max_bwd(_c(dout.float()), arg, _c(cluster)), None, None, None
+
+
+_warned_local_sync_bn = False
+
+
+def _bn_gelu(x, bn, norm="torch"):
     """nn.BatchNorm1d -> GELU, in the module's own mode: training = batch statistics, running buffers updated like the
-    module would; eval (`model.eval(); model(batch)`, e.g. a validation-loss hook) = running statistics, buffers untouched."""
+    module would; eval (`model.eval(); model(batch)`, e.g. a validation-loss hook) = running statistics, buffers untouched.
+    norm "fused" (model.train_norm): the training form runs as `_BnGelu` where the kernels cover it (width a multiple of 16 up
+    to 512, affine, a float momentum) - with statistics over all ranks when `bn` is an nn.SyncBatchNorm (`sync_group`)."""
     if not bn.training:
         return F.gelu(F.batch_norm(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, False, bn.momentum, bn.eps))
+    group = sync_group(bn)
+    if (norm == "fused" and x.dim() == 2 and x.dtype == torch.float32 and x.shape[1] in _NORM_WIDTHS and bn.weight is not None
+            and bn.bias is not None and isinstance(bn.momentum, float)):
+        return _BnGelu.apply(x, bn.weight, bn.bias, bn, group)
+    if group is not None:
+        global _warned_local_sync_bn
+        if not _warned_local_sync_bn:
+            _warned_local_sync_bn = True
+            warnings.warn("nn.SyncBatchNorm under more than one rank: this path normalises with the statistics of THIS rank's "
+                          "rows only; model.train_norm = \"fused\" synchronises them (cdsegnet_amd/train_graph.py)")
     if bn.num_batches_tracked is not None:
         bn.num_batches_tracked.add_(1)
     return F.gelu(F.batch_norm(x, bn.running_mean, bn.running_var, bn.weight, bn.bias, True, bn.momentum, bn.eps))
@@ -491,6 +616,7 @@ class TrainGraph:
         self.criteria = build_criteria(model.criteria_cfg, model.loss_type, model.task_num)
         self.fused_criteria = None  # losses.FusedCriteria, built when model.train_loss first says "fused"
         self.train_loss = "torch"   # from model.train_loss at every forward
+        self.train_norm = "torch"   # from model.train_norm at every forward
 
     # ---------------------------------------------------------------------------------------- pieces
     def _mask(self, st, name, rate, masks):
@@ -552,26 +678,30 @@ class TrainGraph:
         lv = plan.levels[0]
         x = feat[plan.perm0.long()]
         y = subm_conv(x, emb.stem.conv.weight, None, lv.nbr(emb.stem.conv.kernel_size, True), self.mm_variant, self.det)
-        return _St(lv, _bn_gelu(y, emb.stem.norm), curves, inv0)
+        return _St(lv, _bn_gelu(y, emb.stem.norm, self.train_norm), curves, inv0)
 
     def _pooling(self, plan, st, down, cum_to, perm):
         """ref: ptv3.py:464-555."""
         fine, coarse = st.level, plan.levels[cum_to]
         cluster, seg = plan.link(fine.cum, cum_to)
-        y = _SegmentMax.apply(self._lin(st.x, down.proj), seg, cluster, coarse.n)
+        y = self._lin(st.x, down.proj)
+        if self.train_norm == "fused" and y.shape[1] in _NORM_WIDTHS:
+            y = _SegmentMaxArg.apply(y, seg, cluster, coarse.n)
+        else:
+            y = _SegmentMax.apply(y, seg, cluster, coarse.n)
         curves = st.curves if perm is None else [st.curves[int(j)] for j in perm]
         order = coarse.order(st.curves[0])  # the reference numbers the pooled points by unique(code[0]) (ptv3.py:489)
         if order is None:
             order = torch.arange(coarse.n, dtype=torch.int32, device=st.x.device)
-        return _St(coarse, _bn_gelu(y, down.norm[0]), curves, order, parent=st)
+        return _St(coarse, _bn_gelu(y, down.norm[0], self.train_norm), curves, order, parent=st)
 
     def _unpooling(self, plan, st, up):
         """ref: ptv3.py:597-630."""
         parent = st.parent
         fine, coarse = parent.level, st.level
         cluster, seg = plan.link(fine.cum, coarse.cum)
-        child = _bn_gelu(self._lin(st.x, up.proj[0]), up.proj[1])
-        par = _bn_gelu(self._lin(parent.x, up.proj_skip[0]), up.proj_skip[1])
+        child = _bn_gelu(self._lin(st.x, up.proj[0]), up.proj[1], self.train_norm)
+        par = _bn_gelu(self._lin(parent.x, up.proj_skip[0]), up.proj_skip[1], self.train_norm)
         out = _St(fine, None, parent.curves, parent.ref_order, parent=parent.parent)
         out.conv = par  # what the next Block's CPE conv reads: the skip feature before scaling and merging
         f = 2 ** -0.5 if up.skip_connection_scale else 1.0
@@ -637,6 +767,7 @@ class TrainGraph:
         self.mm_variant = TRAIN_PRECISIONS[tp] if tp.endswith("-amp") else None
         self.det = resolve_deterministic(self.model)
         self.train_loss = resolve_train_loss(self.model)
+        self.train_norm = resolve_train_norm(self.model)
         if feat_is_cuda(input_dict):
             with torch.autocast(device_type="cuda", enabled=False):
                 return self._forward(input_dict, draws)

@@ -753,6 +753,55 @@ int cdseg_seg_loss_bwd(const float* logits, int ldl, const int64_t* labels, long
                        const int32_t* hist_host, const float* coef, const float* g_ce, const float* g_lovasz, float* dlogits,
                        int lddl, void* stream);
 
+/* ------------------------------------------------------------------ train-mode BatchNorm + GELU, pooling maximum (csrc/norm.hip)
+ * ref: nn.BatchNorm1d (training) -> nn.GELU at the stems, SerializedPooling.norm and both projections of SerializedUnpooling
+ * (ptv3.py:464-555, 597-663), nn.SyncBatchNorm (engines/train.py:275-276), torch_scatter.segment_csr(reduce = "max") and its
+ * arg-max backward (ptv3.py:510-515).  fp32 tensors (rows, c) with a row stride; per channel j over the m rows:
+ *   stats   = [sum_i x_ij (c), sum_i x_ij^2 (c), m]  in fp64: 2 c + 1 doubles.  Buffers of several row shards (ranks) merge by
+ *             plain addition; fp64 sums of fp32 data keep E[x^2] - mean^2 safe.
+ *   mean_j  = stats[j] / n, var_j = max((n stats[c + j] - stats[j]^2) / n^2, 0) with n = stats[2 c] (read on the device; both
+ *             products are carried exactly, so the difference loses nothing beyond the rounding the sums carry),
+ *   invstd_j = 1 / sqrt(var_j + eps), all in fp64 and rounded to fp32 once; the running buffers (each may be NULL) are updated
+ *             in place like nn.BatchNorm1d: r = (1 - momentum) r + momentum v, v = mean for running_mean and the UNBIASED
+ *             variance var n / (n - 1) for running_var (n <= 1: var itself; the caller refuses that case).
+ *   x_hat   = (x - mean) invstd,  z = fma(gamma, x_hat, beta),  y = GELU(z) = z erfc(-z / sqrt 2) / 2; every element-wise
+ *             expression here and in the backward is evaluated in fp64 from the fp32 operands and rounded to fp32 once
+ *   backward: g = dy GELU'(z) with z and x_hat recomputed from x (nothing but x, mean, invstd is kept),
+ *             gsums = [sum_i g_ij (c), sum_i g_ij x_hat_ij (c)] in fp64: 2 c doubles (dbeta and dgamma, mergeable like stats),
+ *             dx = gamma invstd (g - gsums[j] / n - x_hat gsums[c + j] / n), gsums and n = count[0] (fp64) read on the device:
+ *             under SyncBN the caller passes the merged ones.  A non-finite dy reaches dx.
+ * Summation order: block b of the partition owns the rows [b rows_per_block, (b + 1) rows_per_block); inside a block a lane
+ * adds its rows by ascending index and the block's row slots are added by ascending slot; the block partials (in ws) are
+ * added by a second launch as t = p[0]; t += p[1]; ... by ascending block index.  No float atomics: equal inputs give equal
+ * bits, on every device.  The partition query is host only and a function of (m, c) alone.
+ * Pooling maximum: out[j] = max over the rows seg_start[j] .. seg_start[j + 1] - 1 of y (runs are not empty), bit for bit
+ * what the segment maximum above gives with scale 1, shift 0 and no activation; arg[j] (int32) = the FIRST row, ascending,
+ * that holds the maximum (-1 for a run of NaNs only).  Backward over the n fine rows, every element written exactly once:
+ *   dy[i] = arg[cluster[i]] == i ? dout[cluster[i]] : 0   per channel (no zero fill, no atomics).
+ * Status codes, checked before any launch; m = 0 (n = 0) returns CDSEG_OK without one:
+ *   CDSEG_ERR_UNSUPPORTED  c not a multiple of 16 in [16, 512]; 2^31 rows or more (pooling maximum: arg is int32).
+ *   CDSEG_ERR_ARG          a NULL operand; an fp32 / int32 (rows, c) tensor or per-channel vector that is not 16-byte aligned
+ *                          (every lane moves 16 bytes); a row stride below c or not a multiple of 4; an fp64 buffer not
+ *                          8-byte aligned; m < 0; eps < 0; momentum outside [0, 1]; ws not 16-byte aligned.
+ *   CDSEG_ERR_WORKSPACE    ws NULL or ws_bytes below the query. */
+int cdseg_bn_partition(long m, int c, long* rows_per_block, int* blocks);
+size_t cdseg_bn_ws_bytes(long m, int c);
+int cdseg_bn_stats(const float* x, int ldx, long m, int c, double* stats, void* ws, size_t ws_bytes, void* stream);
+int cdseg_bn_finish(const double* stats, int c, double eps, double momentum, float* mean, float* invstd, float* running_mean,
+                    float* running_var, void* stream);
+int cdseg_bn_gelu_fwd(const float* x, int ldx, long m, int c, const float* mean, const float* invstd, const float* gamma,
+                      const float* beta, float* y, int ldy, void* stream);
+int cdseg_bn_gelu_bwd_sums(const float* x, int ldx, const float* dy, int lddy, long m, int c, const float* mean,
+                           const float* invstd, const float* gamma, const float* beta, double* gsums, void* ws, size_t ws_bytes,
+                           void* stream);
+int cdseg_bn_gelu_bwd_dx(const float* x, int ldx, const float* dy, int lddy, long m, int c, const float* mean, const float* invstd,
+                         const float* gamma, const float* beta, const double* gsums, const double* count, float* dx, int lddx,
+                         void* stream);
+int cdseg_segment_max_arg(const float* y, int ldy, const int32_t* seg_start, long m, int c, float* out, int ldo, int32_t* arg,
+                          int lda, void* stream);
+int cdseg_segment_max_bwd(const float* dout, int lddo, const int32_t* arg, int lda, const int32_t* cluster, long n, int c,
+                          float* dy, int lddy, void* stream);
+
 /* ------------------------------------------------------------------ fused optimizer step (csrc/optim.hip)
  * ref: engines/train.py:216-271 (run_step: scaler.unscale_, clip_grad_norm_, scaler.step(optimizer)) on torch.optim.AdamW.
  * One tensor table describes the parameters; a work list cuts them into chunks of at most CDSEG_OPT_CHUNK elements (a

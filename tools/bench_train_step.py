@@ -3,9 +3,10 @@
 with a 16-bit attention core, or under AMP (16-bit attention core, Linears and sparse convs; train_precision), on the HIP kernels (cdsegnet_amd/train_graph.py).  Not a BASELINE metric - the reference publishes no training throughput -
 a first number for the training row of SURVEY 8(f4).
 usage: python tools/bench_train_step.py [scenes=1] [points=120000] [steps=4] [dataset=scannet|scannet200|nuscenes]
-       [train_precision=fp32|fp16-attn|bf16-attn|fp16-amp|bf16-amp] [det] [fused] [fusedopt] [shadow]
+       [train_precision=fp32|fp16-attn|bf16-attn|fp16-amp|bf16-amp] [det] [fused] [fusednorm] [fusedopt] [shadow]
 A trailing `det` sets train_deterministic = True (fixed-order gradient reductions: bit-reproducible steps), a trailing `fused`
-sets train_loss = "fused" (cross entropy + Lovasz on the HIP loss kernels instead of the torch criteria), a trailing `fusedopt`
+sets train_loss = "fused" (cross entropy + Lovasz on the HIP loss kernels instead of the torch criteria), a trailing `fusednorm` sets train_norm =
+"fused" (train-mode BatchNorm + GELU and the pooling maximum on the kernels of csrc/norm.hip), a trailing `fusedopt`
 takes cdsegnet_amd.optim.FusedAdamW in torch.optim.AdamW's place, and `shadow` (with `fusedopt` under an AMP precision) lets it
 keep the 16-bit weight copies the forward multiplies with."""
 import os, sys, time
@@ -25,6 +26,7 @@ dataset = sys.argv[4] if len(sys.argv) > 4 else "scannet"
 train_precision = sys.argv[5] if len(sys.argv) > 5 else "fp32"
 deterministic = "det" in sys.argv[6:]
 fused = "fused" in sys.argv[6:]
+fusednorm = "fusednorm" in sys.argv[6:]
 fusedopt = "fusedopt" in sys.argv[6:]
 shadow = "shadow" in sys.argv[6:]
 if shadow and not (fusedopt and train_precision.endswith("-amp")):
@@ -41,6 +43,8 @@ model.train_precision = train_precision
 model.train_deterministic = deterministic
 if fused:
     model.train_loss = "fused"
+if fusednorm:
+    model.train_norm = "fused"
 sc = synth.collate([(synth.lidar_scene(i, points) if dataset == "nuscenes" else synth.room_scene(i, points)) for i in range(scenes)])
 inp = {k: torch.as_tensor(sc[k]).to(dev) for k in ("coord", "grid_coord", "feat", "offset")}
 inp["segment"] = (torch.as_tensor(np.asarray(sc["segment"]).astype(np.int64)) % cfg["num_classes"]).to(dev)
@@ -71,6 +75,7 @@ for it in range(steps + 1):
     if it:
         times.append((t1 - t0, t2 - t1, t3 - t2))
 t = np.median(np.array(times), axis=0) * 1e3
-print(f"training step, {dataset}, full width, {train_precision}{', deterministic' if deterministic else ''}{', fused loss' if fused else ''}{', FusedAdamW' if fusedopt else ''}{' + 16-bit weight copies' if shadow else ''}, {scenes} scene(s), {n} points: forward {t[0]:.1f} ms, backward {t[1]:.1f} ms, "
-      f"AdamW {t[2]:.1f} ms = {t.sum():.1f} ms/step = {n / t.sum() * 1e3 / 1e6:.2f} M points/s; peak memory "
+tot = np.array(times).sum(1) * 1e3  # run-to-run spread of the whole step
+print(f"training step, {dataset}, full width, {train_precision}{', deterministic' if deterministic else ''}{', fused loss' if fused else ''}{', fused norm' if fusednorm else ''}{', FusedAdamW' if fusedopt else ''}{' + 16-bit weight copies' if shadow else ''}, {scenes} scene(s), {n} points: forward {t[0]:.1f} ms, backward {t[1]:.1f} ms, "
+      f"AdamW {t[2]:.1f} ms = {t.sum():.1f} ms/step (steps {tot.min():.1f} - {tot.max():.1f}) = {n / t.sum() * 1e3 / 1e6:.2f} M points/s; peak memory "
       f"{torch.cuda.max_memory_allocated() / 2**30:.1f} GiB; loss over the steps {[round(v, 4) for v in losses]}")
