@@ -70,6 +70,27 @@ class BlockIO(Structure):
     ]
 
 
+class TrainBlockDesc(Structure):
+    _fields_ = [
+        ("channels", c_int), ("heads", c_int), ("hidden", c_int),
+        ("attn_scale", c_float), ("eps_cpe", c_float), ("eps_norm1", c_float), ("eps_norm2", c_float),
+        ("mm_dtype", c_int), ("attn_dtype", c_int), ("deterministic", c_int),
+        ("param", c_void_p * 18), ("shadow16", c_void_p * 6),
+        ("derived", c_void_p), ("derived_bytes", c_size_t),
+    ]
+
+
+class TrainBlockIO(Structure):
+    _fields_ = [
+        ("n", c_long), ("x_in", c_void_p), ("x_conv", c_void_p), ("t_rows", c_void_p), ("scene_offs", c_void_p),
+        ("num_scenes", c_int), ("mask1", c_void_p), ("mask2", c_void_p),
+        ("nbr", c_void_p), ("gidx", c_void_p), ("widx", c_void_p), ("patch_start", c_void_p),
+        ("num_patches", c_int), ("max_len", c_int), ("num_slots", c_long),
+        ("tape", c_void_p), ("tape_bytes", c_size_t), ("scratch", c_void_p), ("scratch_bytes", c_size_t),
+        ("x_out", c_void_p),
+    ]
+
+
 class PlanSpec(Structure):
     _fields_ = [
         ("nlev", c_int), ("cum", c_int * 9), ("ncurve", c_int), ("curve_rows", c_int * 3),
@@ -282,6 +303,19 @@ SIGNATURES = {
     "cdseg_subm_conv3_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p, c_int, c_float, c_int,
                                      c_void_p]),
     "cdseg_split16": (c_int, [c_void_p, c_int, c_long, c_int, c_void_p, c_void_p, c_int, c_float, c_void_p]),
+    "cdseg_train_block_bytes": (c_int, [POINTER(TrainBlockDesc), c_long, c_long, POINTER(c_size_t), POINTER(c_size_t),
+                                        POINTER(c_size_t), POINTER(c_size_t)]),
+    "cdseg_train_block_grad_offsets": (c_int, [POINTER(TrainBlockDesc), POINTER(c_size_t)]),
+    "cdseg_train_block_prepare": (c_int, [POINTER(TrainBlockDesc), c_void_p]),
+    "cdseg_train_block_forward": (c_int, [POINTER(TrainBlockDesc), POINTER(TrainBlockIO), c_void_p]),
+    "cdseg_train_block_backward": (c_int, [POINTER(TrainBlockDesc), POINTER(TrainBlockIO), c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p]),
+    "cdseg_residual": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_long, c_int, c_void_p]),
+    "cdseg_scale_cast": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_void_p]),
+    "cdseg_add_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_long,
+                                    c_int, c_void_p]),
+    "cdseg_gelu_fwd": (c_int, [c_void_p, c_void_p, c_int, c_long, c_void_p]),
+    "cdseg_gelu_bwd_cast": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p]),
 }
 
 _libs = {}

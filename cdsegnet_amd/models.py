@@ -444,6 +444,11 @@ class DefaultSegmentorV2(nn.Module):
         # nn.SyncBatchNorm modules - convert_sync_batchnorm, cfg.sync_bn - get statistics over all ranks of their process
         # group); read at every forward(), anything else raises ValueError there; not part of the state_dict
         self.train_norm = "torch"
+        # every Block of the training forward: "autograd" (default: ~20 autograd nodes over the library's kernels with torch
+        # device ops between them) | "native": ONE autograd node per Block whose forward and backward are one library call
+        # each (csrc/trainblock.hip: all launches issued from C++, the torch glue as HIP row kernels); read at every
+        # forward(), anything else raises ValueError there; not part of the state_dict
+        self.train_block = "autograd"
         self._lanes = {}
         self.noise_source = "torch_cpu"  # "torch_cpu" replays the reference's CPU-generator draws | "device"
         # noise_level jitter: "torch_cpu" = the CPU-run reference's draw order (golden vectors) | "device" = device

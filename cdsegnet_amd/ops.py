@@ -1304,6 +1304,197 @@ def segment_sum(src, seg_start, m):
     return out
 
 
+# ------------------------------------------------------------------ native training Block (csrc/trainblock.hip)
+TB_PARAMS = 18                      # parameter tensors of a Block, in nn.Module order (include/cdseg.h CDSEG_TB_*)
+TB_MATRICES = (0, 2, 8, 10, 14, 16)  # conv, cpe Linear, qkv, proj, fc1, fc2: the six that have 16-bit / transposed forms
+
+
+class TrainBlock:
+    """One Block's descriptor for the native training executor: the ctypes struct, everything it points to (kept alive here),
+    the library build its 16-bit tensors belong to and the persistent derived-weights buffer."""
+
+    def __init__(self, params, heads, attn_scale, eps, mm_variant, attn_variant, deterministic, shadows=None):
+        params = list(params)
+        if len(params) != TB_PARAMS:
+            raise _lib.CdsegError(f"a Block has {TB_PARAMS} parameter tensors, got {len(params)}")
+        _need_gpu(*params)
+        for p in params:
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise _lib.CdsegError("train_block: parameters are contiguous float32 tensors")
+        if mm_variant is not None and attn_variant is not None and mm_variant != attn_variant:
+            raise _lib.CdsegError("train_block: one 16-bit type per Block")
+        self.variant = mm_variant or attn_variant  # the build whose 16-bit type the Block uses (None: exact fp32)
+        self.mm_lp, self.attn_lp, self.deterministic = mm_variant is not None, attn_variant is not None, bool(deterministic)
+        self.params = params
+        self.shadows = [None] * len(TB_MATRICES) if shadows is None else list(shadows)
+        self.channels, self.hidden, self.heads = params[2].shape[0], params[14].shape[0], int(heads)
+        d = self.desc = _lib.TrainBlockDesc()
+        d.channels, d.heads, d.hidden = self.channels, self.heads, self.hidden
+        d.attn_scale = float(attn_scale)
+        d.eps_cpe, d.eps_norm1, d.eps_norm2 = (float(e) for e in eps)
+        d.mm_dtype, d.attn_dtype, d.deterministic = (BF16 if self.mm_lp else F32), (BF16 if self.attn_lp else F32), int(self.deterministic)
+        for i, p in enumerate(params):
+            d.param[i] = p.data_ptr()
+        for i, s in enumerate(self.shadows):
+            if s is not None and (not self.mm_lp or s.dtype != LP_DTYPES[self.variant] or not s.is_contiguous()):
+                raise _lib.CdsegError("train_block: a shadow copy is a contiguous tensor of the Block's 16-bit type")
+            d.shadow16[i] = None if s is None else s.data_ptr()
+        self.ref = ctypes.byref(d)
+        self.io = _lib.TrainBlockIO()
+        self.io_ref = ctypes.byref(self.io)
+        self.derived_bytes = train_block_bytes(self, 0, 0)[2]
+        self.derived = torch.empty(self.derived_bytes, dtype=torch.uint8, device=params[0].device)
+        d.derived, d.derived_bytes = self.derived.data_ptr(), self.derived_bytes
+        offs = (ctypes.c_size_t * TB_PARAMS)()
+        check(self.lib().cdseg_train_block_grad_offsets(self.ref, offs), "train_block_grad_offsets")
+        self.grad_offsets = [int(o) for o in offs]
+
+    def lib(self):
+        return _lib.load(self.variant)
+
+
+def train_block_bytes(tb, n, slots):
+    """(tape, scratch, derived, grads) bytes of a Block for n rows and `slots` padded attention slots: host code, a function of
+    the shape only, each a multiple of 256."""
+    out = [ctypes.c_size_t(0) for _ in range(4)]
+    check(tb.lib().cdseg_train_block_bytes(tb.ref, int(n), int(slots), *[ctypes.byref(o) for o in out]), "train_block_bytes")
+    return tuple(int(o.value) for o in out)
+
+
+def train_block_grad_views(tb, slab):
+    """The 18 parameter gradients as fp32 views of the gradient slab (uint8), in parameter order, shaped like the parameters."""
+    views = []
+    for p, off in zip(tb.params, tb.grad_offsets):
+        views.append(slab[off:off + 4 * p.numel()].view(torch.float32).view(p.shape))
+    return views
+
+
+def train_block_derived_views(tb):
+    """The derived-weights buffer as tensors, the layout of csrc/trainblock.hip restated (every piece starts at a multiple of
+    256 bytes, in the order of TB_MATRICES): [(transposed weight, 16-bit forward weight or None)] - (in, out) for a Linear,
+    (cin, 27 * cout) for the conv's data-gradient kernel; 16-bit tensors when the products are 16 bit."""
+    dtype = LP_DTYPES[tb.variant] if tb.mm_lp else torch.float32
+    esz = 2 if tb.mm_lp else 4
+    off, out = 0, []
+
+    def take(shape, dt_, e):
+        nonlocal off
+        off = (off + 255) // 256 * 256
+        nbytes = e * shape[0] * shape[1]
+        v = tb.derived[off:off + nbytes].view(dt_).view(shape)
+        off += nbytes
+        return v
+
+    for i in TB_MATRICES:
+        w = tb.params[i]
+        o, k = w.shape[0], w.numel() // w.shape[0]
+        t = take((k // 27, 27 * o) if w.dim() == 5 else (k, o), dtype, esz)
+        out.append((t, take((o, k), dtype, 2) if tb.mm_lp else None))
+    return out
+
+
+def train_block_prepare(tb):
+    """Fill the Block's derived-weights buffer (transposed Linear weights, the conv's data-gradient kernel, 16-bit forms): one
+    launch; once per weight version."""
+    check(tb.lib().cdseg_train_block_prepare(tb.ref, _stream()), "train_block_prepare")
+
+
+def _train_block_io(tb, n, x_in, x_conv, t_rows, scene_offs, mask1, mask2, nbr, gidx, widx, patch_start, patch_start_host, tape,
+                    scratch, x_out):
+    _need_gpu(x_in, x_conv, tape, scratch)
+    for t in (x_in, x_conv, x_out, t_rows, mask1, mask2):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise _lib.CdsegError("train_block: activations, masks and timestep rows are contiguous float32 tensors")
+    ps = [int(v) for v in patch_start_host]
+    io = tb.io
+    io.n = int(n)
+    io.x_in, io.x_conv, io.t_rows, io.scene_offs = x_in.data_ptr(), x_conv.data_ptr(), _dp(t_rows), _dp(scene_offs)
+    io.num_scenes = 0 if t_rows is None else int(t_rows.shape[0])
+    io.mask1, io.mask2 = _dp(mask1), _dp(mask2)
+    io.nbr, io.gidx, io.widx, io.patch_start = nbr.data_ptr(), gidx.data_ptr(), widx.data_ptr(), patch_start.data_ptr()
+    io.num_patches = len(ps) - 1
+    io.max_len = max((ps[i + 1] - ps[i] for i in range(len(ps) - 1)), default=0)
+    io.num_slots = ps[-1]
+    io.tape, io.tape_bytes = tape.data_ptr(), tape.numel()
+    io.scratch, io.scratch_bytes = scratch.data_ptr(), scratch.numel()
+    io.x_out = _dp(x_out)
+    return tb.io_ref
+
+
+def train_block_forward(tb, n, x_in, x_conv, t_rows, scene_offs, mask1, mask2, nbr, gidx, widx, patch_start, patch_start_host,
+                        tape, scratch, x_out):
+    """One Block of the training forward on the native executor: every launch issued by the library, one host call.  x_conv is
+    what the CPE conv reads (may be x_in); t_rows (B, C) with scene_offs (B + 1) int32: the per-scene timestep rows; mask1 /
+    mask2 (n): stochastic-depth row masks already divided by the keep probability; tape (uint8) keeps what the backward reads."""
+    ref = _train_block_io(tb, n, x_in, x_conv, t_rows, scene_offs, mask1, mask2, nbr, gidx, widx, patch_start, patch_start_host,
+                          tape, scratch, x_out)
+    check(tb.lib().cdseg_train_block_forward(tb.ref, ref, _stream()), "train_block_forward")
+    return x_out
+
+
+def train_block_backward(tb, n, x_in, x_conv, t_rows, scene_offs, mask1, mask2, nbr, gidx, widx, patch_start, patch_start_host,
+                         tape, scratch, x_out, dy, dx_in, dx_conv, dt_rows, slab):
+    """Backward of `train_block_forward` (same arguments, the forward's tape): dx_in, dx_conv (None when x_conv is x_in: the conv's
+    data gradient is added into dx_in), dt_rows (with t_rows) and the gradient slab (zeroed here by one memset;
+    `train_block_grad_views`)."""
+    ref = _train_block_io(tb, n, x_in, x_conv, t_rows, scene_offs, mask1, mask2, nbr, gidx, widx, patch_start, patch_start_host,
+                          tape, scratch, x_out)
+    _need_gpu(dy, dx_in, slab)
+    for t in (dy, dx_in, dx_conv, dt_rows):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise _lib.CdsegError("train_block: gradients are contiguous float32 tensors")
+    check(tb.lib().cdseg_train_block_backward(tb.ref, ref, _ptr(dy), _ptr(dx_in), _ptr(dx_conv), _ptr(dt_rows), _ptr(slab),
+                                              _stream()), "train_block_backward")
+
+
+def _row_out(like, lp_variant):
+    return torch.empty(like.shape, dtype=torch.float32 if lp_variant is None else LP_DTYPES[lp_variant], device=like.device)
+
+
+def residual(x, a=None, mask=None, t_rows=None, scene_offs=None, out=None):
+    """out = x + mask[row] * a + t_rows[scene(row)] (fp32; multiply and add rounded separately: bit-equal to torch)."""
+    _need_gpu(x)
+    out = torch.empty_like(x) if out is None else out
+    check(_lib.load().cdseg_residual(_ptr(x), _ptr(a), _ptr(mask), _ptr(t_rows), _ptr(scene_offs),
+                                     0 if t_rows is None else t_rows.shape[0], _ptr(out), x.shape[0], x.shape[1], _stream()), "residual")
+    return out
+
+
+def scale_cast(dy, mask=None, variant=None):
+    """cast(mask[row] * dy) WITHOUT saturation: fp32 (variant None) or the 16-bit type of build `variant` (torch's `.to`)."""
+    _need_gpu(dy)
+    out = _row_out(dy, variant)
+    check(_lib.load(variant).cdseg_scale_cast(_ptr(dy), _ptr(mask), _ptr(out), dt(out) if variant is None else BF16, dy.shape[0],
+                                              dy.shape[1], _stream()), "scale_cast")
+    return out
+
+
+def add_layernorm(x, a, mask, gamma, beta, eps=1e-5, variant=None):
+    """(x1, h): x1 = x + mask[row] * a, h = LayerNorm(x1) in fp32 or the 16-bit type of build `variant`; one pass."""
+    _need_gpu(x, a)
+    x1, h = torch.empty_like(x), _row_out(x, variant)
+    check(_lib.load(variant).cdseg_add_layernorm(_ptr(x), _ptr(a), _ptr(mask), _ptr(gamma), _ptr(beta), float(eps), _ptr(x1), _ptr(h),
+                                                 F32 if variant is None else BF16, x.shape[0], x.shape[1], _stream()), "add_layernorm")
+    return x1, h
+
+
+def gelu_fwd(u, variant=None):
+    """GELU(u) (erf form) in fp32 or the 16-bit type of build `variant`."""
+    _need_gpu(u)
+    g = _row_out(u, variant)
+    check(_lib.load(variant).cdseg_gelu_fwd(_ptr(u), _ptr(g), F32 if variant is None else BF16, u.numel(), _stream()), "gelu_fwd")
+    return g
+
+
+def gelu_bwd_cast(u, dg, variant=None):
+    """dg * GELU'(u) in fp32 or, without saturation, the 16-bit type of build `variant`."""
+    _need_gpu(u, dg)
+    du = _row_out(u, variant)
+    check(_lib.load(variant).cdseg_gelu_bwd_cast(_ptr(u), _ptr(dg), _ptr(du), F32 if variant is None else BF16, u.numel(), _stream()),
+          "gelu_bwd_cast")
+    return du
+
+
 # ------------------------------------------------------------------ train-mode BatchNorm + GELU, pooling maximum (csrc/norm.hip)
 BN_WIDTHS = range(16, 513, 16)  # channel counts of the kernels of csrc/norm.hip
 

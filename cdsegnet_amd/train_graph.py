@@ -69,6 +69,13 @@ all_gather of the (2 c + 1) fp64 buffer in the forward and one of the (2 c) sums
 mode such modules normalise with this rank's rows only, and say so once.  Eval mode, widths that are no multiple of 16 up to
 512, momentum = None and modules without affine parameters take the torch path in either mode; a CPU tensor in the fused mode
 raises like every other op of the library.  These sites are fp32 in every train_precision.
+
+Native Blocks (`model.train_block = "native"`, default "autograd"; read at every forward): every Block of both branches is ONE
+autograd node, `_NativeBlock`, whose forward and backward are one library call each (csrc/trainblock.hip: ops.train_block_forward /
+_backward): the same products through the same entry points, the torch glue between them (residual adds, stochastic-depth
+multiplies, GELU, the timestep rows, gradient zero fills, weight transposes, the fp32 round trips of the AMP path) as HIP row
+kernels, the derived weights of a Block made once per weight version (ops.train_block_prepare).  The CrossBlock, pooling,
+unpooling, stems, heads and criteria are what they are in the default mode, which is unchanged bit for bit.
 """
 import warnings
 
@@ -451,6 +458,78 @@ class _SceneRows(torch.autograd.Function):
         return torch.stack([dy[o[b]:o[b + 1]].sum(0) for b in range(len(o) - 1)]), None, None
 
 
+TRAIN_BLOCKS = ("autograd", "native")
+
+
+def resolve_train_block(model):
+    """model.train_block: "autograd" (default) or "native" (`_NativeBlock`); anything else raises."""
+    tb = getattr(model, "train_block", "autograd")
+    if tb not in TRAIN_BLOCKS:
+        raise ValueError(f"train_block must be one of {sorted(TRAIN_BLOCKS)}, not {tb!r}")
+    return tb
+
+
+def block_parameters(mod):
+    """The 18 parameter tensors of a Block in nn.Module order (include/cdseg.h CDSEG_TB_*)."""
+    mods = (mod.cpe[0], mod.cpe[1], mod.cpe[2], mod.norm1[0], mod.attn.qkv, mod.attn.proj, mod.norm2[0], mod.mlp[0].fc1, mod.mlp[0].fc2)
+    out = []
+    for m in mods:
+        if m.bias is None:
+            raise ValueError("train_block = 'native' needs the bias of every Linear / conv of a Block (qkv_bias = True)")
+        out += [m.weight, m.bias]
+    return out
+
+
+class _NativeBlock(torch.autograd.Function):
+    """One whole Block (ref: ptv3.py:399-428) as ONE autograd node (`model.train_block = "native"`): the forward is one library
+    call that keeps what the backward reads in a tape, the backward is one library call that writes dx_in, dx_conv, dt_rows and
+    a gradient slab whose 18 views are returned in parameter order (csrc/trainblock.hip).  The parameters, the optimizer's
+    16-bit copies in use, the tape and the index tensors are saved with save_for_backward: a weight that changes in place between
+    forward and backward (an optimizer step) is an autograd error, as with the per-op nodes."""
+
+    @staticmethod
+    def forward(ctx, tb, idx, x_in, x_conv, t_rows, mask1, mask2, *weights):
+        scene_offs, nbr, gidx, widx, patch_start, psh = idx
+        x_in = _c(x_in.float())
+        xc = x_in if x_conv is None else _c(x_conv.float())
+        t_rows = None if t_rows is None else _c(t_rows.float())
+        n = x_in.shape[0]
+        tape_b, scratch_b, _, grads_b = ops.train_block_bytes(tb, n, psh[-1])
+        dev = x_in.device
+        tape = torch.empty(tape_b, dtype=torch.uint8, device=dev)
+        scratch = torch.empty(scratch_b, dtype=torch.uint8, device=dev)
+        x_out = torch.empty_like(x_in)
+        ops.train_block_forward(tb, n, x_in, xc, t_rows, scene_offs, mask1, mask2, nbr, gidx, widx, patch_start, psh, tape, scratch,
+                                x_out)
+        opt = [t for t in (None if x_conv is None else xc, t_rows, mask1, mask2) if t is not None]
+        ctx.save_for_backward(x_in, tape, scene_offs, nbr, gidx, widx, patch_start, *opt, *weights)
+        ctx.meta = (tb, list(psh), x_conv is not None, t_rows is not None, mask1 is not None, mask2 is not None, scratch_b, grads_b, len(weights))
+        return x_out
+
+    @staticmethod
+    def backward(ctx, dy):
+        tb, psh, has_xc, has_t, has_m1, has_m2, scratch_b, grads_b, nw = ctx.meta
+        saved = list(ctx.saved_tensors)
+        x_in, tape, scene_offs, nbr, gidx, widx, patch_start = saved[:7]
+        rest = iter(saved[7:])
+        xc = next(rest) if has_xc else x_in
+        t_rows = next(rest) if has_t else None
+        mask1 = next(rest) if has_m1 else None
+        mask2 = next(rest) if has_m2 else None
+        n = x_in.shape[0]
+        dev = x_in.device
+        dy = _c(dy.float())
+        dx_in = torch.empty_like(x_in)
+        dx_conv = torch.empty_like(x_in) if has_xc else None
+        dt_rows = torch.empty_like(t_rows) if has_t else None
+        slab = torch.empty(grads_b, dtype=torch.uint8, device=dev)
+        scratch = torch.empty(scratch_b, dtype=torch.uint8, device=dev)
+        ops.train_block_backward(tb, n, x_in, xc, t_rows, scene_offs, mask1, mask2, nbr, gidx, widx, patch_start, psh, tape, scratch,
+                                 None, dy, dx_in, dx_conv, dt_rows, slab)
+        grads = ops.train_block_grad_views(tb, slab)
+        return (None, None, dx_in, dx_conv, dt_rows, None, None, *grads, *([None] * (nw - len(grads))))  # (the 16-bit copies: no gradient)
+
+
 def _swish(x):  # ptv3.py:30-31
     return x * torch.sigmoid(x)
 
@@ -617,6 +696,8 @@ class TrainGraph:
         self.fused_criteria = None  # losses.FusedCriteria, built when model.train_loss first says "fused"
         self.train_loss = "torch"   # from model.train_loss at every forward
         self.train_norm = "torch"   # from model.train_norm at every forward
+        self.train_block = "autograd"  # from model.train_block at every forward
+        self._native = {}  # id(Block) -> [Block, static key, weight versions, ops.TrainBlock] (train_block "native")
 
     # ---------------------------------------------------------------------------------------- pieces
     def _mask(self, st, name, rate, masks):
@@ -650,8 +731,53 @@ class TrainGraph:
     def _mlp(self, h, mlp):
         return self._lin(F.gelu(self._lin(h, mlp.fc1)), mlp.fc2)
 
+    def _native_desc(self, mod):
+        """The Block's descriptor for the native executor, with its derived weights current: rebuilt when the mode, a
+        parameter's storage or the set of 16-bit optimizer copies changes; `prepare` (one launch) once per weight version."""
+        params = block_parameters(mod)
+        t16 = ops.LP_DTYPES[self.mm_variant] if self.mm_variant is not None else None
+        shadows = [None if t16 is None else _shadow16(params[i], t16) for i in ops.TB_MATRICES]
+        shadows = [s if s is not None and s.is_contiguous() and s.data_ptr() % 16 == 0 else None for s in shadows]
+        att = mod.attn
+        static = (self.mm_variant, self.attn_variant, self.det, att.num_heads, float(att.scale), tuple(p.data_ptr() for p in params),
+                  tuple(None if s is None else s.data_ptr() for s in shadows))
+        versions = tuple(p._version for p in params)
+        ent = self._native.get(id(mod))
+        if ent is None or ent[0] is not mod or ent[1] != static:
+            eps = (float(mod.cpe[2].eps), float(mod.norm1[0].eps), float(mod.norm2[0].eps))
+            tb = ops.TrainBlock([p.detach() for p in params], att.num_heads, att.scale, eps, self.mm_variant, self.attn_variant,
+                                self.det, shadows)
+            ent = self._native[id(mod)] = [mod, static, None, tb]
+        if ent[2] != versions:
+            ops.train_block_prepare(ent[3])
+            ent[2] = versions
+        return ent[3], params, [s for s in shadows if s is not None]
+
+    def _block_native(self, st, mod, name, t_scene, masks):
+        """`_block` as one `_NativeBlock` node; the timestep Linear on B rows stays torch (its gradient arrives as dt_rows)."""
+        lv = st.level
+        x = st.x
+        xconv, st.conv = st.conv, None
+        t_rows = None
+        if t_scene is not None and hasattr(mod, "t_mlp"):
+            t_rows = F.linear(t_scene, mod.t_mlp.weight, mod.t_mlp.bias)
+        att = mod.attn
+        gidx, widx = lv.slots(st.curves[att.order_index], att.patch_size, att.enable_flash)
+        pad = lv.pad(att.patch_size, att.enable_flash)
+        scene_offs, patch_start = pad[2], pad[4]
+        psh = lv.pad_host(att.patch_size, att.enable_flash)[3].tolist()
+        m1 = self._mask(st, name + ".drop_path.0", mod.drop_prob, masks)
+        m2 = self._mask(st, name + ".drop_path.0", mod.drop_prob, masks)
+        m1, m2 = (None if m is None else _c(m.reshape(-1)) for m in (m1, m2))
+        tb, params, shadows = self._native_desc(mod)
+        idx = (scene_offs, lv.nbr(mod.cpe[0].kernel_size, True), gidx, widx, patch_start, psh)
+        st.x = _NativeBlock.apply(tb, idx, x, xconv, t_rows, m1, m2, *params, *shadows)
+        return st
+
     def _block(self, st, mod, name, t_scene, masks):
         """ref: ptv3.py:399-428."""
+        if self.train_block == "native":
+            return self._block_native(st, mod, name, t_scene, masks)
         lv = st.level
         x = st.x
         xconv, st.conv = (x if st.conv is None else st.conv), None
@@ -768,6 +894,7 @@ class TrainGraph:
         self.det = resolve_deterministic(self.model)
         self.train_loss = resolve_train_loss(self.model)
         self.train_norm = resolve_train_norm(self.model)
+        self.train_block = resolve_train_block(self.model)
         if feat_is_cuda(input_dict):
             with torch.autocast(device_type="cuda", enabled=False):
                 return self._forward(input_dict, draws)

@@ -880,6 +880,107 @@ int cdseg_adamw_step(const cdseg_opt_tensor* tensors_host, int count, const cdse
                      const int32_t* chunks_dev, long nchunks, const float* grad_scale, const float* found_inf,
                      const float* clip_coef, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ native training Block (csrc/trainblock.hip)
+ * One PTv3 Block (ref: ptv3.py:399-428) of the TRAINING step in two host calls: the forward keeps what the backward reads
+ * in a tape, the backward writes the input gradients and the 18 parameter gradients.  The launches are those of the
+ * autograd graph (cdsegnet_amd/train_graph.py) through the same entry points - the dense and gathered GEMM, LayerNorm and its
+ * backward, the attention core and its backward, the Linear / conv weight gradients - plus the row kernels below for what that
+ * graph leaves to torch (residual adds, stochastic-depth masks, GELU, the per-scene timestep rows and their column sums, casts).
+ *
+ *   x0 = x_in + LN_cpe(Linear(SubMConv3d(x_conv))) [+ t_rows[scene(row)]]
+ *   x1 = x0 + mask1[row] * proj(attention(qkv(LN1(x0))))
+ *   x_out = x1 + mask2[row] * fc2(GELU(fc1(LN2(x1))))
+ *
+ * mm_dtype CDSEG_BF16: every Linear / conv operand is rounded ONCE to the build's 16-bit type (saturating in the half build),
+ * sums and the residual stream are fp32, every gradient that becomes an operand is cast WITHOUT saturation (an inf stays an
+ * inf for a GradScaler).  attn_dtype CDSEG_BF16: the attention core on 16-bit q / k / v, fp32 dq / dk / dv.
+ * param[]: the 18 fp32 parameter tensors in the order of the CDSEG_TB_* indices; weights are (out, in) row-major, the conv
+ * kernel (C, 27, C).  shadow16[]: optional current 16-bit copies of the six matrices (conv, cpe Linear, qkv, proj, fc1, fc2; NULL:
+ * cdseg_train_block_prepare makes them).  derived: buffer of the size cdseg_train_block_bytes reports, filled by
+ * cdseg_train_block_prepare in ONE launch - the six transposed Linear weights, the mirrored, transposed conv kernel
+ * W'[ci][o][co] = W[co][26-o][ci], in mm_dtype, and with mm_dtype CDSEG_BF16 the 16-bit forward weights where no shadow copy is
+ * given.  Call it again whenever a weight changes.
+ * cdseg_train_block_bytes: host only, a function of the shape alone; every size is a multiple of 256.  The gradient slab holds the
+ * 18 gradients (fp32, parameter order) at the byte offsets cdseg_train_block_grad_offsets reports (each a multiple of 256); the
+ * backward zeroes it with one memset.  slots = patch_start_host[num_patches].
+ * Checked before the first launch (CDSEG_ERR_ARG): a NULL descriptor / io / required pointer, channels or hidden not a multiple
+ * of 16, channels != 16 * heads, max_len > CDSEG_MAX_PATCH, a pointer that is not 16-byte aligned, a tape or scratch below
+ * the reported size, a dtype other than CDSEG_F32 / CDSEG_BF16.  n <= 0: CDSEG_OK, nothing launched. */
+#define CDSEG_TB_CONV_W 0
+#define CDSEG_TB_CONV_B 1
+#define CDSEG_TB_CPE_W 2
+#define CDSEG_TB_CPE_B 3
+#define CDSEG_TB_CPE_LN_G 4
+#define CDSEG_TB_CPE_LN_B 5
+#define CDSEG_TB_NORM1_G 6
+#define CDSEG_TB_NORM1_B 7
+#define CDSEG_TB_QKV_W 8
+#define CDSEG_TB_QKV_B 9
+#define CDSEG_TB_PROJ_W 10
+#define CDSEG_TB_PROJ_B 11
+#define CDSEG_TB_NORM2_G 12
+#define CDSEG_TB_NORM2_B 13
+#define CDSEG_TB_FC1_W 14
+#define CDSEG_TB_FC1_B 15
+#define CDSEG_TB_FC2_W 16
+#define CDSEG_TB_FC2_B 17
+#define CDSEG_TB_PARAMS 18
+typedef struct cdseg_train_block_desc {
+  int channels, heads, hidden;
+  float attn_scale;
+  float eps_cpe, eps_norm1, eps_norm2;
+  int mm_dtype, attn_dtype;
+  int deterministic;       /* parameter gradients through the _det entry points (fixed summation order) */
+  const float* param[18];
+  const void* shadow16[6]; /* conv, cpe Linear, qkv, proj, fc1, fc2: the build's 16-bit type, or NULL */
+  void* derived;
+  size_t derived_bytes;
+} cdseg_train_block_desc;
+typedef struct cdseg_train_block_io {
+  long n;
+  const float* x_in;          /* (n, C) */
+  const float* x_conv;        /* (n, C): what the CPE conv reads; may be x_in */
+  const float* t_rows;        /* (num_scenes, C) or NULL: per-scene timestep rows */
+  const int32_t* scene_offs;  /* (num_scenes + 1) row offsets of the scenes (required with t_rows) */
+  int num_scenes;
+  const float* mask1;         /* (n) or NULL: stochastic-depth row mask of the attention branch, already / keep */
+  const float* mask2;         /* (n) or NULL: of the MLP branch */
+  const int32_t* nbr;         /* (27, n) offset-major kernel map */
+  const int32_t* gidx;
+  const int32_t* widx;
+  const int32_t* patch_start; /* (num_patches + 1) */
+  int num_patches, max_len;
+  long num_slots;             /* patch_start_host[num_patches] */
+  void* tape;
+  size_t tape_bytes;
+  void* scratch;
+  size_t scratch_bytes;
+  float* x_out;               /* (n, C) */
+} cdseg_train_block_io;
+int cdseg_train_block_bytes(const cdseg_train_block_desc* desc, long n, long slots, size_t* tape, size_t* scratch,
+                            size_t* derived, size_t* grads);
+int cdseg_train_block_grad_offsets(const cdseg_train_block_desc* desc, size_t* offsets18_host);
+int cdseg_train_block_prepare(const cdseg_train_block_desc* desc, void* stream);
+int cdseg_train_block_forward(const cdseg_train_block_desc* desc, const cdseg_train_block_io* io, void* stream);
+/* dy (n, C) -> dx_in (n, C), dx_conv (n, C; NULL when io->x_conv == io->x_in: the conv's data gradient is added into dx_in),
+ * dt_rows (num_scenes, C; with io->t_rows), grad_slab.  io: the forward's, tape included. */
+int cdseg_train_block_backward(const cdseg_train_block_desc* desc, const cdseg_train_block_io* io, const float* dy,
+                               float* dx_in, float* dx_conv, float* dt_rows, void* grad_slab, void* stream);
+/* The row kernels of the executor on their own (rows of c fp32 values, c a multiple of 4, contiguous rows, 16-byte aligned
+ * pointers; out_dtype CDSEG_F32 or CDSEG_BF16).  Multiply and add are rounded separately (no contraction).
+ *   residual          out = x + mask[row] * a + t_rows[scene(row)]   (a, mask, t_rows optional; fp32 out; out may be x)
+ *   scale_cast        out = cast(mask[row] * dy), WITHOUT saturation (mask NULL: the plain non-saturating cast)
+ *   add_layernorm     x1 = x + mask[row] * a;  h = LayerNorm(x1) * gamma + beta in out_dtype (saturating), c <= 2048
+ *   gelu_fwd          g = GELU(u) (erf form) in out_dtype (saturating)
+ *   gelu_bwd_cast     du = dg * GELU'(u) in out_dtype WITHOUT saturation */
+int cdseg_residual(const float* x, const float* a, const float* mask, const float* t_rows, const int32_t* scene_offs,
+                   int num_scenes, float* out, long n, int c, void* stream);
+int cdseg_scale_cast(const float* dy, const float* mask, void* out, int out_dtype, long n, int c, void* stream);
+int cdseg_add_layernorm(const float* x, const float* a, const float* mask, const float* gamma, const float* beta, float eps,
+                        float* x1, void* h, int out_dtype, long n, int c, void* stream);
+int cdseg_gelu_fwd(const float* u, void* g, int out_dtype, long count, void* stream);
+int cdseg_gelu_bwd_cast(const float* u, const float* dg, void* du, int out_dtype, long count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,9 @@ parameter gradients, exact fp32) on the HIP kernels, at a real stage shape, next
 usage: python tools/bench_train_block.py [n_points=56000] [heads=4] [cpu=1]
 Prints ms per forward / backward, the algorithmic FLOPs (backward = 2x forward for the Linears and the conv, 2.5x for
 the attention core: recomputed scores + four products) and the CPU time of the same gradients; last, the attention backward
-alone (HIP events around the two kernels) in fp32 and in both 16-bit builds on the same patch tables."""
+alone (HIP events around the two kernels) in fp32 and in both 16-bit builds on the same patch tables; and, last, the Block of the
+training graph itself (cdsegnet_amd/train_graph.py `TrainGraph._block`) in its two modes - the autograd Block and the native
+Block (train_block = "native": one library call each way) - forward and backward between HIP events, fp32 and fp16-amp."""
 import os, sys, time
 import numpy as np
 import torch
@@ -138,3 +140,54 @@ for variant in (None, "bf16", "f16"):
     base = base or med
     print(f"  attention backward kernels, n={n} H={H}, {variant or 'fp32'}: {med:.3f} ms (min {lo:.3f}, max {hi:.3f}; 9 runs)"
           + ("" if variant is None else f" = {base / med:.2f}x the fp32 form"))
+
+
+# ---- the training graph's Block in its two modes (train_block "autograd" / "native"), HIP events around forward and backward
+import types
+from cdsegnet_amd import models, train_graph as TG
+
+
+class _Level:
+    offs_host = [0, n]
+    def nbr(self, ksize, kmajor=False): return nbr
+    def slots(self, curve, patch_size, enable_flash): return gidx, widx
+    def pad(self, patch_size, enable_flash): return (K, npad, offs, offs_pad, ps, K, 0.0)
+    def pad_host(self, patch_size, enable_flash): return (K, None, None, np.asarray(ps_host, dtype=np.int32))
+
+
+blk = models.Block(C, H, patch_size=K, enable_flash=True).to(dev)
+xg = x.clone().requires_grad_(True)
+ref_order = torch.arange(n, dtype=torch.int32, device=dev)
+
+
+def graph_block(tp, mode, reps=7):
+    tg = TG.TrainGraph.__new__(TG.TrainGraph)
+    tg.model = types.SimpleNamespace(training=True)
+    tg.attn_variant = TG.TRAIN_PRECISIONS[tp]
+    tg.mm_variant = TG.TRAIN_PRECISIONS[tp] if tp.endswith("-amp") else None
+    tg.det, tg.train_block, tg._native = False, mode, {}
+    f, b = [], []
+    for _ in range(reps + 2):
+        blk.zero_grad(set_to_none=True)
+        xg.grad = None
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        torch.cuda.synchronize()
+        e[0].record()
+        y = tg._block(TG._St(_Level(), xg, [0], ref_order), blk, "blk", None, None).x
+        e[1].record()
+        y.backward(dy)
+        e[2].record()
+        torch.cuda.synchronize()
+        f.append(e[0].elapsed_time(e[1]))
+        b.append(e[1].elapsed_time(e[2]))
+    f, b = sorted(f[2:]), sorted(b[2:])
+    return f[len(f) // 2], f[0], f[-1], b[len(b) // 2], b[0], b[-1]
+
+
+for tp in ("fp32", "fp16-amp"):
+    rows = {mode: graph_block(tp, mode) for mode in ("autograd", "native", "autograd", "native")}  # (alternating; the later run is kept)
+    for mode, r in rows.items():
+        print(f"  training-graph Block, n={n} C={C} H={H}, {tp}, {mode}: forward {r[0]:.3f} ms ({r[1]:.3f} - {r[2]:.3f}), "
+              f"backward {r[3]:.3f} ms ({r[4]:.3f} - {r[5]:.3f}); 7 runs, HIP events")
+    a, m = rows["autograd"], rows["native"]
+    print(f"  native / autograd, {tp}: forward {m[0] / a[0]:.2f}x, backward {m[3] / a[3]:.2f}x the autograd Block's time")
