@@ -180,6 +180,11 @@ SIGNATURES = {
     "cdseg_fragment_select": (c_int, [c_void_p, c_void_p, c_long, c_int, c_void_p, c_void_p]),
     "cdseg_softmax_vote": (c_int, [c_void_p, c_int, c_void_p, c_long, c_int, c_void_p, c_int, c_void_p]),
     "cdseg_argmax_rows": (c_int, [c_void_p, c_int, c_long, c_int, c_void_p, c_void_p]),
+    "cdseg_fragments_build_ws_bytes": (c_size_t, [c_int]),
+    "cdseg_fragments_build": (c_int, [c_void_p, c_void_p, c_long, c_int, c_long, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "cdseg_softmax_vote_fragments": (c_int, [c_void_p, c_int, c_void_p, c_long, c_int, c_int, c_void_p, c_int, c_long, c_void_p]),
+    "cdseg_voxel_inverse": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
     "cdseg_tt_bbox": (c_int, [c_void_p, c_int, c_long, c_void_p, c_void_p]),
     "cdseg_tt_affine": (c_int, [c_void_p, c_int, c_long, c_int, POINTER(ctypes.c_double), c_void_p, POINTER(ctypes.c_double), c_int,
                                 ctypes.c_double, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),

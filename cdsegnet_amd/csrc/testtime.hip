@@ -164,13 +164,90 @@ __global__ void fragment_select_kernel(const int32_t* __restrict__ idx_sort, con
   idx_part[v] = idx_sort[s + frag % c];
 }
 
-// pred[idx[i], :] += softmax(logits[i, :]) ; one wave per row (C up to a few hundred classes)
-__global__ void softmax_vote_kernel(const float* __restrict__ logits, int ldl, const int32_t* __restrict__ idx, long m,
-                                    int c, float* __restrict__ pred, int ldp) {
-  const int lane = threadIdx.x & 63;
-  const long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (row >= m) return;
-  const float* l = logits + row * ldl;
+// all fragments of one augmented scan, dense: thread (v, f) serves voxel v of fragment f = member f % count_v
+// (transform.py:862-864) and writes index[f][v], the gathered grid_coord / feature rows (VEC floats per access: 4 = one
+// 16-byte access per 4 channels) and either the float32 coordinates or, for the per-fragment CenterShift, fragment f's
+// x / y bounds into acc4[f] = [min x, min y, ~max x, ~max y] (ordered-integer atomics as in minmax3_kernel: exact; the
+// maxima are kept complemented so that all four are minima and one fill initialises them).
+// Rows whose source index falls outside [0, n) are left unwritten and take no part in the bounds.
+template <typename TC, int VEC>
+__global__ void fragments_build_kernel(const int32_t* __restrict__ idx_sort, const int32_t* __restrict__ seg_start, long m,
+                                       long n, const int32_t* __restrict__ grid, const float* __restrict__ feat, int c,
+                                       const TC* __restrict__ coord, int32_t* __restrict__ index,
+                                       int32_t* __restrict__ grid_out, float* __restrict__ feat_out,
+                                       float* __restrict__ coord_out, unsigned long long* __restrict__ acc4) {
+  const long v = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int f = blockIdx.y;
+  double lo[2] = {INFINITY, INFINITY}, hi[2] = {-INFINITY, -INFINITY};
+  if (v < m) {
+    const int s = seg_start[v], cnt = seg_start[v + 1] - s;
+    const long src = idx_sort[s + f % cnt], row = (long)f * m + v;
+    index[row] = (int32_t)src;
+    if (src >= 0 && src < n) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a) grid_out[3 * row + a] = grid[3 * src + a];
+      if (VEC == 4) {
+        const float4* fs = (const float4*)(feat + src * c);
+        float4* fd = (float4*)(feat_out + row * c);
+        for (int j = 0; j < c / 4; ++j) fd[j] = fs[j];
+      } else if (VEC == 2) {
+        const float2* fs = (const float2*)(feat + src * c);
+        float2* fd = (float2*)(feat_out + row * c);
+        for (int j = 0; j < c / 2; ++j) fd[j] = fs[j];
+      } else {
+        for (int j = 0; j < c; ++j) feat_out[row * c + j] = feat[src * c + j];
+      }
+      if (acc4) {
+#pragma unroll
+        for (int a = 0; a < 2; ++a) lo[a] = hi[a] = (double)coord[3 * src + a];
+      } else {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) coord_out[3 * row + a] = (float)coord[3 * src + a];
+      }
+    }
+  }
+  if (!acc4) return;
+#pragma unroll
+  for (int a = 0; a < 2; ++a) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      lo[a] = fmin(lo[a], __shfl_xor(lo[a], o, 64));
+      hi[a] = fmax(hi[a], __shfl_xor(hi[a], o, 64));
+    }
+    if ((threadIdx.x & 63) == 0 && lo[a] <= hi[a]) {
+      atomicMin(&acc4[4 * f + a], ord_u64(lo[a]));
+      atomicMin(&acc4[4 * f + 2 + a], ~ord_u64(hi[a]));
+    }
+  }
+}
+// per-fragment CenterShift(apply_z=False) of the gathered coordinates: the subtraction in the source's own precision
+// (center_shift_kernel's expressions), then ONE rounding to float32
+template <typename TC>
+__global__ void fragments_shift_kernel(const int32_t* __restrict__ index, const TC* __restrict__ coord, long m, long n,
+                                       const unsigned long long* __restrict__ acc4, float* __restrict__ coord_out) {
+  const long v = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int f = blockIdx.y;
+  if (v >= m) return;
+  const long row = (long)f * m + v, src = index[row];
+  if (src < 0 || src >= n) return;
+  const TC sx = ((TC)ord_f64(acc4[4 * f]) + (TC)ord_f64(~acc4[4 * f + 2])) / (TC)2;
+  const TC sy = ((TC)ord_f64(acc4[4 * f + 1]) + (TC)ord_f64(~acc4[4 * f + 3])) / (TC)2;
+  coord_out[3 * row] = (float)(coord[3 * src] - sx);
+  coord_out[3 * row + 1] = (float)(coord[3 * src + 1] - sy);
+  coord_out[3 * row + 2] = (float)(coord[3 * src + 2] - (TC)0);
+}
+
+// inverse[idx_sort[j]] = cluster[j]: the voxel rank of every raw point (GridSample(return_inverse=True), transform.py:847-849)
+__global__ void voxel_inverse_kernel(const int32_t* __restrict__ idx_sort, const int32_t* __restrict__ cluster, long n,
+                                     int32_t* __restrict__ inverse) {
+  const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const long i = idx_sort[j];
+  if (i >= 0 && i < n) inverse[i] = cluster[j];
+}
+
+// p[:] += softmax(l[:]) by one wave (C up to a few hundred classes)
+__device__ __forceinline__ void softmax_vote_row(const float* __restrict__ l, int c, int lane, float* p) {
   float mx = -INFINITY;
   for (int j = lane; j < c; j += 64) mx = fmaxf(mx, l[j]);
   mx = wave_max(mx);
@@ -178,8 +255,31 @@ __global__ void softmax_vote_kernel(const float* __restrict__ logits, int ldl, c
   for (int j = lane; j < c; j += 64) s += expf(l[j] - mx);
   s = wave_sum(s);
   const float inv = 1.0f / s;
-  float* p = pred + (long)idx[row] * ldp;
   for (int j = lane; j < c; j += 64) p[j] += expf(l[j] - mx) * inv;
+}
+
+// pred[idx[i], :] += softmax(logits[i, :]) ; one wave per row
+__global__ void softmax_vote_kernel(const float* __restrict__ logits, int ldl, const int32_t* __restrict__ idx, long m,
+                                    int c, float* __restrict__ pred, int ldp) {
+  const int lane = threadIdx.x & 63;
+  const long row = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (row >= m) return;
+  softmax_vote_row(logits + row * ldl, c, lane, pred + (long)idx[row] * ldp);
+}
+
+// the votes of k collated fragments of one scan (logits (k m, c), index (k, m)): the wave of voxel v adds fragments
+// 0 .. k-1 in that order.  The members of a voxel belong to no other voxel, so lane j of this wave is the only writer of
+// column j of their rows: no atomics, and the sums are those of k successive softmax_vote_kernel launches.
+__global__ void softmax_vote_fragments_kernel(const float* __restrict__ logits, int ldl, const int32_t* __restrict__ index,
+                                              long m, int k, int c, float* pred, int ldp, long n) {
+  const int lane = threadIdx.x & 63;
+  const long v = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (v >= m) return;
+  for (int f = 0; f < k; ++f) {
+    const long row = (long)f * m + v, dst = index[row];
+    if (dst < 0 || dst >= n) continue;
+    softmax_vote_row(logits + row * ldl, c, lane, pred + dst * ldp);
+  }
 }
 
 // first arg-max of every row (torch.max(1)[1] tie rule: lowest index)
@@ -543,6 +643,67 @@ int cdseg_softmax_vote(const float* logits, int ldl, const int32_t* idx, long m,
   if (m <= 0 || c <= 0) return CDSEG_OK;
   hipLaunchKernelGGL(softmax_vote_kernel, g1(m * 64), dim3(256), 0, (hipStream_t)stream, logits, ldl, idx, m, c, pred,
                      ldp);
+  CDSEG_CHECK_LAUNCH();
+  return CDSEG_OK;
+}
+
+// All F fragments of one augmented scan (n source rows, m voxels) in a number of launches that does not depend on F:
+// index (F,m) int32, grid_out (F,m,3) int32, feat_out (F,m,c) float32, coord_out (F,m,3) float32 from coord (n,3)
+// float32 / float64.  center_shift != 0: the per-fragment CenterShift(apply_z=False) before the rounding to float32;
+// ws: >= cdseg_fragments_build_ws_bytes(F) bytes of device scratch (may be NULL without the shift).
+size_t cdseg_fragments_build_ws_bytes(int F) { return F > 0 ? (size_t)F * 4 * sizeof(unsigned long long) : 0; }
+
+int cdseg_fragments_build(const int32_t* idx_sort, const int32_t* seg_start, long m, int F, long n, const int32_t* grid,
+                          const float* feat, int c, const void* coord, int coord_f64, int center_shift, int32_t* index,
+                          int32_t* grid_out, float* feat_out, float* coord_out, void* ws, size_t ws_bytes, void* stream) {
+  if (m <= 0 || F <= 0 || n <= 0) return CDSEG_OK;
+  if (!idx_sort || !seg_start || !grid || !feat || !coord || !index || !grid_out || !feat_out || !coord_out || c <= 0)
+    return CDSEG_ERR_ARG;
+  if (F > 65535) return CDSEG_ERR_UNSUPPORTED;  // one grid row per fragment
+  if (center_shift && (!ws || ws_bytes < cdseg_fragments_build_ws_bytes(F))) return CDSEG_ERR_WORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  unsigned long long* acc = center_shift ? (unsigned long long*)ws : nullptr;
+  if (acc) {  // per fragment [min x, min y, ~max x, ~max y] as ordered integers: all four are minima and start at all ones
+    if (hipMemsetAsync(acc, 0xff, cdseg_fragments_build_ws_bytes(F), s) != hipSuccess) return CDSEG_ERR_LAUNCH;
+  }
+  const size_t align = (size_t)feat | (size_t)feat_out;
+  const int vec = (c % 4 == 0 && align % 16 == 0) ? 4 : ((c % 2 == 0 && align % 8 == 0) ? 2 : 1);
+  const dim3 g((unsigned)((m + 255) / 256), (unsigned)F), b(256);
+#define CDSEG_FB(TC, VEC)                                                                                              \
+  hipLaunchKernelGGL((fragments_build_kernel<TC, VEC>), g, b, 0, s, idx_sort, seg_start, m, n, grid, feat, c,           \
+                     (const TC*)coord, index, grid_out, feat_out, coord_out, acc)
+  if (coord_f64) {
+    if (vec == 4) CDSEG_FB(double, 4); else if (vec == 2) CDSEG_FB(double, 2); else CDSEG_FB(double, 1);
+  } else {
+    if (vec == 4) CDSEG_FB(float, 4); else if (vec == 2) CDSEG_FB(float, 2); else CDSEG_FB(float, 1);
+  }
+#undef CDSEG_FB
+  if (acc) {
+    if (coord_f64) hipLaunchKernelGGL(fragments_shift_kernel<double>, g, b, 0, s, index, (const double*)coord, m, n, acc, coord_out);
+    else hipLaunchKernelGGL(fragments_shift_kernel<float>, g, b, 0, s, index, (const float*)coord, m, n, acc, coord_out);
+  }
+  CDSEG_CHECK_LAUNCH();
+  return CDSEG_OK;
+}
+
+// pred[index[f][v], :] += softmax(logits[f m + v, :]) for f = 0 .. k-1 in that order, one launch; pred has n rows.
+// Bit-equal to k successive cdseg_softmax_vote calls PROVIDED the rows of one voxel are named by no other voxel
+// (the fragments of cdseg_fragments_build).
+int cdseg_softmax_vote_fragments(const float* logits, int ldl, const int32_t* index, long m, int k, int c, float* pred,
+                                 int ldp, long n, void* stream) {
+  if (m <= 0 || k <= 0 || c <= 0 || n <= 0) return CDSEG_OK;
+  if (!logits || !index || !pred) return CDSEG_ERR_ARG;
+  hipLaunchKernelGGL(softmax_vote_fragments_kernel, g1(m * 64), dim3(256), 0, (hipStream_t)stream, logits, ldl, index, m, k,
+                     c, pred, ldp, n);
+  CDSEG_CHECK_LAUNCH();
+  return CDSEG_OK;
+}
+
+// GridSample(return_inverse=True): inverse[idx_sort[j]] = cluster[j] (n rows)
+int cdseg_voxel_inverse(const int32_t* idx_sort, const int32_t* cluster, long n, int32_t* inverse, void* stream) {
+  if (n <= 0) return CDSEG_OK;
+  if (!idx_sort || !cluster || !inverse) return CDSEG_ERR_ARG;
+  hipLaunchKernelGGL(voxel_inverse_kernel, g1(n), dim3(256), 0, (hipStream_t)stream, idx_sort, cluster, n, inverse);
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
 }

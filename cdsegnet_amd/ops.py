@@ -1076,6 +1076,52 @@ def argmax_rows(x):
     return out
 
 
+def fragments_build(idx_sort, seg_start, m, frags, grid, feat, coord, center_shift=False):
+    """All ``frags`` fragments of one augmented scan as dense arrays, in launches that do not depend on ``frags``:
+    -> (index (F,m) int32, coord (F,m,3) float32, grid_coord (F,m,3) int32, feat (F,m,C) float32).  grid (n,3) int32,
+    feat (n,C) float32, coord (n,3) float32 / float64; center_shift: the per-fragment CenterShift(apply_z=False) in
+    coord's precision before the one rounding to float32 (include/cdseg.h)."""
+    _need_gpu(idx_sort, seg_start, grid, feat, coord)
+    lib = _lib.load()
+    assert grid.dtype == torch.int32 and feat.dtype == torch.float32 and coord.dtype in (torch.float32, torch.float64)
+    assert feat.dim() == 2 and coord.shape == grid.shape == (feat.shape[0], 3)
+    grid, feat, coord = grid.contiguous(), feat.contiguous(), coord.contiguous()
+    m, frags, n, c, dev = int(m), int(frags), feat.shape[0], feat.shape[1], feat.device
+    index = torch.empty((frags, m), dtype=torch.int32, device=dev)
+    coord_out = torch.empty((frags, m, 3), dtype=torch.float32, device=dev)
+    grid_out = torch.empty((frags, m, 3), dtype=torch.int32, device=dev)
+    feat_out = torch.empty((frags, m, c), dtype=torch.float32, device=dev)
+    ws = workspace(lib.cdseg_fragments_build_ws_bytes(frags), dev) if center_shift else None
+    check(lib.cdseg_fragments_build(_ptr(idx_sort), _ptr(seg_start), m, frags, n, _ptr(grid), _ptr(feat), c, _ptr(coord),
+                                    1 if coord.dtype == torch.float64 else 0, 1 if center_shift else 0, _ptr(index),
+                                    _ptr(grid_out), _ptr(feat_out), _ptr(coord_out), _ptr(ws), 0 if ws is None else ws.numel(),
+                                    _stream()), "fragments_build")
+    return index, coord_out, grid_out, feat_out
+
+
+def softmax_vote_fragments(logits, index, pred):
+    """pred[index[f][v]] += softmax(logits[f m + v]) for the k = index.shape[0] collated fragments, f ascending, one launch;
+    bit-equal to k successive softmax_vote calls on fragments_build's index rows."""
+    _need_gpu(logits, index, pred)
+    k, m = index.shape
+    assert index.dtype == torch.int32 and index.is_contiguous() and logits.shape[0] == k * m
+    assert logits.dtype == pred.dtype == torch.float32 and logits.stride(1) == 1 and pred.stride(1) == 1
+    assert pred.shape[1] == logits.shape[1]
+    check(_lib.load().cdseg_softmax_vote_fragments(_ptr(logits), logits.stride(0), _ptr(index), m, k, logits.shape[1], _ptr(pred),
+                                                   pred.stride(0), pred.shape[0], _stream()), "softmax_vote_fragments")
+    return pred
+
+
+def voxel_inverse(idx_sort, cluster):
+    """GridSample(return_inverse=True): inverse (n,) int32 with inverse[idx_sort[j]] = cluster[j]."""
+    _need_gpu(idx_sort, cluster)
+    n = idx_sort.numel()
+    assert idx_sort.dtype == cluster.dtype == torch.int32 and cluster.numel() >= n
+    out = torch.empty(n, dtype=torch.int32, device=idx_sort.device)
+    check(_lib.load().cdseg_voxel_inverse(_ptr(idx_sort), _ptr(cluster), n, _ptr(out), _stream()), "voxel_inverse")
+    return out
+
+
 def knn1(ref_xyz, ref_offset, qry_xyz, qry_offset, origin, cell, want_dist=False):
     """Exact nearest reference point (same batch element) of every query.  offsets: int32 cumulative ends."""
     lib = _lib.load()

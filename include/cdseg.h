@@ -330,6 +330,27 @@ int cdseg_softmax_vote(const float* logits, int ldl, const int32_t* idx, long m,
                        void* stream);
 /* out[i] = first arg-max of row i.  ref: engines/test.py:278 */
 int cdseg_argmax_rows(const float* x, int ldx, long n, int c, int32_t* out, void* stream);
+/* ALL F fragments of one augmented scan as dense arrays, in a number of launches that does not depend on F
+ * (ref: transform.py:867-895 + the post_transform CenterShift(apply_z=False) :142-155 and Collect :27-50).
+ * idx_sort / seg_start: the stable voxel sort and its m runs over the n source rows; fragment f takes member f % count_v
+ * of voxel v.  index (F,m) int32 = source rows; grid_out (F,m,3) = grid rows; feat_out (F,m,c) = feat rows (16-byte
+ * accesses when c % 4 == 0 and both feature pointers are 16-byte aligned, 8-byte for even c, else 4-byte); coord_out (F,m,3)
+ * float32 from coord (n,3) float32 (coord_f64 = 0) or float64.  center_shift != 0: fragment f's coordinates minus
+ * [(xmin + xmax) / 2, (ymin + ymax) / 2, 0] of that fragment, computed in coord's precision (bounds by order-independent
+ * integer min / max atomics), then rounded to float32 once - bit-equal to cdseg_fragment_select + cdseg_gather_rows +
+ * cdseg_center_shift + a conversion.  ws: cdseg_fragments_build_ws_bytes(F) bytes (only read with center_shift).
+ * F <= 65535.  Source rows outside [0, n) are skipped. */
+size_t cdseg_fragments_build_ws_bytes(int F);
+int cdseg_fragments_build(const int32_t* idx_sort, const int32_t* seg_start, long m, int F, long n, const int32_t* grid,
+                          const float* feat, int c, const void* coord, int coord_f64, int center_shift, int32_t* index,
+                          int32_t* grid_out, float* feat_out, float* coord_out, void* ws, size_t ws_bytes, void* stream);
+/* the votes of k collated fragments in one launch: pred[index[f][v], :] += softmax(logits[f m + v, :]), f = 0 .. k-1 in
+ * that order for every voxel v (logits (k m, c), index (k, m), pred n rows).  No float atomics; bit-equal to k successive
+ * cdseg_softmax_vote calls when no row is named by two voxels (the fragments of cdseg_fragments_build). */
+int cdseg_softmax_vote_fragments(const float* logits, int ldl, const int32_t* index, long m, int k, int c, float* pred,
+                                 int ldp, long n, void* stream);
+/* GridSample(return_inverse=True) :847-849: inverse[idx_sort[j]] = cluster[j], the voxel rank of every one of the n rows */
+int cdseg_voxel_inverse(const int32_t* idx_sort, const int32_t* cluster, long n, int32_t* inverse, void* stream);
 
 /* ------------------------------------------------------------------ train-time pipeline
  * ref: configs/{scannet,scannet200,nuscenes}/CDSegNet.py data.train / data.val transform lists, datasets/transform.py.
