@@ -88,6 +88,7 @@ class TrainBlockIO(Structure):
         ("num_patches", c_int), ("max_len", c_int), ("num_slots", c_long),
         ("tape", c_void_p), ("tape_bytes", c_size_t), ("scratch", c_void_p), ("scratch_bytes", c_size_t),
         ("x_out", c_void_p),
+        ("n_conv", c_long), ("row_vox", c_void_p), ("row_start", c_void_p),
     ]
 
 
@@ -316,6 +317,10 @@ SIGNATURES = {
     "cdseg_train_block_backward": (c_int, [POINTER(TrainBlockDesc), POINTER(TrainBlockIO), c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p]),
     "cdseg_residual": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_long, c_int, c_void_p]),
+    "cdseg_gather_first": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_void_p]),
+    "cdseg_residual_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_long, c_int, c_void_p]),
+    "cdseg_run_sum": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p]),
+    "cdseg_scatter_first": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_void_p]),
     "cdseg_scale_cast": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_void_p]),
     "cdseg_add_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_long,
                                     c_int, c_void_p]),

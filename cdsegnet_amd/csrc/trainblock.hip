@@ -7,8 +7,9 @@
 // The products are the library's own entry points, called as the autograd graph calls them (cdseg_gemm dense and gathered,
 // cdseg_layernorm / _bwd[_det], cdseg_attention / _bwd, cdseg_linear_wgrad[16][_det], cdseg_conv_wgrad[16][_det]).  New
 // here: the row kernels for what torch did (residual, scale_cast, add_layernorm, gelu_fwd, gelu_bwd_cast, the per-scene column
-// sums of dt_rows) and the derive kernel of cdseg_train_block_prepare.  All of them: 16-byte loads and stores, wave64,
-// grid-stride loops, no LDS, no float atomics, no scratch.
+// sums of dt_rows), the derive kernel of cdseg_train_block_prepare, and the four kernels of the row level (a Mix3D batch trained on
+// every point: io->n_conv, row_vox, row_start - gather_first, residual_rows, run_sum, scatter_first).  All of them: 16-byte loads
+// and stores, wave64, grid-stride loops, no LDS, no float atomics, no scratch.
 #include <cstring>
 
 #include "common.h"
@@ -78,6 +79,94 @@ __global__ void residual_kernel(const float* x, const float* a, const float* __r
       v.x = v.x + r.x; v.y = v.y + r.y; v.z = v.z + r.z; v.w = v.w + r.w;
     }
     *reinterpret_cast<float4*>(out + 4 * t) = v;
+  }
+}
+
+// ---------------------------------------------------------------- the row level above the voxels (Mix3D, every point a row)
+// n rows in voxel order, the rows of a voxel contiguous: row_vox (n) is the voxel of a row, row_start (nv + 1) the first row of
+// every voxel's run.  Rows of c floats, c a multiple of 4; one thread per 16-byte chunk, consecutive lanes on consecutive
+// chunks, so a wave covers 256 / c voxels (or rows) and a run's rows are walked by the lanes of its columns.
+
+// gather_first: out[v] = cast(x[row_start[v]])  (16-bit: saturating, the forward's operand cast)
+template <bool LP>
+__global__ void gather_first_kernel(const float* __restrict__ x, const int32_t* __restrict__ row_start, void* __restrict__ out,
+                                    long nv, int c) {
+  const int nchunk = c >> 2;
+  const long total = nv * nchunk;
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
+    const long v = t / nchunk;
+    const int ch = (int)(t - v * nchunk);
+    const float4 val = *reinterpret_cast<const float4*>(x + (long)row_start[v] * c + 4 * ch);
+    if (LP) store4_sat((bf16_t*)out + 4 * t, val);
+    else *reinterpret_cast<float4*>((float*)out + 4 * t) = val;
+  }
+}
+
+// residual_rows: out[i] = x[i] + a[row_vox[i]] + t_rows[scene(i)]  (a: one row per voxel; out may be x)
+__global__ void residual_rows_kernel(const float* x, const float* __restrict__ a, const int32_t* __restrict__ row_vox,
+                                     const float* __restrict__ t_rows, const int32_t* __restrict__ offs, int nb, float* out, long n,
+                                     int c) {
+#pragma clang fp contract(off)
+  const int nchunk = c >> 2;
+  const long total = n * nchunk;
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
+    const long row = t / nchunk;
+    const int ch = (int)(t - row * nchunk);
+    float4 v = *reinterpret_cast<const float4*>(x + 4 * t);
+    const float4 p = *reinterpret_cast<const float4*>(a + (long)row_vox[row] * c + 4 * ch);
+    v.x = v.x + p.x; v.y = v.y + p.y; v.z = v.z + p.z; v.w = v.w + p.w;
+    if (t_rows) {
+      const float4 r = *reinterpret_cast<const float4*>(t_rows + (long)scene_of(offs, nb, row) * c + 4 * ch);
+      v.x = v.x + r.x; v.y = v.y + r.y; v.z = v.z + r.z; v.w = v.w + r.w;
+    }
+    *reinterpret_cast<float4*>(out + 4 * t) = v;
+  }
+}
+
+// run_sum: out[v] = 0 + dx[row_start[v]] + ... + dx[row_start[v + 1] - 1], in ascending row order
+__global__ void run_sum_kernel(const float* __restrict__ dx, const int32_t* __restrict__ row_start, float* __restrict__ out, long nv,
+                               int c) {
+#pragma clang fp contract(off)
+  const int nchunk = c >> 2;
+  const long total = nv * nchunk;
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
+    const long v = t / nchunk;
+    const int ch = (int)(t - v * nchunk);
+    const long r0 = row_start[v], r1 = row_start[v + 1];
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (long r = r0; r < r1; ++r) {
+      const float4 d = *reinterpret_cast<const float4*>(dx + r * c + 4 * ch);
+      s.x = s.x + d.x; s.y = s.y + d.y; s.z = s.z + d.z; s.w = s.w + d.w;
+    }
+    *reinterpret_cast<float4*>(out + 4 * t) = s;
+  }
+}
+
+// scatter_first: the conv's data gradient g (one row per voxel) belongs to the FIRST row of the voxel's run.
+// ACC: dx[i] += g[row_vox[i]] on first rows, the other rows untouched; else dx[i] = g[row_vox[i]] or 0 (every row written)
+template <bool ACC>
+__global__ void scatter_first_kernel(const float* __restrict__ g, const int32_t* __restrict__ row_vox,
+                                     const int32_t* __restrict__ row_start, float* dx, long n, int c) {
+#pragma clang fp contract(off)
+  const int nchunk = c >> 2;
+  const long total = n * nchunk;
+  for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
+    const long row = t / nchunk;
+    const int ch = (int)(t - row * nchunk);
+    const long v = row_vox[row];
+    const bool first = (long)row_start[v] == row;
+    if (ACC) {
+      if (first) {
+        float4 d = *reinterpret_cast<const float4*>(dx + 4 * t);
+        const float4 p = *reinterpret_cast<const float4*>(g + v * c + 4 * ch);
+        d.x = d.x + p.x; d.y = d.y + p.y; d.z = d.z + p.z; d.w = d.w + p.w;
+        *reinterpret_cast<float4*>(dx + 4 * t) = d;
+      }
+    } else {
+      float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (first) p = *reinterpret_cast<const float4*>(g + v * c + 4 * ch);
+      *reinterpret_cast<float4*>(dx + 4 * t) = p;
+    }
   }
 }
 
@@ -498,6 +587,10 @@ bool io_ok(const cdseg_train_block_desc* d, const cdseg_train_block_io* io, bool
   if ((((uintptr_t)io->mask1 | (uintptr_t)io->mask2 | (uintptr_t)io->nbr | (uintptr_t)io->gidx | (uintptr_t)io->widx |
         (uintptr_t)io->patch_start | (uintptr_t)io->scene_offs) & 3) != 0)
     return false;
+  // the row level (Mix3D): all three or none; the tape and the scratch are sized by n >= n_conv and gain nothing
+  if (io->n_conv == 0 ? (io->row_vox || io->row_start) : (io->n_conv < 1 || io->n_conv > io->n || !io->row_vox || !io->row_start))
+    return false;
+  if ((((uintptr_t)io->row_vox | (uintptr_t)io->row_start) & 3) != 0) return false;
   if (io->tape_bytes < carve_tape(d, io->n, nullptr).total) return false;
   if (io->scratch_bytes < carve_scratch(d, io->n, io->num_slots, nullptr).total) return false;
   return true;
@@ -589,6 +682,52 @@ extern "C" int cdseg_residual(const float* x, const float* a, const float* mask,
   if ((mask && !a) || (t_rows && (!scene_offs || num_scenes <= 0))) return CDSEG_ERR_ARG;
   hipLaunchKernelGGL(residual_kernel, dim3(row_grid(n * (c >> 2))), dim3(ROW_BLOCK), 0, (hipStream_t)stream, x, a, mask, t_rows,
                      scene_offs, num_scenes, out, n, c);
+  CDSEG_CHECK_LAUNCH();
+  return CDSEG_OK;
+}
+
+extern "C" int cdseg_gather_first(const float* x, const int32_t* row_start, void* out, int out_dtype, long nv, int c, void* stream) {
+  if (nv <= 0) return CDSEG_OK;
+  if (!x || !row_start || !out || c <= 0 || (c & 3) || !al16(x) || !al16(out) || ((uintptr_t)row_start & 3)) return CDSEG_ERR_ARG;
+  if (out_dtype != CDSEG_F32 && out_dtype != CDSEG_BF16) return CDSEG_ERR_ARG;
+  const dim3 grid(row_grid(nv * (c >> 2))), block(ROW_BLOCK);
+  if (out_dtype == CDSEG_BF16) hipLaunchKernelGGL(gather_first_kernel<true>, grid, block, 0, (hipStream_t)stream, x, row_start, out, nv, c);
+  else hipLaunchKernelGGL(gather_first_kernel<false>, grid, block, 0, (hipStream_t)stream, x, row_start, out, nv, c);
+  CDSEG_CHECK_LAUNCH();
+  return CDSEG_OK;
+}
+
+extern "C" int cdseg_residual_rows(const float* x, const float* a, const int32_t* row_vox, const float* t_rows,
+                                   const int32_t* scene_offs, int num_scenes, float* out, long n, int c, void* stream) {
+  if (n <= 0) return CDSEG_OK;
+  if (!x || !a || !row_vox || !out || c <= 0 || (c & 3) || !al16(x) || !al16(a) || !al16(out) || !al16(t_rows) ||
+      ((uintptr_t)row_vox & 3))
+    return CDSEG_ERR_ARG;
+  if (t_rows && (!scene_offs || num_scenes <= 0)) return CDSEG_ERR_ARG;
+  hipLaunchKernelGGL(residual_rows_kernel, dim3(row_grid(n * (c >> 2))), dim3(ROW_BLOCK), 0, (hipStream_t)stream, x, a, row_vox,
+                     t_rows, scene_offs, num_scenes, out, n, c);
+  CDSEG_CHECK_LAUNCH();
+  return CDSEG_OK;
+}
+
+extern "C" int cdseg_run_sum(const float* dx, const int32_t* row_start, float* out, long nv, int c, void* stream) {
+  if (nv <= 0) return CDSEG_OK;
+  if (!dx || !row_start || !out || c <= 0 || (c & 3) || !al16(dx) || !al16(out) || ((uintptr_t)row_start & 3)) return CDSEG_ERR_ARG;
+  hipLaunchKernelGGL(run_sum_kernel, dim3(row_grid(nv * (c >> 2))), dim3(ROW_BLOCK), 0, (hipStream_t)stream, dx, row_start, out, nv,
+                     c);
+  CDSEG_CHECK_LAUNCH();
+  return CDSEG_OK;
+}
+
+extern "C" int cdseg_scatter_first(const float* g, const int32_t* row_vox, const int32_t* row_start, float* dx, int accumulate,
+                                   long n, int c, void* stream) {
+  if (n <= 0) return CDSEG_OK;
+  if (!g || !row_vox || !row_start || !dx || c <= 0 || (c & 3) || !al16(g) || !al16(dx) ||
+      (((uintptr_t)row_vox | (uintptr_t)row_start) & 3))
+    return CDSEG_ERR_ARG;
+  const dim3 grid(row_grid(n * (c >> 2))), block(ROW_BLOCK);
+  if (accumulate) hipLaunchKernelGGL(scatter_first_kernel<true>, grid, block, 0, (hipStream_t)stream, g, row_vox, row_start, dx, n, c);
+  else hipLaunchKernelGGL(scatter_first_kernel<false>, grid, block, 0, (hipStream_t)stream, g, row_vox, row_start, dx, n, c);
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
 }
@@ -727,16 +866,29 @@ extern "C" int cdseg_train_block_forward(const cdseg_train_block_desc* d, const 
   const float* const* P = d->param;
 
   // ---- CPE: x0 = x_in + LN(Linear(conv(x_conv))) [+ t_rows[scene]]
+  // (row level: the whole CPE runs on the nc voxels - the conv reads the first row of every voxel - and row i adds
+  // LN(z)[row_vox[i]]; the voxel rows of x_conv live in the tape's 16-bit slot or, fp32, in scratch: the backward gathers again)
+  const bool rows = io->n_conv > 0;
+  const long nc = rows ? io->n_conv : n;
   const void* xc = io->x_conv;
-  if (lp) {
+  if (rows) {
+    xc = lp ? T.xc16 : S.h0;
+    TB_TRY(cdseg_gather_first(io->x_conv, io->row_start, (void*)xc, MM, nc, C, stream));
+  } else if (lp) {
     TB_TRY(cdseg_cast(io->x_conv, CDSEG_F32, T.xc16, CDSEG_BF16, n * C, stream));
     xc = T.xc16;
   }
-  TB_TRY(gemm(d, S, n, xc, fwd_weight(d, D, M_CONV), P[CDSEG_TB_CONV_B], C, C, T.yc, MM, io->nbr, stream));
-  TB_TRY(gemm(d, S, n, T.yc, fwd_weight(d, D, M_CPE), P[CDSEG_TB_CPE_B], C, C, T.z, CDSEG_F32, nullptr, stream));
-  TB_TRY(ln_fwd((const float*)T.z, P[CDSEG_TB_CPE_LN_G], P[CDSEG_TB_CPE_LN_B], d->eps_cpe, io->x_in, T.x0, CDSEG_F32, n, C, stream));
-  if (io->t_rows)
-    TB_TRY(cdseg_residual((const float*)T.x0, nullptr, nullptr, io->t_rows, io->scene_offs, io->num_scenes, (float*)T.x0, n, C, stream));
+  TB_TRY(gemm(d, S, nc, xc, fwd_weight(d, D, M_CONV), P[CDSEG_TB_CONV_B], C, C, T.yc, MM, io->nbr, stream));
+  TB_TRY(gemm(d, S, nc, T.yc, fwd_weight(d, D, M_CPE), P[CDSEG_TB_CPE_B], C, C, T.z, CDSEG_F32, nullptr, stream));
+  if (rows) {
+    TB_TRY(ln_fwd((const float*)T.z, P[CDSEG_TB_CPE_LN_G], P[CDSEG_TB_CPE_LN_B], d->eps_cpe, nullptr, S.f0, CDSEG_F32, nc, C, stream));
+    TB_TRY(cdseg_residual_rows(io->x_in, (const float*)S.f0, io->row_vox, io->t_rows, io->scene_offs, io->num_scenes, (float*)T.x0, n,
+                               C, stream));
+  } else {
+    TB_TRY(ln_fwd((const float*)T.z, P[CDSEG_TB_CPE_LN_G], P[CDSEG_TB_CPE_LN_B], d->eps_cpe, io->x_in, T.x0, CDSEG_F32, n, C, stream));
+    if (io->t_rows)
+      TB_TRY(cdseg_residual((const float*)T.x0, nullptr, nullptr, io->t_rows, io->scene_offs, io->num_scenes, (float*)T.x0, n, C, stream));
+  }
 
   // ---- attention branch: x1 = x0 + mask1 * proj(attention(qkv(LN1(x0))))
   TB_TRY(ln_fwd((const float*)T.x0, P[CDSEG_TB_NORM1_G], P[CDSEG_TB_NORM1_B], d->eps_norm1, nullptr, T.h1, MM, n, C, stream));
@@ -840,32 +992,46 @@ extern "C" int cdseg_train_block_backward(const cdseg_train_block_desc* d, const
   if (io->t_rows)
     TB_TRY(scene_sums(dx_in, io->scene_offs, io->num_scenes, n, C, (float*)S.f1, (size_t)n * (3 * C > H ? 3 * C : H) * 4, dt_rows, stream));
   // ---- CPE: x0 = x_in + LN(z), z = Linear(yc), yc = conv(x_conv)
+  // (row level: the CPE term of a voxel was read by every row of its run - its gradient is the run's sum in ascending row
+  // order, and everything down to the conv's data gradient has nc rows; S.f1 is free once the scene sums are out)
+  const bool rows = io->n_conv > 0;
+  const long nc = rows ? io->n_conv : n;
+  const float* dcpe = dx_in;
+  if (rows) {
+    TB_TRY(cdseg_run_sum(dx_in, io->row_start, (float*)S.f1, nc, C, stream));
+    dcpe = (const float*)S.f1;
+  }
   float* dz = (float*)S.f0;
-  TB_TRY(ln_bwd(d, S, (const float*)T.z, P[CDSEG_TB_CPE_LN_G], d->eps_cpe, dx_in, dz, 0, grad(CDSEG_TB_CPE_LN_G),
-                grad(CDSEG_TB_CPE_LN_B), n, stream));
+  TB_TRY(ln_bwd(d, S, (const float*)T.z, P[CDSEG_TB_CPE_LN_G], d->eps_cpe, dcpe, dz, 0, grad(CDSEG_TB_CPE_LN_G),
+                grad(CDSEG_TB_CPE_LN_B), nc, stream));
   const void* dz_op = dz;
   if (lp) {
-    TB_TRY(cast_nosat(dz, S.h0, n, C, stream));
+    TB_TRY(cast_nosat(dz, S.h0, nc, C, stream));
     dz_op = S.h0;
   }
-  TB_TRY(lin_wgrad(d, S, T.yc, dz_op, n, C, C, grad(CDSEG_TB_CPE_W), grad(CDSEG_TB_CPE_B), stream));
-  TB_TRY(gemm(d, S, n, dz_op, D.t[M_CPE], nullptr, C, C, S.f1, CDSEG_F32, nullptr, stream));  // d yc
+  TB_TRY(lin_wgrad(d, S, T.yc, dz_op, nc, C, C, grad(CDSEG_TB_CPE_W), grad(CDSEG_TB_CPE_B), stream));
+  TB_TRY(gemm(d, S, nc, dz_op, D.t[M_CPE], nullptr, C, C, S.f1, CDSEG_F32, nullptr, stream));  // d yc
   const void* dyc = S.f1;
   if (lp) {
-    TB_TRY(cast_nosat((const float*)S.f1, S.h0, n, C, stream));
+    TB_TRY(cast_nosat((const float*)S.f1, S.h0, nc, C, stream));
     dyc = S.h0;
   }
   const void* xc = lp ? (const void*)T.xc16 : (const void*)io->x_conv;
+  if (rows && !lp) {  // the fp32 voxel rows of x_conv are not on the tape: gathered again (S.h0 is idle with fp32 products)
+    TB_TRY(cdseg_gather_first(io->x_conv, io->row_start, S.h0, CDSEG_F32, nc, C, stream));
+    xc = S.h0;
+  }
   if (d->deterministic)
-    TB_TRY(cdseg_conv_wgrad_det(xc, C, io->nbr, 27, dyc, C, n, C, C, grad(CDSEG_TB_CONV_W), grad(CDSEG_TB_CONV_B), MM, S.aux,
+    TB_TRY(cdseg_conv_wgrad_det(xc, C, io->nbr, 27, dyc, C, nc, C, C, grad(CDSEG_TB_CONV_W), grad(CDSEG_TB_CONV_B), MM, S.aux,
                                 S.aux_bytes, stream));
   else if (lp)
-    TB_TRY(cdseg_conv_wgrad16(xc, C, io->nbr, 27, dyc, C, n, C, C, grad(CDSEG_TB_CONV_W), grad(CDSEG_TB_CONV_B), stream));
+    TB_TRY(cdseg_conv_wgrad16(xc, C, io->nbr, 27, dyc, C, nc, C, C, grad(CDSEG_TB_CONV_W), grad(CDSEG_TB_CONV_B), stream));
   else
-    TB_TRY(cdseg_conv_wgrad((const float*)xc, C, io->nbr, 27, (const float*)dyc, C, n, C, C, grad(CDSEG_TB_CONV_W),
+    TB_TRY(cdseg_conv_wgrad((const float*)xc, C, io->nbr, 27, (const float*)dyc, C, nc, C, C, grad(CDSEG_TB_CONV_W),
                             grad(CDSEG_TB_CONV_B), stream));
-  float* dxc = same ? (float*)S.f0 : dx_conv;
-  TB_TRY(gemm(d, S, n, dyc, D.t[M_CONV], nullptr, C, C, dxc, CDSEG_F32, io->nbr, stream));
-  if (same) TB_TRY(cdseg_residual(dx_in, dxc, nullptr, nullptr, nullptr, 0, dx_in, n, C, stream));
+  float* dxc = (same || rows) ? (float*)S.f0 : dx_conv;
+  TB_TRY(gemm(d, S, nc, dyc, D.t[M_CONV], nullptr, C, C, dxc, CDSEG_F32, io->nbr, stream));
+  if (rows) TB_TRY(cdseg_scatter_first(dxc, io->row_vox, io->row_start, same ? dx_in : dx_conv, same ? 1 : 0, n, C, stream));
+  else if (same) TB_TRY(cdseg_residual(dx_in, dxc, nullptr, nullptr, nullptr, 0, dx_in, n, C, stream));
   return CDSEG_OK;
 }

@@ -206,10 +206,36 @@ class Level:
         return _shared(self._slots, (curve, patch_size, enable_flash), build)
 
 
+class RowLevel(Level):
+    """Level 0 of a training batch whose voxels hold more than one point (Mix3D; `model.train_mix3d = "rows"`): EVERY point is
+    a row, in (batch | z) order with the rows of one voxel contiguous and ascending by caller index.  `voxels` is the plan's
+    level 0 (one row per voxel, the sparse convs' domain), `row_vox` (n) the voxel of a row, `row_start` (V + 1) the first
+    row of a voxel's run, `perm_rows` (n) physical row -> caller row.  Orders, padding tables and slot plans are the Level's
+    own (its radix sort is stable: ties of a curve code keep the physical order); the kernel map is the voxel level's."""
+
+    def __init__(self, voxels, keys, offs_host):
+        """keys (n) int64: the physical voxel row of every point, caller's order."""
+        n, nv = int(keys.numel()), voxels.n
+        row_vox, perm_rows = ops.sort_pairs(keys, None, end_bit=max(1, nv.bit_length()))
+        _, seg, _ = ops.pool_level(row_vox, 0)  # the run-length pass of the pooling links, at shift 0
+        idx = row_vox
+        super().__init__(0, voxels.depth, n, voxels.grid[idx], voxels.batch[idx], voxels.code4[:, idx].contiguous(), offs_host)
+        self.voxels, self.perm_rows = voxels, perm_rows
+        self.row_vox, self.row_start = row_vox.to(torch.int32), seg[:nv + 1]
+
+    def nbr(self, ksize, kmajor=False):
+        raise CdsegError("the row level of a Mix3D batch has no kernel map: sparse convs run on its voxel level (RowLevel.voxels)")
+
+    def child_info(self):
+        raise CdsegError("the row level of a Mix3D batch has no kernel map: sparse convs run on its voxel level (RowLevel.voxels)")
+
+
 class Plan:
     def __init__(self):
         self.levels = {}
         self.links = {}
+        self.rows = None  # RowLevel above levels[0] (training, Mix3D batches with `train_mix3d = "rows"`)
+        self._row_links = {}
         self._finish = None  # Engine.build_plan(defer_pads=True): the padding / slot plans, not built yet
         self._link_lazy = {}
 
@@ -233,6 +259,18 @@ class Plan:
             cluster, seg, _ = ops.pool_level(la.code4[0], 3 * (lb.cum - la.cum))
             return (cluster, seg)
         return _shared(self.links, (a, b), build)
+
+    def link_from(self, fine, b):
+        """`link(fine.cum, b)` for a Level object; from the row level it is two gathers of the voxel level's link: a row
+        pools where its voxel pools, and a pooled row's children start at the first row of its first voxel."""
+        if fine is not self.rows:
+            return self.link(fine.cum, b)
+
+        def build():
+            cluster, seg = self.link(0, b)
+            m = self.levels[b].n
+            return (cluster[fine.row_vox.long()], fine.row_start[seg[:m + 1].long()])
+        return _shared(self._row_links, b, build)
 
 
 class State:

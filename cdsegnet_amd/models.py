@@ -449,6 +449,12 @@ class DefaultSegmentorV2(nn.Module):
         # each (csrc/trainblock.hip: all launches issued from C++, the torch glue as HIP row kernels); read at every
         # forward(), anything else raises ValueError there; not part of the state_dict
         self.train_block = "autograd"
+        # training batches whose voxels hold more than one point (Mix3D, mix_prob = 0.8 in the shipped configs): "fold"
+        # (default: the network runs on the first point of every voxel, the other points read its prediction) | "rows": every
+        # point is a row of its own everywhere but in the sparse convs, which read the first point of a voxel
+        # (engine.RowLevel); no effect on a batch without shared voxels; read at every forward(), anything else raises
+        # ValueError there; not part of the state_dict
+        self.train_mix3d = "fold"
         self._lanes = {}
         self.noise_source = "torch_cpu"  # "torch_cpu" replays the reference's CPU-generator draws | "device"
         # noise_level jitter: "torch_cpu" = the CPU-run reference's draw order (golden vectors) | "device" = device

@@ -1446,7 +1446,7 @@ def train_block_prepare(tb):
 
 
 def _train_block_io(tb, n, x_in, x_conv, t_rows, scene_offs, mask1, mask2, nbr, gidx, widx, patch_start, patch_start_host, tape,
-                    scratch, x_out):
+                    scratch, x_out, rows=None):
     _need_gpu(x_in, x_conv, tape, scratch)
     for t in (x_in, x_conv, x_out, t_rows, mask1, mask2):
         if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
@@ -1464,33 +1464,85 @@ def _train_block_io(tb, n, x_in, x_conv, t_rows, scene_offs, mask1, mask2, nbr, 
     io.tape, io.tape_bytes = tape.data_ptr(), tape.numel()
     io.scratch, io.scratch_bytes = scratch.data_ptr(), scratch.numel()
     io.x_out = _dp(x_out)
+    if rows is None:
+        io.n_conv, io.row_vox, io.row_start = 0, None, None
+    else:  # the row level of a Mix3D batch (engine.RowLevel): nbr describes the row_start.numel() - 1 voxels
+        row_vox, row_start = rows
+        if (row_vox.dtype != torch.int32 or row_start.dtype != torch.int32 or not row_vox.is_contiguous() or not row_start.is_contiguous()
+                or row_vox.numel() != int(n) or nbr.shape[-1] != row_start.numel() - 1):
+            raise _lib.CdsegError("train_block: rows = (row_vox (n), row_start (voxels + 1)) contiguous int32, nbr over the voxels")
+        io.n_conv, io.row_vox, io.row_start = row_start.numel() - 1, row_vox.data_ptr(), row_start.data_ptr()
     return tb.io_ref
 
 
 def train_block_forward(tb, n, x_in, x_conv, t_rows, scene_offs, mask1, mask2, nbr, gidx, widx, patch_start, patch_start_host,
-                        tape, scratch, x_out):
+                        tape, scratch, x_out, rows=None):
     """One Block of the training forward on the native executor: every launch issued by the library, one host call.  x_conv is
     what the CPE conv reads (may be x_in); t_rows (B, C) with scene_offs (B + 1) int32: the per-scene timestep rows; mask1 /
-    mask2 (n): stochastic-depth row masks already divided by the keep probability; tape (uint8) keeps what the backward reads."""
+    mask2 (n): stochastic-depth row masks already divided by the keep probability; tape (uint8) keeps what the backward reads.
+    rows = (row_vox (n), row_start (V + 1)) int32: the n rows are the points of V voxels (engine.RowLevel), nbr is the map of the
+    V voxels, the CPE runs on the first row of every voxel and every row adds its voxel's term."""
     ref = _train_block_io(tb, n, x_in, x_conv, t_rows, scene_offs, mask1, mask2, nbr, gidx, widx, patch_start, patch_start_host,
-                          tape, scratch, x_out)
+                          tape, scratch, x_out, rows)
     check(tb.lib().cdseg_train_block_forward(tb.ref, ref, _stream()), "train_block_forward")
     return x_out
 
 
 def train_block_backward(tb, n, x_in, x_conv, t_rows, scene_offs, mask1, mask2, nbr, gidx, widx, patch_start, patch_start_host,
-                         tape, scratch, x_out, dy, dx_in, dx_conv, dt_rows, slab):
+                         tape, scratch, x_out, dy, dx_in, dx_conv, dt_rows, slab, rows=None):
     """Backward of `train_block_forward` (same arguments, the forward's tape): dx_in, dx_conv (None when x_conv is x_in: the conv's
     data gradient is added into dx_in), dt_rows (with t_rows) and the gradient slab (zeroed here by one memset;
     `train_block_grad_views`)."""
     ref = _train_block_io(tb, n, x_in, x_conv, t_rows, scene_offs, mask1, mask2, nbr, gidx, widx, patch_start, patch_start_host,
-                          tape, scratch, x_out)
+                          tape, scratch, x_out, rows)
     _need_gpu(dy, dx_in, slab)
     for t in (dy, dx_in, dx_conv, dt_rows):
         if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
             raise _lib.CdsegError("train_block: gradients are contiguous float32 tensors")
     check(tb.lib().cdseg_train_block_backward(tb.ref, ref, _ptr(dy), _ptr(dx_in), _ptr(dx_conv), _ptr(dt_rows), _ptr(slab),
                                               _stream()), "train_block_backward")
+
+
+def gather_first(x, row_start, variant=None):
+    """out[v] = x[row_start[v]] for the V = row_start.numel() - 1 voxels of a row level; variant "f16" / "bf16": cast to that
+    build's 16-bit type, saturating."""
+    _need_gpu(x, row_start)
+    nv = row_start.numel() - 1
+    out = torch.empty((nv, x.shape[1]), dtype=torch.float32 if variant is None else LP_DTYPES[variant], device=x.device)
+    check(_lib.load(variant).cdseg_gather_first(_ptr(x), _ptr(row_start), _ptr(out), F32 if variant is None else BF16, nv, x.shape[1],
+                                                _stream()), "gather_first")
+    return out
+
+
+def residual_rows(x, a, row_vox, t_rows=None, scene_offs=None, out=None):
+    """out = x + a[row_vox] + t_rows[scene(row)] (fp32, adds rounded separately: bit-equal to torch)."""
+    _need_gpu(x, a, row_vox)
+    out = torch.empty_like(x) if out is None else out
+    check(_lib.load().cdseg_residual_rows(_ptr(x), _ptr(a), _ptr(row_vox), _ptr(t_rows), _ptr(scene_offs),
+                                          0 if t_rows is None else t_rows.shape[0], _ptr(out), x.shape[0], x.shape[1], _stream()),
+          "residual_rows")
+    return out
+
+
+def run_sum(dx, row_start):
+    """out[v] = sum of the rows row_start[v] .. row_start[v + 1] - 1 of dx, ascending (fp32)."""
+    _need_gpu(dx, row_start)
+    nv = row_start.numel() - 1
+    out = torch.empty((nv, dx.shape[1]), dtype=torch.float32, device=dx.device)
+    check(_lib.load().cdseg_run_sum(_ptr(dx), _ptr(row_start), _ptr(out), nv, dx.shape[1], _stream()), "run_sum")
+    return out
+
+
+def scatter_first(g, row_vox, row_start, dx=None):
+    """The conv's data gradient g (one row per voxel) on the first row of every run: added into dx when given, else a new
+    (n, c) tensor whose other rows are zero."""
+    _need_gpu(g, row_vox, row_start)
+    acc = dx is not None
+    if not acc:
+        dx = torch.empty((row_vox.numel(), g.shape[1]), dtype=torch.float32, device=g.device)
+    check(_lib.load().cdseg_scatter_first(_ptr(g), _ptr(row_vox), _ptr(row_start), _ptr(dx), int(acc), dx.shape[0], g.shape[1],
+                                          _stream()), "scatter_first")
+    return dx
 
 
 def _row_out(like, lp_variant):

@@ -76,6 +76,14 @@ _backward): the same products through the same entry points, the torch glue betw
 multiplies, GELU, the timestep rows, gradient zero fills, weight transposes, the fp32 round trips of the AMP path) as HIP row
 kernels, the derived weights of a Block made once per weight version (ops.train_block_prepare).  The CrossBlock, pooling,
 unpooling, stems, heads and criteria are what they are in the default mode, which is unchanged bit for bit.
+
+Mix3D batches (`model.train_mix3d = "rows"`, default "fold"; read at every forward; no effect on a batch without shared
+voxels): a batch element made of two merged scenes has voxels that hold several points.  "fold" runs the network on the first
+point of every voxel and copies its prediction to the others.  "rows" keeps every point as a row - serialization, attention,
+BatchNorm statistics, stochastic depth, pooling, heads, loss - on an `engine.RowLevel` above the plan of the unique voxels; the
+sparse convs (stems, the CPE of the level-0 Blocks, the stale conv input behind the last unpooling) take the voxel as their
+unit: conv(x)[i] = conv_V(x[first])[vox(i)] with today's kernel map, first = the voxel's first point in the caller's order
+(`_conv`, `_spread`; the native Block does the same inside its two calls).  `TrainGraph.last_shared` = (N, V) of the last forward.
 """
 import warnings
 
@@ -458,6 +466,18 @@ class _SceneRows(torch.autograd.Function):
         return torch.stack([dy[o[b]:o[b + 1]].sum(0) for b in range(len(o) - 1)]), None, None
 
 
+TRAIN_MIX3D = ("fold", "rows")
+
+
+def resolve_train_mix3d(model):
+    """model.train_mix3d: "fold" (default) or "rows" (engine.RowLevel: every point of a shared voxel is trained); anything else
+    raises."""
+    tm = getattr(model, "train_mix3d", "fold")
+    if tm not in TRAIN_MIX3D:
+        raise ValueError(f"train_mix3d must be one of {sorted(TRAIN_MIX3D)}, not {tm!r}")
+    return tm
+
+
 TRAIN_BLOCKS = ("autograd", "native")
 
 
@@ -489,7 +509,7 @@ class _NativeBlock(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, tb, idx, x_in, x_conv, t_rows, mask1, mask2, *weights):
-        scene_offs, nbr, gidx, widx, patch_start, psh = idx
+        scene_offs, nbr, gidx, widx, patch_start, psh, rows = idx  # rows: None or (row_vox, row_start) of an engine.RowLevel
         x_in = _c(x_in.float())
         xc = x_in if x_conv is None else _c(x_conv.float())
         t_rows = None if t_rows is None else _c(t_rows.float())
@@ -500,9 +520,11 @@ class _NativeBlock(torch.autograd.Function):
         scratch = torch.empty(scratch_b, dtype=torch.uint8, device=dev)
         x_out = torch.empty_like(x_in)
         ops.train_block_forward(tb, n, x_in, xc, t_rows, scene_offs, mask1, mask2, nbr, gidx, widx, patch_start, psh, tape, scratch,
-                                x_out)
+                                x_out, **({} if rows is None else dict(rows=rows)))
         opt = [t for t in (None if x_conv is None else xc, t_rows, mask1, mask2) if t is not None]
+        opt += [] if rows is None else list(rows)
         ctx.save_for_backward(x_in, tape, scene_offs, nbr, gidx, widx, patch_start, *opt, *weights)
+        ctx.has_rows = rows is not None
         ctx.meta = (tb, list(psh), x_conv is not None, t_rows is not None, mask1 is not None, mask2 is not None, scratch_b, grads_b, len(weights))
         return x_out
 
@@ -516,6 +538,7 @@ class _NativeBlock(torch.autograd.Function):
         t_rows = next(rest) if has_t else None
         mask1 = next(rest) if has_m1 else None
         mask2 = next(rest) if has_m2 else None
+        rows = dict(rows=(next(rest), next(rest))) if ctx.has_rows else {}
         n = x_in.shape[0]
         dev = x_in.device
         dy = _c(dy.float())
@@ -525,7 +548,7 @@ class _NativeBlock(torch.autograd.Function):
         slab = torch.empty(grads_b, dtype=torch.uint8, device=dev)
         scratch = torch.empty(scratch_b, dtype=torch.uint8, device=dev)
         ops.train_block_backward(tb, n, x_in, xc, t_rows, scene_offs, mask1, mask2, nbr, gidx, widx, patch_start, psh, tape, scratch,
-                                 None, dy, dx_in, dx_conv, dt_rows, slab)
+                                 None, dy, dx_in, dx_conv, dt_rows, slab, **rows)
         grads = ops.train_block_grad_views(tb, slab)
         return (None, None, dx_in, dx_conv, dt_rows, None, None, *grads, *([None] * (nw - len(grads))))  # (the 16-bit copies: no gradient)
 
@@ -697,6 +720,8 @@ class TrainGraph:
         self.train_loss = "torch"   # from model.train_loss at every forward
         self.train_norm = "torch"   # from model.train_norm at every forward
         self.train_block = "autograd"  # from model.train_block at every forward
+        self.train_mix3d = "fold"      # from model.train_mix3d at every forward
+        self.last_shared = None        # (N points, V voxels) of the last forward
         self._native = {}  # id(Block) -> [Block, static key, weight versions, ops.TrainBlock] (train_block "native")
 
     # ---------------------------------------------------------------------------------------- pieces
@@ -718,9 +743,23 @@ class TrainGraph:
         keep = 1.0 - rate
         return torch.empty((st.x.shape[0], 1), dtype=torch.float32, device=st.x.device).bernoulli_(keep) / keep
 
+    def _conv(self, lv, x, conv, bias):
+        """Sparse conv of a level's rows.  On a row level (Mix3D, `train_mix3d = "rows"`) the voxel is the conv's unit: it reads
+        the first row of every voxel and returns ONE row per voxel (`_spread` hands it to the voxel's rows)."""
+        if isinstance(lv, _engine.RowLevel):
+            x, lv = x[lv.row_start[:-1].long()], lv.voxels
+        return subm_conv(x, conv.weight, bias, lv.nbr(conv.kernel_size, True), self.mm_variant, self.det)
+
+    def _spread(self, lv, y):
+        """Voxel rows -> the level's rows (the identity below a row level).  The backward adds a voxel's contiguous run in
+        ascending row order in either mode: the atomic-free form costs nothing extra here."""
+        if isinstance(lv, _engine.RowLevel):
+            return _GatherRuns.apply(y, lv.row_vox.long(), lv.row_start, None)
+        return y
+
     def _cpe(self, lv, x, seq):
-        y = subm_conv(x, seq[0].weight, seq[0].bias, lv.nbr(seq[0].kernel_size, True), self.mm_variant, self.det)
-        return self._ln(self._lin(y, seq[1]), seq[2])
+        y = self._conv(lv, x, seq[0], seq[0].bias)
+        return self._spread(lv, self._ln(self._lin(y, seq[1]), seq[2]))
 
     def _lin(self, x, mod):
         return linear(x, mod, self.mm_variant, self.det)
@@ -770,7 +809,9 @@ class TrainGraph:
         m2 = self._mask(st, name + ".drop_path.0", mod.drop_prob, masks)
         m1, m2 = (None if m is None else _c(m.reshape(-1)) for m in (m1, m2))
         tb, params, shadows = self._native_desc(mod)
-        idx = (scene_offs, lv.nbr(mod.cpe[0].kernel_size, True), gidx, widx, patch_start, psh)
+        rows = isinstance(lv, _engine.RowLevel)
+        idx = (scene_offs, (lv.voxels if rows else lv).nbr(mod.cpe[0].kernel_size, True), gidx, widx, patch_start, psh,
+               (lv.row_vox, lv.row_start) if rows else None)
         st.x = _NativeBlock.apply(tb, idx, x, xconv, t_rows, m1, m2, *params, *shadows)
         return st
 
@@ -801,15 +842,16 @@ class TrainGraph:
 
     def _embedding(self, plan, feat, emb, curves, inv0):
         """ref: ptv3.py:633-663.  inv0: caller row -> physical row (the reference's level-0 order is the caller's)."""
-        lv = plan.levels[0]
-        x = feat[plan.perm0.long()]
-        y = subm_conv(x, emb.stem.conv.weight, None, lv.nbr(emb.stem.conv.kernel_size, True), self.mm_variant, self.det)
+        rows = plan.rows
+        lv = plan.levels[0] if rows is None else rows
+        x = feat[(plan.perm0 if rows is None else rows.perm_rows).long()]
+        y = self._spread(lv, self._conv(lv, x, emb.stem.conv, None))
         return _St(lv, _bn_gelu(y, emb.stem.norm, self.train_norm), curves, inv0)
 
     def _pooling(self, plan, st, down, cum_to, perm):
         """ref: ptv3.py:464-555."""
         fine, coarse = st.level, plan.levels[cum_to]
-        cluster, seg = plan.link(fine.cum, cum_to)
+        cluster, seg = plan.link_from(fine, cum_to)
         y = self._lin(st.x, down.proj)
         if self.train_norm == "fused" and y.shape[1] in _NORM_WIDTHS:
             y = _SegmentMaxArg.apply(y, seg, cluster, coarse.n)
@@ -825,7 +867,7 @@ class TrainGraph:
         """ref: ptv3.py:597-630."""
         parent = st.parent
         fine, coarse = parent.level, st.level
-        cluster, seg = plan.link(fine.cum, coarse.cum)
+        cluster, seg = plan.link_from(fine, coarse.cum)
         child = _bn_gelu(self._lin(st.x, up.proj[0]), up.proj[1], self.train_norm)
         par = _bn_gelu(self._lin(parent.x, up.proj_skip[0]), up.proj_skip[1], self.train_norm)
         out = _St(fine, None, parent.curves, parent.ref_order, parent=parent.parent)
@@ -872,6 +914,23 @@ class TrainGraph:
         m = self._mask(nst, name, cb.drop_prob, masks)
         nst.x = x + (h if m is None else h * m)
 
+    def _rows_plan(self, grid, offset_host, keep, rep, offset_u):
+        """The plan of a Mix3D batch in `train_mix3d = "rows"`: today's plan of the V unique voxels (kernel maps, pooled
+        levels) with an engine.RowLevel of all N points above its level 0."""
+        nv = int(keep.numel())
+        plan = self.eng.build_plan(grid[keep], offset_u.to(torch.int64), [int(v) for v in offset_u.cpu().tolist()], nv)
+        vox_of_kept = torch.empty(nv, dtype=torch.long, device=rep.device)  # kept point -> physical voxel row
+        vox_of_kept[plan.perm0.long()] = torch.arange(nv, device=rep.device)
+        plan.rows = _engine.RowLevel(plan.levels[0], vox_of_kept[rep], [0] + [int(v) for v in offset_host])
+        if not getattr(self, "_warned_rows", False):
+            self._warned_rows = True
+            seg = plan.rows.row_start.long()
+            shared = int((seg[1:] - seg[:-1])[(seg[1:] - seg[:-1]) > 1].sum())
+            warnings.warn(f"training batch with {100.0 * shared / rep.numel():.1f} % of its {rep.numel()} points in voxels that "
+                          f"hold more than one point (Mix3D): every point is trained as a row of its own, the sparse convs read "
+                          f"the first point of a voxel (train_mix3d = 'rows', cdsegnet_amd/train_graph.py)")
+        return plan
+
     # ---------------------------------------------------------------------------------------- the forward
     def forward(self, input_dict, draws=None):
         """input_dict: coord, grid_coord, feat, offset, segment on the model's device.  draws (optional, for replaying a
@@ -886,6 +945,7 @@ class TrainGraph:
         kernels), so the trainer's AMP branch runs unchanged: the scaler multiplies an fp32 loss, and only a scaled gradient
         that leaves half's range inside the "fp16-attn" core (non-finite dq / dk / dv) or, under "fp16-amp", in the unsaturated
         cast of a Linear's / conv's dy (non-finite dx / dw / db) shows up as an overflow."""
+        self.train_mix3d = resolve_train_mix3d(self.model)
         tp = getattr(self.model, "train_precision", "fp32")
         if tp not in TRAIN_PRECISIONS:
             raise ValueError(f"train_precision must be one of {sorted(TRAIN_PRECISIONS)}, not {tp!r}")
@@ -925,22 +985,33 @@ class TrainGraph:
             # every voxel, and every folded point reads its representative's prediction - it still enters the loss with its own
             # label, and its gradient flows into the shared row.
             keep, rep, offset_u = voxel_representatives(grid, offset)
-            if not getattr(self, "_warned_duplicates", False):
-                self._warned_duplicates = True
-                warnings.warn(f"training batch with {e.count} points in already occupied voxels (Mix3D): folded onto the "
-                              f"first point of their voxel (cdsegnet_amd/train_graph.py)")
-            feat, coord, grid = feat[keep], coord[keep], grid[keep]
-            n, offset_in = feat.shape[0], offset
-            offset = offset_u
-            offset_host = [int(v) for v in offset.cpu().tolist()]
-            if "noise" in draws:
-                draws = dict(draws, noise=torch.as_tensor(draws["noise"], dtype=torch.float32)[keep.cpu()])
-            plan = self.eng.build_plan(grid, offset.to(torch.int64), offset_host, n)
-        lv0 = plan.levels[0]
+            self.last_shared = (n, int(keep.numel()))
+            if self.train_mix3d == "rows":
+                # ... unless `model.train_mix3d = "rows"`: every point is a row of its own in serialization, attention,
+                # BatchNorm statistics, stochastic depth, pooling and the loss, as in the reference; only the sparse convs
+                # take the voxel as their unit (engine.RowLevel: the plan of the unique voxels with a row level above it)
+                plan = self._rows_plan(grid, offset_host, keep, rep, offset_u)
+                rep = None
+            else:
+                if not getattr(self, "_warned_duplicates", False):
+                    self._warned_duplicates = True
+                    warnings.warn(f"training batch with {e.count} points in already occupied voxels (Mix3D): folded onto the "
+                                  f"first point of their voxel (cdsegnet_amd/train_graph.py)")
+                feat, coord, grid = feat[keep], coord[keep], grid[keep]
+                n, offset_in = feat.shape[0], offset
+                offset = offset_u
+                offset_host = [int(v) for v in offset.cpu().tolist()]
+                if "noise" in draws:
+                    draws = dict(draws, noise=torch.as_tensor(draws["noise"], dtype=torch.float32)[keep.cpu()])
+                plan = self.eng.build_plan(grid, offset.to(torch.int64), offset_host, n)
+        else:
+            self.last_shared = (n, n)
+        lv0 = plan.levels[0] if plan.rows is None else plan.rows
+        perm0 = (plan.perm0 if plan.rows is None else plan.rows.perm_rows).long()  # physical row -> caller row
         inv0 = torch.empty(n, dtype=torch.long, device=dev)
-        inv0[plan.perm0.long()] = torch.arange(n, device=dev)
+        inv0[perm0] = torch.arange(n, device=dev)
         batch0 = torch.empty(n, dtype=torch.long, device=dev)  # batch index in the CALLER's order
-        batch0[plan.perm0.long()] = lv0.batch.long()
+        batch0[perm0] = lv0.batch.long()
         point = {"offset": offset, "loss_mode": "train"}
         base_curves = [_engine.CURVES.index(o) for o in bb.order]
 

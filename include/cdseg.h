@@ -977,6 +977,16 @@ typedef struct cdseg_train_block_io {
   void* scratch;
   size_t scratch_bytes;
   float* x_out;               /* (n, C) */
+  /* The row level above the voxels (a Mix3D batch trained on every point): all zero / NULL = one row per voxel, the executor
+   * above launch for launch.  Otherwise the n rows are in voxel order, the rows of a voxel contiguous, and the sparse conv takes
+   * the voxel as its unit: nbr describes n_conv voxels, the whole CPE (conv, Linear, LayerNorm) runs on the first row of every
+   * voxel and row i adds the CPE term of voxel row_vox[i].  Backward: a voxel's CPE gradient is the sum over its run in
+   * ascending row order, the conv's data gradient lands on the run's first row (the other rows of dx_conv are zero).
+   * Tape and scratch keep their sizes (they are sized by n >= n_conv).  CDSEG_ERR_ARG before any launch: n_conv outside
+   * [1, n], one of the two pointers without the other or without n_conv, a pointer that is not 4-byte aligned. */
+  long n_conv;
+  const int32_t* row_vox;     /* (n): voxel of a row, ascending */
+  const int32_t* row_start;   /* (n_conv + 1): first row of every voxel's run, row_start[n_conv] = n */
 } cdseg_train_block_io;
 int cdseg_train_block_bytes(const cdseg_train_block_desc* desc, long n, long slots, size_t* tape, size_t* scratch,
                             size_t* derived, size_t* grads);
@@ -996,6 +1006,18 @@ int cdseg_train_block_backward(const cdseg_train_block_desc* desc, const cdseg_t
  *   gelu_bwd_cast     du = dg * GELU'(u) in out_dtype WITHOUT saturation */
 int cdseg_residual(const float* x, const float* a, const float* mask, const float* t_rows, const int32_t* scene_offs,
                    int num_scenes, float* out, long n, int c, void* stream);
+/* The row kernels of the row level (io->n_conv above; row_vox (n), row_start (nv + 1) as there):
+ *   gather_first      out[v] = cast(x[row_start[v]]) in out_dtype (saturating), nv rows
+ *   residual_rows     out[i] = x[i] + a[row_vox[i]] + t_rows[scene(i)]   (a: nv rows; t_rows optional; out may be x)
+ *   run_sum           out[v] = 0 + dx[row_start[v]] + ... + dx[row_start[v + 1] - 1], ascending
+ *   scatter_first     accumulate: dx[row_start[v]] += g[v], other rows untouched; else dx[i] = g[row_vox[i]] on the first row of
+ *                     a run and 0 on the others (all n rows written) */
+int cdseg_gather_first(const float* x, const int32_t* row_start, void* out, int out_dtype, long nv, int c, void* stream);
+int cdseg_residual_rows(const float* x, const float* a, const int32_t* row_vox, const float* t_rows, const int32_t* scene_offs,
+                        int num_scenes, float* out, long n, int c, void* stream);
+int cdseg_run_sum(const float* dx, const int32_t* row_start, float* out, long nv, int c, void* stream);
+int cdseg_scatter_first(const float* g, const int32_t* row_vox, const int32_t* row_start, float* dx, int accumulate, long n, int c,
+                        void* stream);
 int cdseg_scale_cast(const float* dy, const float* mask, void* out, int out_dtype, long n, int c, void* stream);
 int cdseg_add_layernorm(const float* x, const float* a, const float* mask, const float* gamma, const float* beta, float eps,
                         float* x1, void* h, int out_dtype, long n, int c, void* stream);

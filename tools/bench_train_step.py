@@ -4,12 +4,15 @@ with a 16-bit attention core, or under AMP (16-bit attention core, Linears and s
 a first number for the training row of SURVEY 8(f4).
 usage: python tools/bench_train_step.py [scenes=1] [points=120000] [steps=4] [dataset=scannet|scannet200|nuscenes]
        [train_precision=fp32|fp16-attn|bf16-attn|fp16-amp|bf16-amp] [det] [fused] [fusednorm] [fusedopt] [shadow] [nativeblock]
+       [mix3d|mix3d-rows]
 A trailing `det` sets train_deterministic = True (fixed-order gradient reductions: bit-reproducible steps), a trailing `fused`
 sets train_loss = "fused" (cross entropy + Lovasz on the HIP loss kernels instead of the torch criteria), a trailing `fusednorm` sets train_norm =
 "fused" (train-mode BatchNorm + GELU and the pooling maximum on the kernels of csrc/norm.hip), a trailing `fusedopt`
 takes cdsegnet_amd.optim.FusedAdamW in torch.optim.AdamW's place, and `shadow` (with `fusedopt` under an AMP precision) lets it
 keep the 16-bit weight copies the forward multiplies with.  A trailing `nativeblock` sets train_block = "native" (every Block one
-autograd node on the executor of csrc/trainblock.hip)."""
+autograd node on the executor of csrc/trainblock.hip).  A trailing `mix3d` merges the scenes pairwise into one batch element each
+(Mix3D: the merged rooms share voxels) and trains them in the default train_mix3d = "fold"; `mix3d-rows` sets train_mix3d =
+"rows" on the same batch (every point a row of its own)."""
 import os, sys, time
 import numpy as np
 import torch
@@ -31,6 +34,7 @@ fusednorm = "fusednorm" in sys.argv[6:]
 fusedopt = "fusedopt" in sys.argv[6:]
 shadow = "shadow" in sys.argv[6:]
 nativeblock = "nativeblock" in sys.argv[6:]
+mix3d = "rows" if "mix3d-rows" in sys.argv[6:] else ("fold" if "mix3d" in sys.argv[6:] else None)
 if shadow and not (fusedopt and train_precision.endswith("-amp")):
     sys.exit("`shadow` needs `fusedopt` and an AMP train_precision (the fp32 step multiplies with the fp32 weights)")
 dev = torch.device("cuda")
@@ -52,6 +56,9 @@ if nativeblock:
 sc = synth.collate([(synth.lidar_scene(i, points) if dataset == "nuscenes" else synth.room_scene(i, points)) for i in range(scenes)])
 inp = {k: torch.as_tensor(sc[k]).to(dev) for k in ("coord", "grid_coord", "feat", "offset")}
 inp["segment"] = (torch.as_tensor(np.asarray(sc["segment"]).astype(np.int64)) % cfg["num_classes"]).to(dev)
+if mix3d is not None:  # point_collate_fn's merge: offset[1:-1:2] + offset[-1]
+    model.train_mix3d = mix3d
+    inp["offset"] = torch.cat([inp["offset"][1:-1:2], inp["offset"][-1:]])
 n = inp["feat"].shape[0]
 named = dict(model.named_parameters())
 groups = [dict(params=[p for k, p in named.items() if "block" not in k], lr=0.002),
@@ -83,6 +90,8 @@ tot = np.array(times).sum(1) * 1e3  # run-to-run spread of the whole step
 print(f"training step, {dataset}, full width, {train_precision}{', deterministic' if deterministic else ''}{', fused loss' if fused else ''}{', fused norm' if fusednorm else ''}{', FusedAdamW' if fusedopt else ''}{' + 16-bit weight copies' if shadow else ''}{', native Blocks' if nativeblock else ''}, {scenes} scene(s), {n} points: forward {t[0]:.1f} ms, backward {t[1]:.1f} ms, "
       f"AdamW {t[2]:.1f} ms = {t.sum():.1f} ms/step (steps {tot.min():.1f} - {tot.max():.1f}) = {n / t.sum() * 1e3 / 1e6:.2f} M points/s; peak memory "
       f"{torch.cuda.max_memory_allocated() / 2**30:.1f} GiB; loss over the steps {[round(v, 4) for v in losses]}")
+if mix3d is not None:
+    print(f"Mix3D, train_mix3d = {mix3d!r}: {len(inp['offset'])} batch element(s), N = %d points in V = %d voxels" % model._train_graph.last_shared)
 if nativeblock:
     tbs = [ent[3] for ent in model._train_graph._native.values()]
     print(f"native Blocks: {len(tbs)} descriptors, persistent derived-weights buffers {sum(tb.derived_bytes for tb in tbs) / 2**20:.1f} MiB "
