@@ -166,6 +166,8 @@ SIGNATURES = {
     "cdseg_pad_plan": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_long, c_void_p, c_void_p, c_void_p]),
     "cdseg_pad_plan_batch": (c_int, [c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int),
                                      POINTER(c_long), c_int, c_void_p, c_void_p, c_void_p]),
+    "cdseg_slots_select": (c_int, [POINTER(c_void_p), POINTER(c_void_p), c_int, c_void_p, c_int, c_char_p, c_long, c_void_p,
+                                   c_void_p, c_void_p]),
     "cdseg_plan_begin_layout": (c_int, [POINTER(PlanSpec), c_long, c_int, POINTER(c_long), POINTER(c_long)]),
     "cdseg_plan_begin": (c_int, [POINTER(PlanSpec), POINTER(PlanBeginIO), c_int, c_void_p]),
     "cdseg_plan_finish_layout": (c_int, [POINTER(PlanSpec), c_long, c_int, POINTER(c_long), POINTER(c_int), POINTER(c_long),

@@ -478,6 +478,32 @@ __global__ void pad_plan_batch_kernel(PadBatchP b, int32_t* __restrict__ gidx, i
   widx[t] = real ? g : -1;
 }
 
+// slot plan of a collated batch whose elements read DIFFERENT curves: padded slot s of batch element b takes its entry
+// from the slot plan of curve choice[b] (all sources are slot plans of the same level and patch key, so slot s means the
+// same position in each).  The choices travel in the launch arguments; plain 4-byte accesses (the sources are arena views)
+struct SlotsSelectP {
+  const int32_t* g[4];
+  const int32_t* w[4];
+  unsigned char choice[CDSEG_SLOTS_SELECT_MAX];
+  int nb;
+};
+
+__global__ void slots_select_kernel(SlotsSelectP p, const int32_t* __restrict__ offs_pad, long n_pad,
+                                    int32_t* __restrict__ gidx, int32_t* __restrict__ widx) {
+  const long s = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n_pad) return;
+  int lo = 0, hi = p.nb - 1;  // first batch element with offs_pad[e+1] > s
+  while (lo < hi) {
+    int mid = (lo + hi) >> 1;
+    if (offs_pad[mid + 1] > s) hi = mid; else lo = mid + 1;
+  }
+  const int c = p.choice[lo];
+  const int32_t* g = c == 0 ? p.g[0] : c == 1 ? p.g[1] : c == 2 ? p.g[2] : p.g[3];
+  const int32_t* w = c == 0 ? p.w[0] : c == 1 ? p.w[1] : c == 2 ? p.w[2] : p.w[3];
+  gidx[s] = g[s];
+  widx[s] = w[s];
+}
+
 inline dim3 grid1d(long n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
 
 }  // namespace
@@ -857,6 +883,31 @@ int cdseg_pad_plan_batch(int count, const int32_t* const* orders, const int32_t*
   }
   if (b.start[count] == 0) return CDSEG_OK;
   hipLaunchKernelGGL(pad_plan_batch_kernel, grid1d(b.start[count]), dim3(256), 0, (hipStream_t)stream, b, gidx, widx);
+  CDSEG_CHECK_LAUNCH();
+  return CDSEG_OK;
+}
+
+// out[s] = src[choice[b(s)]][s] for every padded slot s of batch element b: the slot plan of a collated batch whose
+// elements read different curves, composed from the per-curve slot plans of one level and patch key.
+int cdseg_slots_select(const int32_t* const* gidx_src, const int32_t* const* widx_src, int nsrc, const int32_t* offs_pad,
+                       int nb, const unsigned char* choice_host, long n_pad, int32_t* gidx, int32_t* widx, void* stream) {
+  if (!gidx_src || !widx_src || !choice_host || nsrc < 1 || nsrc > 4 || nb <= 0 || n_pad < 0) return CDSEG_ERR_ARG;
+  if (nb > CDSEG_SLOTS_SELECT_MAX) return CDSEG_ERR_UNSUPPORTED;
+  SlotsSelectP p;
+  for (int c = 0; c < 4; ++c) {
+    p.g[c] = c < nsrc ? gidx_src[c] : nullptr;
+    p.w[c] = c < nsrc ? widx_src[c] : nullptr;
+  }
+  for (int b = 0; b < CDSEG_SLOTS_SELECT_MAX; ++b) p.choice[b] = 0;
+  for (int b = 0; b < nb; ++b) {
+    const int c = choice_host[b];
+    if (c >= nsrc || !p.g[c] || !p.w[c]) return CDSEG_ERR_ARG;  // a chosen source must exist
+    p.choice[b] = (unsigned char)c;
+  }
+  p.nb = nb;
+  if (n_pad == 0) return CDSEG_OK;
+  if (!offs_pad || !gidx || !widx) return CDSEG_ERR_ARG;
+  hipLaunchKernelGGL(slots_select_kernel, grid1d(n_pad), dim3(256), 0, (hipStream_t)stream, p, offs_pad, n_pad, gidx, widx);
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
 }

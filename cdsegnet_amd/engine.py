@@ -43,14 +43,15 @@ class _ShareEvents(threading.local):
 SHARE_EVENTS = _ShareEvents()
 
 
-def _shared(cache, key, build):
+def _shared(cache, key, build, force=False):
     """Lazily built plan item shared by the two branch streams: the builder's stream records an event, a consumer
-    on the other stream waits for it (the item itself lives as long as the plan)."""
+    on the other stream waits for it (the item itself lives as long as the plan).  force: the item belongs to a plan that
+    outlives one forward (Engine.shared_plan) - whichever stream of whichever forward builds it records the event."""
     ent = cache.get(key)
     cur = ops.current_stream_id()
     if ent is None:
         val = build()
-        ent = cache[key] = (val, cur, ops.record_event() if (cur is not None and SHARE_EVENTS.on) else None)
+        ent = cache[key] = (val, cur, ops.record_event() if (cur is not None and (SHARE_EVENTS.on or force)) else None)
     elif ent[1] != cur and ent[2] is not None:
         ops.wait_event(ent[2])
     return ent[0]
@@ -80,6 +81,7 @@ class Level:
         self._gbc_lazy = lazy
         self.offs_host = offs_host  # (B+1) python ints
         self.parent = None  # (parent Level, (cluster, seg_start)) when the next pooled level is one octree step up
+        self.shared = False  # the level of a plan that outlives one forward (Plan.share): lazy items always carry an event
         self._order = {}
         self._nbr = {}
         self._pad = {}
@@ -121,7 +123,7 @@ class Level:
             nb = len(self.offs_host) - 1
             end_bit = min(64, 3 * self.depth + max(1, nb.bit_length()))
             return ops.sort_pairs(self.code4[curve], None, end_bit=end_bit)[1]
-        return _shared(self._order, curve, build)
+        return _shared(self._order, curve, build, self.shared)
 
     def nbr(self, ksize, kmajor=False):
         # offset-major tables: a wave searches one offset of 64 consecutive z-ordered points (same cache lines);
@@ -135,7 +137,7 @@ class Level:
                 return ops.nbr_table_from_info(self.grid, cluster, par.nbr(3, True), self.child_info(), par.n, self.depth,
                                                ksize, kmajor)
             return ops.nbr_table(self.code4[0], self.grid, self.batch, self.depth, ksize, kmajor)
-        return _shared(self._nbr, (ksize, kmajor), build)
+        return _shared(self._nbr, (ksize, kmajor), build, self.shared)
 
     def child_info(self):
         """Per parent cell of this level's points: first child row + octant occupancy (the stem kernel's traversal)."""
@@ -145,7 +147,7 @@ class Level:
         def build():
             par, (_, seg) = self.parent
             return ops.child_info(self.code4[0], seg, par.n)
-        return _shared(self._nbr, "child_info", build)
+        return _shared(self._nbr, "child_info", build, self.shared)
 
     def pad_host_py(self, patch_size, enable_flash):
         """Host side of the padding plan (ref: ptv3.py:188-250) in plain Python ints - a scene has a handful of batch
@@ -195,6 +197,21 @@ class Level:
         return sum_l2 - float(K) * (n_pad - self.n)
 
     def slots(self, curve, patch_size, enable_flash):
+        """(gidx, widx) of the attention slots on `curve`: a curve index, or a tuple of curve indices, one per batch element
+        (every element of a collated batch under its own order shuffle) - then the pair is composed element by element from
+        the per-curve slot plans (cdseg_slots_select) and cached under the tuple."""
+        if isinstance(curve, tuple):
+            if len(curve) != len(self.offs_host) - 1:
+                raise ValueError(f"{len(curve)} curves for a batch of {len(self.offs_host) - 1} elements")
+            if len(set(curve)) == 1:
+                return self.slots(curve[0], patch_size, enable_flash)
+
+            def compose():
+                _, n_pad, _, offs_pad = self.pad(patch_size, enable_flash)[:4]
+                used = set(curve)
+                srcs = [self.slots(c, patch_size, enable_flash) if c in used else None for c in range(max(used) + 1)]
+                return ops.slots_select(srcs, offs_pad, curve, n_pad)
+            return _shared(self._slots, (curve, patch_size, enable_flash), compose, self.shared)
         lz = self._slot_lazy.pop((curve, patch_size, enable_flash), None) if self._slot_lazy else None
         if lz is not None:
             A, go, wo, n_pad, sid = lz
@@ -203,7 +220,7 @@ class Level:
         def build():
             K, n_pad, offs, offs_pad = self.pad(patch_size, enable_flash)[:4]
             return ops.pad_plan(self.order(curve), offs, offs_pad, K, n_pad)
-        return _shared(self._slots, (curve, patch_size, enable_flash), build)
+        return _shared(self._slots, (curve, patch_size, enable_flash), build, self.shared)
 
 
 class RowLevel(Level):
@@ -238,6 +255,28 @@ class Plan:
         self._row_links = {}
         self._finish = None  # Engine.build_plan(defer_pads=True): the padding / slot plans, not built yet
         self._link_lazy = {}
+        # a plan that outlives one forward (Engine.shared_plan): finished on the stream that built it, `ready` recorded there,
+        # every consuming stream waits for `ready` once (`_waited`); an item still built lazily afterwards records its own
+        # event whatever SHARE_EVENTS says.  `source` = the (grid_coord, offset) tensors it was built from (no copies)
+        self.shared = False
+        self.ready = self.stream = self.source = None
+        self._waited = set()
+
+    def share(self, source):
+        """Mark the plan as shared: call on the building stream once everything a forward touches has been built."""
+        self.shared = True
+        for lv in self.levels.values():
+            lv.shared = True
+        self.source = source
+        self.stream = ops.current_stream_id()
+        self.ready = ops.record_event() if self.stream is not None else None
+
+    def join(self):
+        """A forward on the bound stream is about to read the plan: wait for `ready` (once per stream)."""
+        cur = ops.current_stream_id()
+        if self.ready is not None and cur != self.stream and cur not in self._waited:
+            ops.wait_event(self.ready)
+            self._waited.add(cur)
 
     def finish_pads(self):
         """Build the deferred padding / slot plans (no-op when build_plan already did).  Called on the stream the plan was
@@ -258,7 +297,7 @@ class Plan:
                 return ops.link_derive(cl0a, seg0a, la.n, cl0b, seg0b, lb.n)
             cluster, seg, _ = ops.pool_level(la.code4[0], 3 * (lb.cum - la.cum))
             return (cluster, seg)
-        return _shared(self.links, (a, b), build)
+        return _shared(self.links, (a, b), build, self.shared)
 
     def link_from(self, fine, b):
         """`link(fine.cum, b)` for a Level object; from the row level it is two gathers of the voxel level's link: a row
@@ -270,11 +309,32 @@ class Plan:
             cluster, seg = self.link(0, b)
             m = self.levels[b].n
             return (cluster[fine.row_vox.long()], fine.row_start[seg[:m + 1].long()])
-        return _shared(self._row_links, b, build)
+        return _shared(self._row_links, b, build, self.shared)
+
+
+def _per_element(perm):
+    """Is `perm` a list of permutations (one per batch element) rather than one permutation?"""
+    return perm is not None and len(perm) > 0 and hasattr(perm[0], "__len__") and np.ndim(perm[0]) == 1
+
+
+def reshuffle_curves(curves, perm, nb):
+    """The order shuffle `[curves[j] for j in perm]` (ref: ptv3.py:493-496, structure.py:92-99).  `curves`: per order index
+    a curve index or a tuple of `nb` curve indices, one per batch element.  `perm`: None (no shuffle), one permutation (the
+    whole batch, the reference's collated forward), or `nb` permutations - element b's applies to element b's entries, which
+    is what `nb` single forwards under those draws do."""
+    if perm is None:
+        return curves
+    if not _per_element(perm):
+        return [curves[int(j)] for j in perm]
+    if len(perm) != nb:
+        raise ValueError(f"{len(perm)} permutations for a batch of {nb} elements")
+    return [tuple(c[b] if isinstance(c, tuple) else c for b, c in ((b, curves[int(perm[b][i])]) for b in range(nb)))
+            for i in range(len(curves))]
 
 
 class State:
-    """A branch's activations at one level."""
+    """A branch's activations at one level: x fp32 residual stream, xc its T-typed shadow, curves[i] = the curve order index i
+    reads - a curve index, or a tuple of them (one per batch element: per-fragment draws)."""
 
     def __init__(self, level, x, xc, curves):
         self.level, self.x, self.xc, self.curves = level, x, xc, curves
@@ -343,6 +403,7 @@ class Engine:
         self._sat = None
         self.exact_attention_core = False  # budget tool only: fp32 attention core inside a 16-bit trunk (binding path)
         self._pad_keys = None
+        self.plans_built = 0  # plans build_plan has produced (a forward that is handed a plan builds none)
         self.native_plan = True  # build_plan through cdseg_plan_begin / cdseg_plan_finish (False: one binding call per step; tools A/B)
         self._plan_specs = {}
         self._tb_cache = {}  # timestep -> per-Block bias vectors (_t_bias)
@@ -743,7 +804,7 @@ class Engine:
             true_depth = int(gmax_host.item()).bit_length()
             self._depth_hint[grid.device] = true_depth
             if true_depth != depth:  # the guess was wrong: everything built so far used the wrong code width
-                return self.build_plan(grid, offset_dev, offset_host, n, _exact_depth=true_depth)
+                return self._build_plan(grid, offset_dev, offset_host, n, _exact_depth=true_depth)
         if flat[-1]:
             raise DuplicateVoxelsError(
                 f"input has {flat[-1]} duplicate voxels (points sharing (batch, grid_coord) with another "
@@ -815,6 +876,13 @@ class Engine:
         return plan
 
     def build_plan(self, grid, offset_dev, offset_host, n, _exact_depth=None, while_device_works=None, defer_pads=False):
+        """The plan of one forward (`_build_plan`), counted in `plans_built`."""
+        plan = self._build_plan(grid, offset_dev, offset_host, n, _exact_depth, while_device_works, defer_pads)
+        with self._work_lock:
+            self.plans_built += 1
+        return plan
+
+    def _build_plan(self, grid, offset_dev, offset_host, n, _exact_depth=None, while_device_works=None, defer_pads=False):
         """Serialization, pooled levels, kernel-map sources, padding / slot plans of one forward.
         Host reads: ONE in steady state (round 5) - the pooled sizes.  The serialization depth (`int(grid_coord.max())
         .bit_length()`, structure.py:66: the reference's first host sync) is taken from the previous call's plan, the grid
@@ -918,7 +986,7 @@ class Engine:
                 true_depth = int(gmax_host.item()).bit_length()
                 self._depth_hint[grid.device] = true_depth
                 if true_depth != depth:  # the guess was wrong: everything built so far used the wrong code width
-                    return self.build_plan(grid, offset_dev, offset_host, n, _exact_depth=true_depth, defer_pads=defer_pads)
+                    return self._build_plan(grid, offset_dev, offset_host, n, _exact_depth=true_depth, defer_pads=defer_pads)
                 gmax_host = None
             if flat[-1]:
                 # the model's input contract (GridSample upstream, structure.py:39-102 downstream): one point per voxel.
@@ -962,7 +1030,7 @@ class Engine:
             true_depth = int(gmax_dev.item()).bit_length()
             self._depth_hint[grid.device] = true_depth
             if true_depth != depth:
-                return self.build_plan(grid, offset_dev, offset_host, n, _exact_depth=true_depth, defer_pads=defer_pads)
+                return self._build_plan(grid, offset_dev, offset_host, n, _exact_depth=true_depth, defer_pads=defer_pads)
         def finish_pads():
             # every padding plan the model will ask for, uploaded with ONE host->device copy
             if self._pad_keys is None:  # static per model: walk the module tree once
@@ -1007,6 +1075,93 @@ class Engine:
         else:
             finish_pads()
         return plan
+
+    # -- a plan that outlives one forward ---------------------------------------------------------------
+    def shared_plan(self, input_dict):
+        """The plan of `input_dict`'s geometry - built from grid_coord, offset and offset_host and nothing else - for any
+        number of forwards (`inference(..., plan=)`): the fragments of one test-time augmentation hold one point per voxel
+        over the same voxels in the same row order, so they share it.  Finished here, on the calling stream: the padding /
+        slot plans and every order, kernel map, child-info word and link the model's forward touches (a static list per
+        model, `_touch_plan`), then ONE event; every consuming stream waits for it once (Plan.join).  The plan's tensors
+        belong to the calling stream's allocator pool: keep the plan alive until the consuming streams have been joined
+        (inference_many joins its lanes before it returns)."""
+        grid, offset = input_dict["grid_coord"], input_dict["offset"]
+        dev = grid.device
+        try:
+            with _lib.use(self.variant):
+                self.prepare(dev)
+                if dev.type == "cuda" and hasattr(ops, "bind_stream"):
+                    ops.bind_stream()
+                n = grid.shape[0]
+                offset_host = [int(v) for v in input_dict["offset_host"]] if "offset_host" in input_dict else None
+                plan = self.build_plan(grid, offset.to(torch.int64), offset_host, n)
+                share, SHARE_EVENTS.on = SHARE_EVENTS.on, False  # one stream, one event for everything: `ready`
+                try:
+                    self._touch_plan(plan)
+                finally:
+                    SHARE_EVENTS.on = share
+                plan.share((grid, offset))
+        finally:
+            if hasattr(ops, "unbind_stream"):
+                ops.unbind_stream()
+        return plan
+
+    def _touch_plan(self, plan):
+        """Build (or cut out of the arenas) every plan item a forward of this model reads - what run_embedding, run_pooling,
+        run_block, run_unpooling and run_cross_block ask for, on any order shuffle."""
+        bb, w = self.model.backbone, self.w
+        plan.finish_pads()
+        curves = sorted({CURVES.index(o) for o in bb.order})
+        lv0 = plan.levels[0]
+        stems = ["n_emb"] + (["c_emb"] if bb.condition else [])
+        if any((pre + ".wimg") in w for pre in stems) and lv0.parent is not None and lv0.n < (1 << 24):
+            lv0.parent[0].nbr(3, True)
+            lv0.child_info()
+        if not all((pre + ".wimg") in w for pre in stems) or lv0.parent is None or lv0.n >= (1 << 24):
+            lv0.nbr(5, True)
+
+        def attn(lv, patch, flash):
+            lv.pad(patch, flash)
+            for c in curves:
+                lv.slots(c, patch, flash)
+
+        def stage(mods, lv):
+            lv.nbr(3, True)
+            for name, mod in mods._modules.items():
+                if name.startswith("block"):
+                    attn(lv, mod.attn.patch_size, mod.attn.enable_flash)
+
+        for branch, cum, ns in (("n", plan.n_cum, bb.n_num_stages),) + ((("c", plan.c_cum, bb.c_num_stages),) if bb.condition else ()):
+            for s in range(ns):
+                if s > 0:
+                    plan.link(cum[s - 1], cum[s])
+                stage(getattr(getattr(bb, f"_{branch}_enc"), f"enc{s}"), plan.levels[cum[s]])
+            for s in range(ns - 1):
+                stage(getattr(getattr(bb, f"_{branch}_dec"), f"dec{s}"), plan.levels[cum[s]])
+        if bb.condition:
+            att = bb._tm_dec0.cross_block2.attn
+            for lv in (plan.levels[plan.n_cum[-1]], plan.levels[plan.c_cum[-1]]):
+                lv.nbr(3, True)
+                attn(lv, att.q_patch_size, att.enable_flash)
+
+    def _check_plan(self, plan, input_dict, n, offset_host):
+        """A forward was handed a plan: its level-0 size and per-element offsets against the input's HOST values (no device
+        read); with `model.check_shared_geometry` also the grid and the offsets themselves (one host read)."""
+        lv0 = plan.levels[0]
+        if lv0.n != n:
+            raise CdsegError(f"the plan was built for {lv0.n} points, the input has {n}")
+        if offset_host is not None and list(lv0.offs_host[1:]) != list(offset_host):
+            raise CdsegError(f"the plan was built for batch offsets {list(lv0.offs_host[1:])}, the input has {list(offset_host)}")
+        if getattr(self.model, "check_shared_geometry", False):
+            if plan.source is None:
+                raise CdsegError("check_shared_geometry: the plan does not come from shared_plan")
+            grid, offset = input_dict["grid_coord"], input_dict["offset"]
+            src_grid, src_offset = plan.source
+            same = (grid.shape == src_grid.shape and offset.shape == src_offset.shape and
+                    bool(torch.equal(grid.to(src_grid.dtype), src_grid)) and
+                    bool(torch.equal(offset.to(src_offset.dtype), src_offset)))
+            if not same:
+                raise CdsegError("check_shared_geometry: grid_coord / offset differ from the ones the plan was built from")
 
     # ------------------------------------------------------------------ layers
     def _buf(self, rows, cols, dtype):
@@ -1221,7 +1376,7 @@ class Engine:
             ops.segment_max(y, seg, coarse.n, w[pre + ".bn.scale"], w[pre + ".bn.shift"], ops.ACT_GELU, x,
                             None if xc is x else xc)
         self._sat_note(xc)
-        curves = st.curves if perm is None else [st.curves[int(j)] for j in perm]
+        curves = reshuffle_curves(st.curves, perm, len(coarse.offs_host) - 1)
         out = State(coarse, x, xc, curves)
         out.parent = st
         return out
@@ -1420,6 +1575,29 @@ class Engine:
         d["rng_base"] = self.reserve_rng()
         return d
 
+    def predraw_fragments(self, input_dict, noise_level=None):
+        """The draws of ONE collated forward over k fragments that share geometry, as k single forwards take them: the
+        concatenation of k `predraw` calls in fragment order (torch's CPU generator ends where k single forwards leave it).
+        feat_noise / noise are row-concatenated, every draw position holds k permutations (one per batch element: the
+        composed slot plans of Level.slots give every fragment its own shuffle), and with noise_source = "device" every
+        fragment's rows come from its own reserved stream ids (`rng_bases`)."""
+        if not input_dict.get("shared_geometry"):
+            raise ValueError("per-fragment draws are defined for a batch whose elements share geometry (the fragments of one "
+                             "test-time augmentation: TestScene.collated marks them)")
+        feat = input_dict["feat"]
+        ends = [int(v) for v in input_dict["offset_host"]]
+        k, m = len(ends), ends[0]
+        if ends != [m * (j + 1) for j in range(k)] or feat.shape[0] != k * m:
+            raise ValueError(f"elements that share geometry have the same number of points, got offsets {ends}")
+        ds = [self.predraw({"feat": feat[j * m:(j + 1) * m]}, noise_level) for j in range(k)]
+        d = {"per_fragment": True, "rng_base": ds[0]["rng_base"], "rng_bases": [x["rng_base"] for x in ds]}
+        for key in ("feat_noise", "noise"):
+            if key in ds[0]:
+                d[key] = None if ds[0][key] is None else torch.cat([x[key] for x in ds], 0)
+        if "perms" in ds[0]:
+            d["perms"] = [[x["perms"][p] for x in ds] for p in range(len(ds[0]["perms"]))]
+        return d
+
     def _add_work(self, flops, nbytes=0.0):
         with self._work_lock:
             self.attn_work += flops
@@ -1447,29 +1625,39 @@ class Engine:
 
     def _device_randn(self, shape):
         seed = torch.initial_seed()
-        out = ops.randn(shape, seed, self._tls.rng, self.device)
+        bases = getattr(self._tls, "rng_frag", None)
+        if bases:
+            # per-fragment draws: the rows of fragment j come from fragment j's own reserved stream ids, as its own forward
+            # would draw them (k small launches; the cursor counts the draws of this forward)
+            step, rows = self._tls.rng - bases[0], shape[0] // len(bases)
+            out = torch.empty(tuple(shape), dtype=torch.float32, device=self.device)
+            for j, b in enumerate(bases):
+                ops.randn((rows,) + tuple(shape[1:]), seed, b + step, self.device, out=out[j * rows:(j + 1) * rows])
+        else:
+            out = ops.randn(shape, seed, self._tls.rng, self.device)
         self._tls.rng += 1
         return out
 
     # ------------------------------------------------------------------ forward
-    def inference(self, input_dict, noise_level=None, draws=None):
-        """Single-step inference (ref: default.py:371-422)."""
+    def inference(self, input_dict, noise_level=None, draws=None, plan=None):
+        """Single-step inference (ref: default.py:371-422).  plan: a `shared_plan` of this input's geometry - the forward
+        then builds no plan and reads nothing from the device."""
         prev = ops.set_f32x3(self.x3) if hasattr(ops, "set_f32x3") else None
         try:
             with _lib.use(self.variant):
-                return self._inference(input_dict, noise_level, draws)
+                return self._inference(input_dict, noise_level, draws, plan)
         finally:
             if prev is not None:
                 ops.set_f32x3(prev)
             if hasattr(ops, "unbind_stream"):
                 ops.unbind_stream()
 
-    def inference_ddim(self, input_dict, step=1, mode="avg", noise_level=None, draws=None):
+    def inference_ddim(self, input_dict, step=1, mode="avg", noise_level=None, draws=None, plan=None):
         """Multi-step inference MSAI (mode="avg") / MSFI ("final") (ref: default.py:278-369)."""
         prev = ops.set_f32x3(self.x3) if hasattr(ops, "set_f32x3") else None
         try:
             with _lib.use(self.variant):
-                return self._inference_ddim(input_dict, step, mode, noise_level, draws)
+                return self._inference_ddim(input_dict, step, mode, noise_level, draws, plan)
         finally:
             if prev is not None:
                 ops.set_f32x3(prev)
@@ -1477,7 +1665,7 @@ class Engine:
                 ops.unbind_stream()
 
     # -- shared set-up -------------------------------------------------------------------------------
-    def _setup(self, input_dict, noise_level, draws, n_backbone_calls, always_noise=False):
+    def _setup(self, input_dict, noise_level, draws, n_backbone_calls, always_noise=False, plan=None):
         m, bb = self.model, self.model.backbone
         feat = input_dict["feat"]
         dev = feat.device  # CPU tensors are rejected by every op (cdsegnet_amd.ops): no CPU fallback
@@ -1504,8 +1692,18 @@ class Engine:
             self._tls.rng = (d["rng_base"] if "rng_base" in d
                              else self.reserve_rng(max(self.RNG_RESERVE, 2 + n_backbone_calls)))
 
-        plan = self.build_plan(grid, offset.to(torch.int64), offset_host, n, while_device_works=host_draws, defer_pads=True)
+        if plan is None:
+            plan = self.build_plan(grid, offset.to(torch.int64), offset_host, n, while_device_works=host_draws, defer_pads=True)
+        else:  # a plan that outlives one forward (shared_plan): nothing is built and nothing is read here
+            self._check_plan(plan, input_dict, n, offset_host)
+            plan.join()
+            host_draws()
         draws = box["draws"]
+        self._tls.rng_frag = draws.get("rng_bases")  # per-fragment draws (predraw_fragments): one device-RNG window per element
+        per_fragment = draws.get("per_fragment") or (bb.shuffle_orders and any(_per_element(p) for p in draws["perms"]))
+        if per_fragment and not input_dict.get("shared_geometry"):
+            raise ValueError("per-fragment draws are defined for a batch whose elements share geometry (the fragments of one "
+                             "test-time augmentation: TestScene.collated marks them)")
         feat = feat.float().contiguous()
         if noise_level is not None:  # ref: default.py:373-374 (perturbs feat and rebinds it in input_dict)
             fn = draws.get("feat_noise")
@@ -1552,9 +1750,9 @@ class Engine:
             self.saturation_count = int(self._sat.item())  # (diagnostic mode: one host read)
             self._sat = None
 
-    def _inference(self, input_dict, noise_level=None, draws=None):
+    def _inference(self, input_dict, noise_level=None, draws=None, plan=None):
         m, bb = self.model, self.model.backbone
-        feat, draws, perms, plan, _ = self._setup(input_dict, noise_level, draws, 1)
+        feat, draws, perms, plan, _ = self._setup(input_dict, noise_level, draws, 1, plan=plan)
         n, dev = feat.shape[0], feat.device
         c_ch = m.c_in_channels
         c_feat = c_perm = None
@@ -1575,14 +1773,15 @@ class Engine:
         self._sat_end()
         return logits
 
-    def _inference_ddim(self, input_dict, step, mode, noise_level, draws):
+    def _inference_ddim(self, input_dict, step, mode, noise_level, draws, plan=None):
         m, bb = self.model, self.model.backbone
         if not bb.condition:
-            return self._inference(input_dict, noise_level, draws)
+            return self._inference(input_dict, noise_level, draws, plan)
         if m.dm_target != "noise":
             raise NotImplementedError("dm_target other than 'noise'")
         schedule = np.linspace(-1, m.T - 1, num=step + 1, dtype=int)[::-1]  # ref: default.py:224-226
-        feat, draws, perms, plan, per_call = self._setup(input_dict, noise_level, draws, len(schedule), always_noise=True)
+        feat, draws, perms, plan, per_call = self._setup(input_dict, noise_level, draws, len(schedule), always_noise=True,
+                                                         plan=plan)
         n, dev = feat.shape[0], feat.device
         nz = draws.get("noise")
         # the plan (codes, orders, kernel maps, slot plans) is step-invariant: built once, unlike the reference
@@ -1623,8 +1822,10 @@ class Engine:
         pi = iter(perms)
         base_curves = [CURVES.index(o) for o in bb.order]
 
+        nb = len(plan.levels[0].offs_host) - 1
+
         def shuffled(perm):
-            return list(base_curves) if perm is None else [base_curves[int(j)] for j in perm]
+            return reshuffle_curves(list(base_curves), perm, nb)
 
         n_cum, c_cum = plan.n_cum, plan.c_cum
         if cond:

@@ -463,6 +463,9 @@ class DefaultSegmentorV2(nn.Module):
         # diagnostic (IEEE-half trunk): count clamped activations during `inference` (a few extra launches and one host
         # read per call; off by default) -> engine().saturation_count / .saturation_checked after the call
         self.count_saturation = False
+        # a forward that is handed a plan (`plan=`) compares its grid_coord and offset with the ones the plan was built from
+        # and raises CdsegError on a difference: one host read per forward, so off by default
+        self.check_shared_geometry = False
         self._engine = None
 
     # -- engine cache management -------------------------------------------------------------
@@ -487,12 +490,14 @@ class DefaultSegmentorV2(nn.Module):
 
     # -- reference API -----------------------------------------------------------------------
     @torch.no_grad()
-    def inference(self, input_dict, eval=True, noise_level=None, draws=None):
+    def inference(self, input_dict, eval=True, noise_level=None, draws=None, plan=None):
         """ref: default.py:371-422.  Returns dict(seg_logits=(N, num_classes) fp32 on the input's device).
         ``draws`` (optional) injects the random draws: dict(noise=(N,c_in) tensor, perms=[8 x (4,)],
         feat_noise=(N,C) when noise_level is set); by default they are drawn from torch's CPU generator in
-        the reference's consumption order, so ``torch.manual_seed`` reproduces the reference bit-for-bit."""
-        logits = self.engine().inference(input_dict, noise_level=noise_level, draws=draws)
+        the reference's consumption order, so ``torch.manual_seed`` reproduces the reference bit-for-bit.
+        ``plan`` (optional): the result of ``model.plan`` on an input of the same geometry - the forward then builds no
+        plan and makes no host read; same logits, bit for bit."""
+        logits = self.engine().inference(input_dict, noise_level=noise_level, draws=draws, plan=plan)
         if eval:
             # ref: default.py:414-420 - the criteria in "eval" mode on the n-branch prediction only (the MSE term finds no
             # c_pred and contributes 0.0, losses/misc.py:53-54): cross entropy + Lovasz, summed whatever the loss_type
@@ -502,7 +507,16 @@ class DefaultSegmentorV2(nn.Module):
         return dict(seg_logits=logits)
 
     @torch.no_grad()
-    def inference_many(self, input_dicts, lanes=4, noise_level=None, draws=None, threads=False, batch=1):
+    def plan(self, input_dict):
+        """The integer side of a forward - curve codes and orders, pooled levels, kernel maps, padding tables, slot plans -
+        built once from ``grid_coord``, ``offset`` and ``offset_host`` for every forward over that geometry
+        (``inference(..., plan=)``, ``inference_many(..., plans=)``): all fragments of one test-time augmentation hold one
+        point per voxel over the same voxels in the same row order.  Keep the plan alive until the streams that consume it
+        have been joined.  ``engine().plans_built`` counts the plans built so far."""
+        return self.engine().shared_plan(input_dict)
+
+    @torch.no_grad()
+    def inference_many(self, input_dicts, lanes=4, noise_level=None, draws=None, threads=False, batch=1, plans=None):
         """Throughput form of ``inference`` for a sequence of INDEPENDENT scenes (the tester's loop over scenes /
         fragments, ref: engines/test.py:197-279): scene i runs on HIP stream ``lane[i % lanes]``, so up to ``lanes``
         scenes are in flight on the GPU.  The deep, latency-bound stages of one scene (a few hundred points, tens of
@@ -516,6 +530,8 @@ class DefaultSegmentorV2(nn.Module):
         GPU): launches and host work per scene drop by ``batch``.  A batched scene gets the logits the reference
         gives it inside that batch (the serialization depth and the order shuffles are per batch), not bit-for-bit
         those of a stand-alone call.
+        ``plans`` (optional): one ``model.plan`` result per forward (per collated group when ``batch`` > 1; the same plan
+        object may appear many times), built on the caller's current stream.
         Returns the list of output dicts (one per input scene), valid on the caller's current stream."""
         dicts = list(input_dicts)
         if not dicts:
@@ -523,7 +539,7 @@ class DefaultSegmentorV2(nn.Module):
         if batch > 1:
             groups = [dicts[i:i + batch] for i in range(0, len(dicts), batch)]
             outs = self.inference_many([collate_device(g) for g in groups], lanes=lanes, noise_level=noise_level,
-                                       draws=draws, threads=threads)
+                                       draws=draws, threads=threads, plans=plans)
             res = []
             for g, o in zip(groups, outs):
                 pos = 0
@@ -535,8 +551,8 @@ class DefaultSegmentorV2(nn.Module):
         dev = dicts[0]["feat"].device
         eng = self.engine()
         if dev.type != "cuda" or lanes <= 1:
-            return [self.inference(d, eval=False, noise_level=noise_level,
-                                   draws=None if draws is None else draws[i]) for i, d in enumerate(dicts)]
+            return [self.inference(d, eval=False, noise_level=noise_level, draws=None if draws is None else draws[i],
+                                   plan=None if plans is None else plans[i]) for i, d in enumerate(dicts)]
         eng.prepare(dev)
         all_draws = [draws[i] if draws is not None else eng.predraw(d, noise_level) for i, d in enumerate(dicts)]
         cur = torch.cuda.current_stream(dev)
@@ -555,7 +571,8 @@ class DefaultSegmentorV2(nn.Module):
                 with torch.no_grad(), torch.cuda.stream(streams[j]):
                     streams[j].wait_event(ready)  # inputs produced on the caller's stream
                     for i in range(j, len(dicts), nl):
-                        o = eng.inference(dicts[i], noise_level=noise_level, draws=all_draws[i])
+                        o = eng.inference(dicts[i], noise_level=noise_level, draws=all_draws[i],
+                                          plan=None if plans is None else plans[i])
                         o.record_stream(cur)
                         outs[i] = dict(seg_logits=o)
             except BaseException as e:  # noqa: BLE001 - re-raised in the caller
@@ -575,7 +592,8 @@ class DefaultSegmentorV2(nn.Module):
                     st.wait_event(ready)
                 for i, d in enumerate(dicts):
                     with torch.cuda.stream(streams[i % nl]):
-                        o = eng.inference(d, noise_level=noise_level, draws=all_draws[i])
+                        o = eng.inference(d, noise_level=noise_level, draws=all_draws[i],
+                                          plan=None if plans is None else plans[i])
                     o.record_stream(cur)
                     outs[i] = dict(seg_logits=o)
         finally:
@@ -587,14 +605,15 @@ class DefaultSegmentorV2(nn.Module):
         return outs
 
     @torch.no_grad()
-    def inference_ddim(self, input_dict, T=1000, step=1, report=10, eval=True, mode="avg", noise_level=None, draws=None):
+    def inference_ddim(self, input_dict, T=1000, step=1, report=10, eval=True, mode="avg", noise_level=None, draws=None,
+                       plan=None):
         """Multi-step inference (ref: default.py:278-369): MSAI mode="avg", MSFI mode="final".  The step-invariant
         plan (serialization, kernel maps, slot plans) is built once and reused by all step+1 backbone calls."""
         if T != self.T:
             raise ValueError("T differs from the model's diffusion length")
         if mode not in ("avg", "final"):
             raise ValueError(mode)
-        logits = self.engine().inference_ddim(input_dict, step=step, mode=mode, noise_level=noise_level, draws=draws)
+        logits = self.engine().inference_ddim(input_dict, step=step, mode=mode, noise_level=noise_level, draws=draws, plan=plan)
         if eval:  # ref: default.py:361-367
             from .losses import build_criteria
             point = dict(n_pred=logits, n_target=input_dict["segment"], loss_mode="eval")

@@ -428,6 +428,35 @@ def pad_plan(order, offs, offs_pad, patch, n_pad):
     return gidx, widx
 
 
+SLOTS_SELECT_MAX = 64  # include/cdseg.h CDSEG_SLOTS_SELECT_MAX
+
+
+def slots_select(sources, offs_pad, choice, n_pad):
+    """Slot plan of a collated batch whose elements read different curves: out[s] = sources[choice[b]][s] for every padded
+    slot s of batch element b.  sources: up to four (gidx, widx) pairs of n_pad int32 each (the slot plans of one level and
+    patch key), None where no element chooses it; offs_pad (nb + 1) int32 on the device; choice: nb host ints.  The choices
+    ride in the launch arguments: no host-to-device copy.  -> (gidx, widx)."""
+    choice = [int(c) for c in choice]
+    _need_gpu(offs_pad)
+    if offs_pad.dtype != torch.int32 or not offs_pad.is_contiguous():
+        raise _lib.CdsegError("slots_select: offs_pad is a contiguous int32 tensor")
+    if len(choice) != offs_pad.numel() - 1 or any(c < 0 or c > 255 for c in choice):
+        raise _lib.CdsegError("slots_select: one choice in 0..255 per batch element")
+    k = len(sources)
+    dev = offs_pad.device
+    gsrc = (ctypes.c_void_p * max(1, k))(*[None if s is None else s[0].data_ptr() for s in sources])
+    wsrc = (ctypes.c_void_p * max(1, k))(*[None if s is None else s[1].data_ptr() for s in sources])
+    for s in sources:
+        if s is not None and (s[0].numel() != n_pad or s[1].numel() != n_pad or s[0].dtype != torch.int32 or
+                              s[1].dtype != torch.int32 or not s[0].is_contiguous() or not s[1].is_contiguous()):
+            raise _lib.CdsegError("slots_select: every source is a pair of contiguous int32 tensors of n_pad elements")
+    gidx = torch.empty(n_pad, dtype=torch.int32, device=dev)
+    widx = torch.empty(n_pad, dtype=torch.int32, device=dev)
+    check(_lib.load().cdseg_slots_select(gsrc, wsrc, k, _ptr(offs_pad), len(choice), bytes(choice), int(n_pad), _ptr(gidx),
+                                         _ptr(widx), _stream()), "slots_select")
+    return gidx, widx
+
+
 # ------------------------------------------------------------------ native plan builder (csrc/plan.hip)
 class NativePlanCall:
     """One forward's plan through cdseg_plan_begin / cdseg_plan_finish: owns the two arenas of each call and hands out views.
@@ -934,8 +963,12 @@ def gemv(w, b, x, act=ACT_NONE):
     return y
 
 
-def randn(shape, seed, offset, device):
-    out = torch.empty(shape, dtype=torch.float32, device=device)
+def randn(shape, seed, offset, device, out=None):
+    """out: a contiguous float32 tensor of `shape` to fill (a row slice of a larger one) instead of a fresh allocation."""
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=device)
+    elif tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise _lib.CdsegError("randn: `out` is a contiguous float32 tensor of the requested shape")
     check(_lib.load().cdseg_randn(_ptr(out), out.numel(), int(seed) & (2 ** 64 - 1), int(offset), _stream()), "randn")
     return out
 

@@ -306,7 +306,9 @@ class TestScene:
 
     augs        one dict per aug_transform list with the DENSE fragments of that augmented scan: index (F,m) int32 (rows
                 of the transformed scan), coord (F,m,3) float32, grid_coord (F,m,3) int32, feat (F,m,C) float32,
-                num_voxels m, num_fragments F, offset (1,) int64 on the device
+                num_voxels m, num_fragments F, offset (1,) int64 on the device, shared_geometry True: GridSample(mode=
+                "test") picks member i % count of every voxel in voxel-key order (transform.py:867-895), so all F fragments
+                hold one point per voxel over the same voxels in the same row order - grid_coord is F copies of one grid
     fragments   the flat list of per-fragment dicts in the reference's order (aug-major, fragment-minor): zero-copy views
                 of the arrays above (coord, grid_coord, feat, index) with offset / offset_host, ready for model.inference
     n           rows of the transformed scan = rows the votes cover;  n_raw: rows of the raw scan
@@ -324,7 +326,8 @@ class TestScene:
         self.trace = {}
 
     def collated(self, a, f0, k):
-        """Fragments f0 .. f0+k-1 of augmentation a as ONE batch of k scenes: views, nothing is copied."""
+        """Fragments f0 .. f0+k-1 of augmentation a as ONE batch of k scenes: views, nothing is copied.  The dict carries the
+        augmentation's ``shared_geometry`` mark: every element of the batch has the same grid."""
         g = self.augs[a]
         m, k = g["num_voxels"], min(k, g["num_fragments"] - f0)
         if k == 1:
@@ -333,7 +336,8 @@ class TestScene:
         ends = [m * (j + 1) for j in range(k)]
         return dict(coord=g["coord"][sl].reshape(k * m, 3), grid_coord=g["grid_coord"][sl].reshape(k * m, 3),
                     feat=g["feat"][sl].reshape(k * m, -1), index=g["index"][sl],
-                    offset=torch.arange(m, k * m + 1, m, dtype=torch.int64, device=g["coord"].device), offset_host=ends)
+                    offset=torch.arange(m, k * m + 1, m, dtype=torch.int64, device=g["coord"].device), offset_host=ends,
+                    shared_geometry=bool(g.get("shared_geometry")))
 
 
 class TestPipeline:
@@ -465,22 +469,54 @@ class TestPipeline:
                                                         center_shift=self.plan["shift"])
                 off = torch.full((1,), m, dtype=torch.int64, device=dev)  # a device fill, no host-to-device copy
                 scene.augs.append(dict(index=index, coord=fc, grid_coord=fg, feat=ff, num_voxels=m, num_fragments=nfrag,
-                                       offset=off, first=len(scene.fragments), aug_coord=c))
-                scene.fragments += [dict(coord=fc[f], grid_coord=fg[f], feat=ff[f], index=index[f], offset=off, offset_host=[m])
-                                    for f in range(nfrag)]
+                                       offset=off, first=len(scene.fragments), aug_coord=c, shared_geometry=True))
+                scene.fragments += [dict(coord=fc[f], grid_coord=fg[f], feat=ff[f], index=index[f], offset=off, offset_host=[m],
+                                         shared_geometry=True) for f in range(nfrag)]
         finally:
             ops.unbind_stream()
         return scene
 
     # ------------------------------------------------------------------------------------------------ model + vote
     @torch.no_grad()
-    def vote(self, model, scene, num_classes, noise_level=None, lanes=4, fragment_batch=1):
+    def vote(self, model, scene, num_classes, noise_level=None, lanes=4, fragment_batch=1, share_plan=False,
+             fragment_draws="batch"):
         """model.inference on every fragment (``fragment_batch`` consecutive fragments of one augmentation per forward),
-        pred[index] += softmax(logits) in the reference's order, arg-max, and ``[inverse]`` when the scene has one."""
+        pred[index] += softmax(logits) in the reference's order, arg-max, and ``[inverse]`` when the scene has one.
+
+        share_plan      True: the fragments of an augmentation share their geometry (``prepare`` marks them; no grid is
+                        compared here), so the model's plan is built once per (augmentation, group size) - at most two per
+                        augmentation, one at fragment_batch=1 - before the forwards are issued, and handed to
+                        ``inference_many(plans=...)``: no forward builds a plan or reads from the device.  Same votes, bit
+                        for bit.
+        fragment_draws  "batch" (default): a collated forward takes ONE set of random draws, the reference's own batching |
+                        "fragment" (needs share_plan=True): every fragment of a collated forward takes its own draws - noise
+                        rows and order shuffles - in fragment order, as fragment_batch=1 does: k fragments then compute what
+                        k forwards of the reference's protocol compute, at the launch count of one forward."""
+        if fragment_draws not in ("batch", "fragment"):
+            raise ValueError(f"fragment_draws={fragment_draws!r}: 'batch' or 'fragment'")
+        if fragment_draws == "fragment" and not share_plan:
+            raise ValueError("fragment_draws='fragment' needs share_plan=True")
+        if share_plan and not (hasattr(model, "plan") and hasattr(model, "inference_many")):
+            raise ValueError("share_plan=True needs a model with plan() and inference_many()")
         k = max(1, int(fragment_batch))
         groups = [(a, f0) for a, g in enumerate(scene.augs) for f0 in range(0, g["num_fragments"], k)]
         dicts = [scene.collated(a, f0, k) for a, f0 in groups]
-        if hasattr(model, "inference_many"):
+        if share_plan:
+            built = {}
+            for (a, f0), d in zip(groups, dicts):
+                if not scene.augs[a].get("shared_geometry"):
+                    raise ValueError(f"share_plan=True: augmentation {a} is not marked as sharing geometry")
+                key = (a, len(d["offset_host"]))
+                if key not in built:
+                    built[key] = model.plan(d)
+            plans = [built[(a, len(d["offset_host"]))] for (a, _), d in zip(groups, dicts)]
+            draws = None
+            if fragment_draws == "fragment":  # in fragment order, from this one thread, before anything is issued
+                eng = model.engine()
+                draws = [eng.predraw_fragments(d, noise_level) for d in dicts]
+            outs = model.inference_many(dicts, lanes=lanes, noise_level=noise_level, draws=draws, plans=plans)
+            del plans, built  # (inference_many has joined its lanes: nothing reads the plans any more)
+        elif hasattr(model, "inference_many"):
             outs = model.inference_many(dicts, lanes=lanes, noise_level=noise_level)
         else:
             outs = [model.inference(d, eval=False, noise_level=noise_level) for d in dicts]
@@ -500,14 +536,17 @@ class TestPipeline:
 
     @torch.no_grad()
     def segment(self, model, raw, num_classes, scene_index=0, noise_level=None, lanes=4, fragment_batch=1, max_fragments=None,
-                draws=None):
+                draws=None, share_plan=False, fragment_draws="batch"):
         """Raw scan -> (labels int32, pred float32 (scene.n, num_classes) summed softmax votes).  The labels are for the
         ORIGINAL points when the transform list produced ``inverse`` (pred[inverse], engines/test.py:269-272), else for
         the transformed scan's points.  fragment_batch=1 is the reference's protocol, one fragment per forward;
-        fragment_batch=k collates k consecutive fragments of one augmentation (views, no copy) - the caveat of
-        ``inference_many(batch=...)`` applies: the random draws and the serialization depth are per batch."""
+        fragment_batch=k collates k consecutive fragments of one augmentation (views, no copy).  The fragments of an
+        augmentation share their geometry, so the serialization depth of the batch is the single forward's; what is per
+        batch by default is the random draws (the reference's own batching, ``inference_many(batch=...)``).  With
+        share_plan=True and fragment_draws="fragment" every fragment takes its own draws and the batch computes what k
+        single forwards compute (see ``vote``)."""
         scene = self.prepare(raw, scene_index, draws, max_fragments)
-        return self.vote(model, scene, num_classes, noise_level, lanes, fragment_batch)
+        return self.vote(model, scene, num_classes, noise_level, lanes, fragment_batch, share_plan, fragment_draws)
 
     @torch.no_grad()
     def evaluate(self, labels_or_votes, scene, num_classes, ignore_index=-1, reduce=True):

@@ -161,6 +161,15 @@ int cdseg_pad_plan(const int32_t* order, const int32_t* offs, const int32_t* off
 int cdseg_pad_plan_batch(int count, const int32_t* const* orders, const int32_t* const* offs,
                          const int32_t* const* offs_pad, const int* patch, const long* n_pad, int nb, int32_t* gidx,
                          int32_t* widx, void* stream);
+/* Slot plan of a collated batch whose elements read DIFFERENT curves (test-time voting with one order shuffle per
+ * fragment): gidx[s] = gidx_src[choice[b]][s], widx[s] = widx_src[choice[b]][s] for every padded slot s of batch element b
+ * (offs_pad[b] <= s < offs_pad[b + 1]).  gidx_src / widx_src: host arrays of nsrc (<= 4) device pointers, the slot plans of
+ * ONE level and patch key on the curves in question, n_pad int32 each; an entry no element chooses may be NULL, a chosen
+ * NULL entry (or choice >= nsrc) is CDSEG_ERR_ARG before any launch.  choice_host: nb bytes on the HOST, passed to the
+ * kernel by value (no host-to-device copy); nb > CDSEG_SLOTS_SELECT_MAX is CDSEG_ERR_UNSUPPORTED.  No LDS, no atomics. */
+#define CDSEG_SLOTS_SELECT_MAX 64
+int cdseg_slots_select(const int32_t* const* gidx_src, const int32_t* const* widx_src, int nsrc, const int32_t* offs_pad,
+                       int nb, const unsigned char* choice_host, long n_pad, int32_t* gidx, int32_t* widx, void* stream);
 
 /* ------------------------------------------------------------------ dense / gathered GEMM
  * out = epilogue(A @ W^T): nn.Linear (ref: ptv3.py:170-171, 310-313, 463, 597-599, 1562) and,
