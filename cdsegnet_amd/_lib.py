@@ -307,6 +307,8 @@ SIGNATURES = {
     "cdseg_ddim_update": (c_int, [c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int, c_void_p, c_long,
                                   c_void_p]),
     "cdseg_axpy": (c_int, [c_void_p, c_void_p, c_float, c_void_p, c_long, c_void_p]),
+    "cdseg_msi_step": (c_int, [c_void_p, c_void_p, c_long, c_float, c_float, c_float, c_float, c_int, c_void_p, c_void_p, c_long,
+                               c_int, c_float, c_void_p]),
     "cdseg_count_saturated": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p]),
     "cdseg_subm_conv3_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p, c_int, c_float, c_int,
                                      c_void_p]),

@@ -212,21 +212,98 @@ __global__ void gather_pad_cast_kernel(const float* __restrict__ src, int ld_src
   else ((bf16_t*)dst)[t] = f32_to_bf16(v);
 }
 
-// DDIM step on a uniform timestep (ref: default.py:192-214), same operation order as the reference
+// DDIM step on a uniform timestep (ref: default.py:192-214), same operation order as the reference.  One element's
+// arithmetic, shared by ddim_update_kernel and msi_step_kernel and PINNED: which products the compiler fuses into an fma
+// depends on the code around the expression (the scalar kernel fuses the numerator and leaves the two last products alone,
+// a float4 body did not), so the fusion is spelled out and contraction is off - the two kernels agree bit for bit by
+// construction, and with what ddim_update_kernel has always computed.
+__device__ __forceinline__ float ddim_one(float x, float e, float s_ab1, float s_1ab, float s_ab, float s_1ab1,
+                                          int final_step) {
+#pragma clang fp contract(off)
+  const float x0 = __builtin_fmaf(-s_1ab, e, x) / s_ab;
+  const float p = s_ab1 * x0, q = s_1ab1 * e;
+  return final_step ? x0 : p + q;
+}
+
 __global__ void ddim_update_kernel(const float* __restrict__ xt, const float* __restrict__ eps, float s_ab1,
                                    float s_1ab, float s_ab, float s_1ab1, int final_step, float* __restrict__ out,
                                    long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float e = eps[i];
-  const float x0 = (xt[i] - s_1ab * e) / s_ab;
-  out[i] = final_step ? x0 : (s_ab1 * x0 + s_1ab1 * e);
+  out[i] = ddim_one(xt[i], eps[i], s_ab1, s_1ab, s_ab, s_1ab1, final_step);
 }
 
 __global__ void axpy_kernel(const float* __restrict__ a, const float* __restrict__ b, float alpha,
                             float* __restrict__ out, long n) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = a[i] + alpha * b[i];
+}
+
+// ---- the glue of one multi-step inference step in ONE launch (cdseg_msi_step): the DDIM update of c_xt in place (ddim_one)
+// and the running sum / mean of the logits, bit-equal to axpy_kernel: a + 1 * l is one rounded sum fused or not, and
+// 0 + scale * s is the rounded product fused or not (a zero product gives +0 both ways).
+// mode 0: acc = logits | 1: acc = acc + 1 * logits (axpy, alpha 1) | 2: acc = 0 + scale * (acc + 1 * logits) (two axpys)
+__device__ __forceinline__ float msi_acc_one(float a, float l, int mode, float scale) {
+  if (mode == 0) return l;
+  const float s = a + 1.0f * l;
+  return mode == 1 ? s : 0.0f + scale * s;
+}
+
+// One half of the launch: n floats as `head` scalars up to the first 16-byte boundary, `nvec` float4 groups and a scalar
+// tail (vec = 1: both arrays sit at the same offset from a 16-byte boundary), or as scalar groups of four (vec = 0).
+// units = nvec + 1 (the last unit takes head and tail) or ceil(n / 4).
+struct MsiHalf {
+  long n, head, nvec, units;
+  int vec;
+};
+
+__global__ __launch_bounds__(256) void msi_step_kernel(float* __restrict__ c_xt, const float* __restrict__ eps, MsiHalf hc,
+                                                       float s_ab1, float s_1ab, float s_ab, float s_1ab1, int final_step,
+                                                       float* __restrict__ acc, const float* __restrict__ logits, MsiHalf hl,
+                                                       int acc_mode, float scale) {
+  long u = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (u < hc.units) {
+    if (hc.vec && u < hc.nvec) {
+      const long i = hc.head + 4 * u;  // (c_xt + head is 16-byte aligned, i + 3 < n)
+      float4 x = *reinterpret_cast<const float4*>(c_xt + i);
+      const float4 e = *reinterpret_cast<const float4*>(eps + i);
+      x.x = ddim_one(x.x, e.x, s_ab1, s_1ab, s_ab, s_1ab1, final_step);
+      x.y = ddim_one(x.y, e.y, s_ab1, s_1ab, s_ab, s_1ab1, final_step);
+      x.z = ddim_one(x.z, e.z, s_ab1, s_1ab, s_ab, s_1ab1, final_step);
+      x.w = ddim_one(x.w, e.w, s_ab1, s_1ab, s_ab, s_1ab1, final_step);
+      *reinterpret_cast<float4*>(c_xt + i) = x;
+      return;
+    }
+    long lo = 4 * u, hi = lo + 4 < hc.n ? lo + 4 : hc.n;  // a scalar group of four
+    if (hc.vec) lo = 0, hi = hc.n;                        // head and tail: the rows between them are skipped below
+    for (long i = lo; i < hi; ++i) {
+      if (hc.vec && i == hc.head) i += 4 * hc.nvec;
+      if (i >= hi) break;
+      c_xt[i] = ddim_one(c_xt[i], eps[i], s_ab1, s_1ab, s_ab, s_1ab1, final_step);
+    }
+    return;
+  }
+  u -= hc.units;
+  if (u >= hl.units) return;
+  if (hl.vec && u < hl.nvec) {
+    const long i = hl.head + 4 * u;
+    const float4 l = *reinterpret_cast<const float4*>(logits + i);
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (acc_mode != 0) a = *reinterpret_cast<const float4*>(acc + i);
+    a.x = msi_acc_one(a.x, l.x, acc_mode, scale);
+    a.y = msi_acc_one(a.y, l.y, acc_mode, scale);
+    a.z = msi_acc_one(a.z, l.z, acc_mode, scale);
+    a.w = msi_acc_one(a.w, l.w, acc_mode, scale);
+    *reinterpret_cast<float4*>(acc + i) = a;
+    return;
+  }
+  long lo = 4 * u, hi = lo + 4 < hl.n ? lo + 4 : hl.n;
+  if (hl.vec) lo = 0, hi = hl.n;
+  for (long i = lo; i < hi; ++i) {
+    if (hl.vec && i == hl.head) i += 4 * hl.nvec;
+    if (i >= hi) break;
+    acc[i] = msi_acc_one(acc_mode != 0 ? acc[i] : 0.f, logits[i], acc_mode, scale);
+  }
 }
 
 }  // namespace
@@ -403,6 +480,46 @@ int cdseg_axpy(const float* a, const float* b, float alpha, float* out, long n, 
   if (n <= 0) return CDSEG_OK;
   hipLaunchKernelGGL(axpy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, b, alpha,
                      out, n);
+  CDSEG_CHECK_LAUNCH();
+  return CDSEG_OK;
+}
+
+static MsiHalf msi_half(const void* a, const void* b, long n) {
+  MsiHalf h = {n, 0, 0, 0, 0};
+  const uintptr_t ma = (uintptr_t)a & 15, mb = (uintptr_t)b & 15;
+  if (ma == mb) {  // one row slice of a 6-channel batch starts 8 bytes off a boundary: both arrays do, or neither
+    h.vec = 1;
+    h.head = (long)(((16 - ma) & 15) >> 2);
+    if (h.head > n) h.head = n;
+    h.nvec = (n - h.head) >> 2;
+    h.units = h.nvec + 1;
+  } else {
+    h.units = (n + 3) >> 2;
+  }
+  return h;
+}
+
+// The glue of one step of multi-step inference, one launch over both arrays:
+//   eps != NULL:  c_xt[0..n_c) <- the DDIM update of cdseg_ddim_update, IN PLACE
+//   acc != NULL:  acc[0..n_l) <- logits (acc_mode 0) | acc + logits (1) | (acc + logits) * scale (2)
+// bit-equal to cdseg_ddim_update / cdseg_axpy(alpha 1) / cdseg_axpy(0, sum, scale).  Everything is checked before the launch.
+int cdseg_msi_step(float* c_xt, const float* eps, long n_c, float sqrt_ab_prev, float sqrt_1m_ab, float sqrt_ab,
+                   float sqrt_1m_ab_prev, int final_step, float* acc, const float* logits, long n_l, int acc_mode,
+                   float scale, void* stream) {
+  if (n_c < 0 || n_l < 0 || acc_mode < 0 || acc_mode > 2) return CDSEG_ERR_ARG;
+  if (eps && n_c > 0 && !c_xt) return CDSEG_ERR_ARG;
+  if (acc && n_l > 0 && !logits) return CDSEG_ERR_ARG;
+  if ((((uintptr_t)c_xt | (uintptr_t)eps | (uintptr_t)acc | (uintptr_t)logits) & 3)) return CDSEG_ERR_ARG;
+  if (!eps) n_c = 0;
+  if (!acc) n_l = 0;
+  if (n_c == 0 && n_l == 0) return CDSEG_OK;
+  MsiHalf hc = {0, 0, 0, 0, 0}, hl = {0, 0, 0, 0, 0};
+  if (n_c > 0) hc = msi_half(c_xt, eps, n_c);
+  if (n_l > 0) hl = msi_half(acc, logits, n_l);
+  const long blocks = (hc.units + hl.units + 255) / 256;
+  if (blocks > 0x7FFFFFFFL) return CDSEG_ERR_ARG;
+  hipLaunchKernelGGL(msi_step_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, c_xt, eps, hc, sqrt_ab_prev,
+                     sqrt_1m_ab, sqrt_ab, sqrt_1m_ab_prev, final_step, acc, logits, hl, acc_mode, scale);
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
 }

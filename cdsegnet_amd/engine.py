@@ -1564,23 +1564,27 @@ class Engine:
             d["perms"] = [torch.randperm(no).tolist() for _ in range(n_perms)]
         return d
 
-    def predraw(self, input_dict, noise_level=None):
-        """The random draws of one single-step inference, taken NOW from torch's CPU generator (and the device-RNG
-        stream ids reserved now): lets inference_many issue scenes from several threads while the draws stay in
-        scene order."""
+    def predraw(self, input_dict, noise_level=None, n_backbone_calls=1, always_noise=False):
+        """The random draws of one inference, taken NOW from torch's CPU generator (and the device-RNG stream ids
+        reserved now): lets inference_many / inference_ddim_many issue scenes on several lanes while the draws stay in
+        scene order.  Defaults: single-step inference; a multi-step inference of `step` steps takes
+        n_backbone_calls = step + 1 and always_noise = True, as `_setup` does for it."""
         m, bb = self.model, self.model.backbone
         feat = input_dict["feat"]
         per_call = (2 + len(bb.c_stride) + len(bb.n_stride)) if bb.condition else (1 + len(bb.n_stride))
-        d = self.draw(feat.shape[0], tuple(feat.shape), m.c_in_channels, noise_level, per_call)
-        d["rng_base"] = self.reserve_rng()
+        n_calls = int(n_backbone_calls)
+        d = self.draw(feat.shape[0], tuple(feat.shape), m.c_in_channels, noise_level, per_call * n_calls, always_noise)
+        d["rng_base"] = self.reserve_rng() if n_calls == 1 else self.reserve_rng(max(self.RNG_RESERVE, 2 + n_calls))
         return d
 
-    def predraw_fragments(self, input_dict, noise_level=None):
+    def predraw_fragments(self, input_dict, noise_level=None, n_backbone_calls=1, always_noise=False):
         """The draws of ONE collated forward over k fragments that share geometry, as k single forwards take them: the
         concatenation of k `predraw` calls in fragment order (torch's CPU generator ends where k single forwards leave it).
         feat_noise / noise are row-concatenated, every draw position holds k permutations (one per batch element: the
         composed slot plans of Level.slots give every fragment its own shuffle), and with noise_source = "device" every
-        fragment's rows come from its own reserved stream ids (`rng_bases`)."""
+        fragment's rows come from its own reserved stream ids (`rng_bases`).  n_backbone_calls / always_noise as in
+        `predraw`: the draws of ONE collated multi-step inference are k multi-step predraws in fragment order (with device
+        noise every fragment's stream-id cursor advances once per draw of the loop)."""
         if not input_dict.get("shared_geometry"):
             raise ValueError("per-fragment draws are defined for a batch whose elements share geometry (the fragments of one "
                              "test-time augmentation: TestScene.collated marks them)")
@@ -1589,7 +1593,7 @@ class Engine:
         k, m = len(ends), ends[0]
         if ends != [m * (j + 1) for j in range(k)] or feat.shape[0] != k * m:
             raise ValueError(f"elements that share geometry have the same number of points, got offsets {ends}")
-        ds = [self.predraw({"feat": feat[j * m:(j + 1) * m]}, noise_level) for j in range(k)]
+        ds = [self.predraw({"feat": feat[j * m:(j + 1) * m]}, noise_level, n_backbone_calls, always_noise) for j in range(k)]
         d = {"per_fragment": True, "rng_base": ds[0]["rng_base"], "rng_bases": [x["rng_base"] for x in ds]}
         for key in ("feat_noise", "noise"):
             if key in ds[0]:
@@ -1604,6 +1608,7 @@ class Engine:
             self.attn_bytes += nbytes
 
     RNG_RESERVE = 8  # device-RNG streams one single-step inference may consume
+    msi_stats = None  # dict(backbone_calls=, n_encoders=, c_decoders=) of the last inference / inference_ddim call
 
     def reserve_rng(self, k=None):
         """Reserve a block of device-RNG stream ids (call in scene order from ONE thread: keeps the device noise
@@ -1652,12 +1657,13 @@ class Engine:
             if hasattr(ops, "unbind_stream"):
                 ops.unbind_stream()
 
-    def inference_ddim(self, input_dict, step=1, mode="avg", noise_level=None, draws=None, plan=None):
-        """Multi-step inference MSAI (mode="avg") / MSFI ("final") (ref: default.py:278-369)."""
+    def inference_ddim(self, input_dict, step=1, mode="avg", noise_level=None, draws=None, plan=None, reuse_encoder=False):
+        """Multi-step inference MSAI (mode="avg") / MSFI ("final") (ref: default.py:278-369).  The last backbone call runs
+        no c-decoder (its noise estimate is read by nobody).  reuse_encoder: see DefaultSegmentorV2.inference_ddim."""
         prev = ops.set_f32x3(self.x3) if hasattr(ops, "set_f32x3") else None
         try:
             with _lib.use(self.variant):
-                return self._inference_ddim(input_dict, step, mode, noise_level, draws, plan)
+                return self._inference_ddim(input_dict, step, mode, noise_level, draws, plan, reuse_encoder)
         finally:
             if prev is not None:
                 ops.set_f32x3(prev)
@@ -1769,11 +1775,25 @@ class Engine:
                 c_feat = feat if c_ch == feat.shape[1] else input_dict["coord"].float().contiguous()
                 c_perm = plan.perm0
         self._sat_begin(dev)
+        self._msi_begin()
         logits, _ = self.backbone(plan, feat, c_feat, c_perm, t, perms, want_c=False)
+        self._msi_end()
         self._sat_end()
         return logits
 
-    def _inference_ddim(self, input_dict, step, mode, noise_level, draws, plan=None):
+    def _msi_begin(self):
+        self._tls.msi = dict(backbone_calls=0, n_encoders=0, c_decoders=0)
+
+    def _msi_count(self, key):
+        st = getattr(self._tls, "msi", None)
+        if st is not None:
+            st[key] += 1
+
+    def _msi_end(self):
+        """Publish what the call that ends here ran: engine.msi_stats = dict(backbone_calls=, n_encoders=, c_decoders=)."""
+        self.msi_stats, self._tls.msi = self._tls.msi, None
+
+    def _inference_ddim(self, input_dict, step, mode, noise_level, draws, plan=None, reuse_encoder=False):
         m, bb = self.model, self.model.backbone
         if not bb.condition:
             return self._inference(input_dict, noise_level, draws, plan)
@@ -1789,31 +1809,58 @@ class Engine:
             ops.gather_rows(nz.to(dev, torch.float32).contiguous(), plan.perm0)
         ab = m.Alpha_bar
         n_pred = None
+        # reuse_encoder: n_emb and the n-encoder stages depend on feat and on the n-branch shuffles alone - run in the first
+        # call, kept for the later ones (backbone(hoist=)); the later calls' n-branch shuffles are drawn and ignored
+        hoist = {} if reuse_encoder else None
+        one_launch = hasattr(ops, "msi_step")  # (an op layer without the fused glue runs the three element-wise ops)
+        self._msi_begin()
         for k, t in enumerate(schedule):
             t = int(t)
-            logits, eps = self.backbone(plan, feat, c_xt, None, t, perms[per_call * k:per_call * (k + 1)], want_c=True)
+            # the reference leaves its loop on t <= 0 right after this call (default.py:327-349) - the schedule always ends
+            # at -1 -: the last call's noise estimate and DDIM update are read by nobody, so its c-decoder is not run
+            last = t <= 0
+            logits, eps = self.backbone(plan, feat, c_xt, None, t, perms[per_call * k:per_call * (k + 1)], want_c=not last,
+                                        hoist=hoist)
             # DDIM update on the uniform timestep (ref: default.py:192-214); scalars in fp32 like the reference
-            s_ab, s_1ab = float(torch.sqrt(ab[t])), float(torch.sqrt(1 - ab[t]))
-            if t == 0:
-                c_xt = ops.ddim_update(c_xt, eps, 0.0, s_1ab, s_ab, 0.0, final=True)
+            # (a call at t = 0 is the last one: the "final" form x0 of the update is never read either)
+            coef = None
+            if not last:
+                coef = (float(torch.sqrt(ab[t - 1])), float(torch.sqrt(1 - ab[t])), float(torch.sqrt(ab[t])),
+                        float(torch.sqrt(1 - ab[t - 1])), False)
+            if one_launch:
+                # c_xt is updated in place: the call that read it (its stem gathers a copy) precedes this on the stream
+                acc = n_pred if (mode == "avg" and n_pred is not None) else None
+                if coef is not None or acc is not None:
+                    ops.msi_step(c_xt if coef else None, eps if coef else None, *(coef or (0.0, 0.0, 1.0, 0.0, False)),
+                                 acc=acc, logits=logits if acc is not None else None,
+                                 acc_mode=ops.MSI_MEAN if last else ops.MSI_ADD,
+                                 scale=float(1.0 / len(schedule)) if last else 1.0)
+                if acc is None:
+                    n_pred = logits
+                    if mode == "avg" and last:  # (a schedule of one call, T = 1: the mean's factor still applies)
+                        n_pred = ops.axpy(torch.zeros_like(n_pred), n_pred, 1.0 / len(schedule))
             else:
-                c_xt = ops.ddim_update(c_xt, eps, float(torch.sqrt(ab[t - 1])), s_1ab, s_ab,
-                                       float(torch.sqrt(1 - ab[t - 1])), final=False)
-            if mode == "avg":
-                n_pred = logits if n_pred is None else ops.axpy(n_pred, logits, 1.0)
-            else:
-                n_pred = logits
-            if t <= 0:
+                if coef is not None:
+                    c_xt = ops.ddim_update(c_xt, eps, *coef[:4], final=coef[4])
+                if mode == "avg":
+                    n_pred = logits if n_pred is None else ops.axpy(n_pred, logits, 1.0)
+                else:
+                    n_pred = logits
+            if last:
                 break
-        if mode == "avg":
+        if mode == "avg" and not one_launch:
             n_pred = ops.axpy(torch.zeros_like(n_pred), n_pred, 1.0 / len(schedule))
+        self._msi_end()
         return n_pred
 
     # -- backbone ------------------------------------------------------------------------------------
-    def backbone(self, plan, feat, c_feat, c_perm, t, perms, want_c):
+    def backbone(self, plan, feat, c_feat, c_perm, t, perms, want_c, hoist=None):
         """PT-v3m1 forward (ref: ptv3.py:1757-1846).  feat (N,C) in the caller's order; c_feat with c_perm
         (None: already in physical order).  Returns logits in the caller's order and, if want_c, the
-        c-head output (noise estimate) in physical order."""
+        c-head output (noise estimate) in physical order.
+        hoist (multi-step inference, reuse_encoder): a dict that carries the n-encoder's bottleneck State from the first
+        call to the later ones - an empty dict is filled, a filled one replaces n_emb and the n-encoder stages (the
+        n-branch shuffles of `perms` are then ignored: the States hold the first call's curves)."""
         bb = self.model.backbone
         w = self.w
         cond = bb.condition
@@ -1874,19 +1921,34 @@ class Engine:
                 return enc_stage(st, "c", 2, c_cum, p_c2)
 
             fork = self.fork_stage if (dev.type == "cuda" and self.fork_stage is not None) else None
+            if hoist:
+                fork = None  # the n-encoder is not run: nothing for the c-branch to run beside
             SHARE_EVENTS.on = fork is not None
             if fork is None:
                 plan.finish_pads()
             cst = c_branch() if fork is None else None
-            nst = self._eng("n_emb").run_embedding(plan, feat, plan.perm0, "n_emb", n_curves)
-            plan.finish_pads()  # (deferred by _setup: the stem is device work for the plan's last stretch of host time)
-            join = None
-            for s in range(bb.n_num_stages):
-                if fork is not None and s == fork:
-                    cst, join = self._on_side_stream(c_branch)
-                nst = enc_stage(nst, "n", s, n_cum, n_perms[s])
-            if join is not None:
-                ops.wait_event(join)
+            if hoist:
+                nst = hoist["nst"]
+            else:
+                nst = self._eng("n_emb").run_embedding(plan, feat, plan.perm0, "n_emb", n_curves)
+                plan.finish_pads()  # (deferred by _setup: the stem is device work for the plan's last stretch of host time)
+                join = None
+                for s in range(bb.n_num_stages):
+                    if fork is not None and s == fork:
+                        cst, join = self._on_side_stream(c_branch)
+                    nst = enc_stage(nst, "n", s, n_cum, n_perms[s])
+                if join is not None:
+                    ops.wait_event(join)
+                self._msi_count("n_encoders")
+            if hoist is not None:
+                # the cross block writes the bottleneck's residual stream in place (_cpe, the proj / tail residual): every
+                # call works on a copy of x.  xc is only read (by q_cpe's conv) and rebound, the encoder States below the
+                # bottleneck are only read by run_unpooling: both are kept by reference
+                hoist["nst"] = nst
+                x = ops.gather_pad_cast(nst.x, None, nst.x.shape[1], torch.float32)
+                work = State(nst.level, x, x if nst.xc is nst.x else nst.xc, nst.curves)
+                work.parent = nst.parent
+                nst = work
             e = self._eng("x")
             e._fit(nst)
             e._fit(cst)
@@ -1896,10 +1958,13 @@ class Engine:
             plan.finish_pads()
             for s in range(bb.n_num_stages):
                 nst = enc_stage(nst, "n", s, n_cum, next(pi) if s > 0 else None)
+            self._msi_count("n_encoders")
         self.trace = {"n_bottleneck": nst.x}
         # decoders.  In single-step inference the c-decoder / c-head never reach seg_logits (dead code).
         c_out = None
+        self._msi_count("backbone_calls")
         if cond and want_c:
+            self._msi_count("c_decoders")
             for s in reversed(range(bb.c_num_stages - 1)):
                 cst = dec_stage(cst, "c", s)
             e = self._eng("c_head")

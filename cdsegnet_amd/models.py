@@ -606,19 +606,98 @@ class DefaultSegmentorV2(nn.Module):
 
     @torch.no_grad()
     def inference_ddim(self, input_dict, T=1000, step=1, report=10, eval=True, mode="avg", noise_level=None, draws=None,
-                       plan=None):
+                       plan=None, reuse_encoder=False):
         """Multi-step inference (ref: default.py:278-369): MSAI mode="avg", MSFI mode="final".  The step-invariant
-        plan (serialization, kernel maps, slot plans) is built once and reused by all step+1 backbone calls."""
+        plan (serialization, kernel maps, slot plans) is built once and reused by all step+1 backbone calls, and the last
+        call runs no c-decoder (nobody reads its noise estimate).
+
+        ``reuse_encoder=True``: the n-branch stem and encoder - whose input, ``feat``, is the same in every step and which
+        no timestep bias reaches - run ONCE, under the n-branch order shuffles of the first backbone call; every step then
+        runs the c-branch, the cross block, the decoders and the heads.  The random draws are consumed exactly as without
+        the flag (8 order shuffles per backbone call; the n-branch positions 1, 3, 4, 6, 7 of the later calls are drawn and
+        ignored), and the result is bit for bit what the un-hoisted loop computes when those positions repeat the first
+        call's draws - one of the outcomes the reference's protocol can draw.  What is given up: MSAI no longer averages
+        over n-branch order shuffles (every step's n-encoder sees the first call's orders), only over the c-branch's
+        shuffles and the diffusion steps.  No effect on a model with ``condition=False``.
+        ``engine().msi_stats`` = dict(backbone_calls=, n_encoders=, c_decoders=) of the last call."""
         if T != self.T:
             raise ValueError("T differs from the model's diffusion length")
         if mode not in ("avg", "final"):
             raise ValueError(mode)
-        logits = self.engine().inference_ddim(input_dict, step=step, mode=mode, noise_level=noise_level, draws=draws, plan=plan)
+        logits = self.engine().inference_ddim(input_dict, step=step, mode=mode, noise_level=noise_level, draws=draws, plan=plan,
+                                              reuse_encoder=reuse_encoder)
         if eval:  # ref: default.py:361-367
             from .losses import build_criteria
             point = dict(n_pred=logits, n_target=input_dict["segment"], loss_mode="eval")
             return dict(loss=build_criteria(self.criteria_cfg, self.loss_type, self.task_num, getattr(self, "train_loss", "torch"))(point), seg_logits=logits)
         return dict(seg_logits=logits)
+
+    @torch.no_grad()
+    def inference_ddim_many(self, input_dicts, step=1, mode="avg", lanes=4, noise_level=None, draws=None, plans=None, batch=1,
+                            reuse_encoder=False):
+        """Throughput form of ``inference_ddim`` for a sequence of independent scenes, the multi-step sibling of
+        ``inference_many``: the whole step loop of scene i is issued on HIP stream ``lane[i % lanes]`` from one host thread, the
+        random draws are taken up front in scene order (``engine().predraw(d, noise_level, step + 1, always_noise=True)``),
+        and the lanes are joined before it returns.  ``batch`` > 1 collates every ``batch`` consecutive scenes into one
+        multi-step forward; ``plans``: one ``model.plan`` result per forward.  Same kernels, same results as calling
+        ``inference_ddim(d, step=step, mode=mode, eval=False, ...)`` scene by scene under the same draws, bit for bit.
+        Returns the list of output dicts (one per input scene), valid on the caller's current stream."""
+        if mode not in ("avg", "final"):
+            raise ValueError(mode)
+        if int(step) < 1:
+            raise ValueError(f"step={step!r}: at least 1")
+        dicts = list(input_dicts)
+        if not dicts:
+            return []
+        if batch > 1:
+            groups = [dicts[i:i + batch] for i in range(0, len(dicts), batch)]
+            outs = self.inference_ddim_many([collate_device(g) for g in groups], step=step, mode=mode, lanes=lanes,
+                                            noise_level=noise_level, draws=draws, plans=plans, reuse_encoder=reuse_encoder)
+            res = []
+            for g, o in zip(groups, outs):
+                pos = 0
+                for d in g:
+                    n = d["feat"].shape[0]
+                    res.append(dict(seg_logits=o["seg_logits"][pos:pos + n]))
+                    pos += n
+            return res
+        dev = dicts[0]["feat"].device
+        eng = self.engine()
+
+        def one(i, d, dr):
+            return eng.inference_ddim(d, step=step, mode=mode, noise_level=noise_level, draws=dr,
+                                      plan=None if plans is None else plans[i], reuse_encoder=reuse_encoder)
+
+        if dev.type != "cuda" or lanes <= 1:
+            return [dict(seg_logits=one(i, d, None if draws is None else draws[i])) for i, d in enumerate(dicts)]
+        eng.prepare(dev)
+        # a model without the c-branch runs single-step inference whatever `step` says (Engine._inference_ddim)
+        n_calls, always = (int(step) + 1, True) if self.backbone.condition else (1, False)
+        all_draws = [draws[i] if draws is not None else eng.predraw(d, noise_level, n_calls, always)
+                     for i, d in enumerate(dicts)]
+        cur = torch.cuda.current_stream(dev)
+        nl = min(int(lanes), len(dicts))
+        streams = self._lanes.setdefault(dev.index, [])  # one pool per device: lanes must not outnumber hardware queues
+        while len(streams) < nl:
+            streams.append(torch.cuda.Stream(device=dev))
+        ready = torch.cuda.Event()
+        ready.record(cur)
+        outs = [None] * len(dicts)
+        fork, eng.fork_stage = eng.fork_stage, None  # concurrency comes from the lanes; no intra-scene fork
+        try:
+            torch.cuda.set_device(dev)
+            for st in streams[:nl]:
+                st.wait_event(ready)  # inputs produced on the caller's stream
+            for i, d in enumerate(dicts):
+                with torch.cuda.stream(streams[i % nl]):
+                    o = one(i, d, all_draws[i])
+                o.record_stream(cur)
+                outs[i] = dict(seg_logits=o)
+        finally:
+            eng.fork_stage = fork
+            for st in streams[:nl]:
+                cur.wait_stream(st)
+        return outs
 
     def forward(self, input_dict, draws=None):
         """Training forward (ref: default.py:424-493): returns dict(loss=...) under torch autograd - `loss.backward()` fills

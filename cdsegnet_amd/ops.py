@@ -1004,6 +1004,28 @@ def axpy(a, b, alpha):
     return out
 
 
+MSI_SET, MSI_ADD, MSI_MEAN = 0, 1, 2  # cdseg_msi_step's acc_mode
+
+
+def msi_step(c_xt=None, eps=None, sqrt_ab_prev=0.0, sqrt_1m_ab=0.0, sqrt_ab=1.0, sqrt_1m_ab_prev=0.0, final=False,
+             acc=None, logits=None, acc_mode=MSI_ADD, scale=1.0):
+    """One launch for the glue of a multi-step inference step: c_xt <- ddim_update(c_xt, eps, ...) IN PLACE (eps None: skipped)
+    and acc <- logits | acc + logits | (acc + logits) * scale (acc None: skipped).  Bit-equal to ddim_update / axpy."""
+    for name, a, b in (("c_xt / eps", c_xt, eps), ("acc / logits", acc, logits)):
+        for t in (a, b):
+            if t is not None:
+                _need_gpu(t)
+                if t.dtype != torch.float32 or not t.is_contiguous():
+                    raise ValueError(f"msi_step: {name} must be contiguous float32 tensors")
+        if a is not None and b is not None and a.numel() != b.numel():
+            raise ValueError(f"msi_step: {name} differ in size ({a.numel()} / {b.numel()})")
+    n_c = c_xt.numel() if c_xt is not None else (eps.numel() if eps is not None else 0)
+    n_l = logits.numel() if logits is not None else (acc.numel() if acc is not None else 0)
+    check(_lib.load().cdseg_msi_step(_ptr(c_xt), _ptr(eps), n_c, float(sqrt_ab_prev), float(sqrt_1m_ab), float(sqrt_ab),
+                                     float(sqrt_1m_ab_prev), 1 if final else 0, _ptr(acc), _ptr(logits), n_l, int(acc_mode),
+                                     float(scale), _stream()), "msi_step")
+
+
 # ------------------------------------------------------------------ test-time pipeline ops
 def voxelize(coord, grid_size):
     """GridSample's voxel coordinates: (grid int32 (n,3) shifted to start at 0, key int64 (n), min int32 (3))."""

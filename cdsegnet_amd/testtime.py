@@ -301,6 +301,16 @@ def parse_test(cfg_data_test):
     return dict(transform=transform, augs=augs, voxelize=vox, shift=shift, feat_keys=feat_keys)
 
 
+def _check_inference_mode(inference_mode, step, reuse_encoder):
+    """The tester's cfg.inference_mode / cfg.step (ref: engines/test.py:212-258), checked before any device work."""
+    if inference_mode not in ("SSI", "MSAI", "MSFI"):
+        raise ValueError(f"inference_mode={inference_mode!r}: 'SSI', 'MSAI' or 'MSFI'")
+    if isinstance(step, bool) or int(step) != step or step < 1:
+        raise ValueError(f"step={step!r}: an integer, at least 1")
+    if reuse_encoder and inference_mode == "SSI":
+        raise ValueError("reuse_encoder=True needs inference_mode 'MSAI' or 'MSFI' (SSI runs the n-encoder once anyway)")
+
+
 class TestScene:
     """What ``TestPipeline.prepare`` returns for one scan.
 
@@ -479,7 +489,7 @@ class TestPipeline:
     # ------------------------------------------------------------------------------------------------ model + vote
     @torch.no_grad()
     def vote(self, model, scene, num_classes, noise_level=None, lanes=4, fragment_batch=1, share_plan=False,
-             fragment_draws="batch"):
+             fragment_draws="batch", inference_mode="SSI", step=1, reuse_encoder=False):
         """model.inference on every fragment (``fragment_batch`` consecutive fragments of one augmentation per forward),
         pred[index] += softmax(logits) in the reference's order, arg-max, and ``[inverse]`` when the scene has one.
 
@@ -491,7 +501,15 @@ class TestPipeline:
         fragment_draws  "batch" (default): a collated forward takes ONE set of random draws, the reference's own batching |
                         "fragment" (needs share_plan=True): every fragment of a collated forward takes its own draws - noise
                         rows and order shuffles - in fragment order, as fragment_batch=1 does: k fragments then compute what
-                        k forwards of the reference's protocol compute, at the launch count of one forward."""
+                        k forwards of the reference's protocol compute, at the launch count of one forward.
+        inference_mode  the tester's cfg.inference_mode (ref: engines/test.py:212-258): "SSI" (default) one backbone call per
+                        forward | "MSAI" / "MSFI": every fragment (or collated group) runs ``step`` DDIM steps through
+                        ``inference_ddim_many(mode="avg" / "final")``; plans, batches and per-fragment draws as for SSI
+                        (a plan serves all step + 1 backbone calls).  ``reuse_encoder``: see ``model.inference_ddim``."""
+        _check_inference_mode(inference_mode, step, reuse_encoder)
+        multi = inference_mode != "SSI"
+        if multi and not hasattr(model, "inference_ddim_many"):
+            raise ValueError(f"inference_mode={inference_mode!r} needs a model with inference_ddim_many()")
         if fragment_draws not in ("batch", "fragment"):
             raise ValueError(f"fragment_draws={fragment_draws!r}: 'batch' or 'fragment'")
         if fragment_draws == "fragment" and not share_plan:
@@ -501,6 +519,16 @@ class TestPipeline:
         k = max(1, int(fragment_batch))
         groups = [(a, f0) for a, g in enumerate(scene.augs) for f0 in range(0, g["num_fragments"], k)]
         dicts = [scene.collated(a, f0, k) for a, f0 in groups]
+
+        def forwards(draws=None, plans=None):
+            if multi:
+                return model.inference_ddim_many(dicts, step=int(step), mode="avg" if inference_mode == "MSAI" else "final",
+                                                 lanes=lanes, noise_level=noise_level, draws=draws, plans=plans,
+                                                 reuse_encoder=reuse_encoder)
+            if draws is None and plans is None:
+                return model.inference_many(dicts, lanes=lanes, noise_level=noise_level)
+            return model.inference_many(dicts, lanes=lanes, noise_level=noise_level, draws=draws, plans=plans)
+
         if share_plan:
             built = {}
             for (a, f0), d in zip(groups, dicts):
@@ -513,11 +541,14 @@ class TestPipeline:
             draws = None
             if fragment_draws == "fragment":  # in fragment order, from this one thread, before anything is issued
                 eng = model.engine()
-                draws = [eng.predraw_fragments(d, noise_level) for d in dicts]
-            outs = model.inference_many(dicts, lanes=lanes, noise_level=noise_level, draws=draws, plans=plans)
-            del plans, built  # (inference_many has joined its lanes: nothing reads the plans any more)
-        elif hasattr(model, "inference_many"):
-            outs = model.inference_many(dicts, lanes=lanes, noise_level=noise_level)
+                if multi:
+                    draws = [eng.predraw_fragments(d, noise_level, int(step) + 1, always_noise=True) for d in dicts]
+                else:
+                    draws = [eng.predraw_fragments(d, noise_level) for d in dicts]
+            outs = forwards(draws, plans)
+            del plans, built  # (the lanes have been joined: nothing reads the plans any more)
+        elif multi or hasattr(model, "inference_many"):
+            outs = forwards()
         else:
             outs = [model.inference(d, eval=False, noise_level=noise_level) for d in dicts]
         dev = scene.augs[0]["coord"].device
@@ -536,7 +567,7 @@ class TestPipeline:
 
     @torch.no_grad()
     def segment(self, model, raw, num_classes, scene_index=0, noise_level=None, lanes=4, fragment_batch=1, max_fragments=None,
-                draws=None, share_plan=False, fragment_draws="batch"):
+                draws=None, share_plan=False, fragment_draws="batch", inference_mode="SSI", step=1, reuse_encoder=False):
         """Raw scan -> (labels int32, pred float32 (scene.n, num_classes) summed softmax votes).  The labels are for the
         ORIGINAL points when the transform list produced ``inverse`` (pred[inverse], engines/test.py:269-272), else for
         the transformed scan's points.  fragment_batch=1 is the reference's protocol, one fragment per forward;
@@ -544,9 +575,11 @@ class TestPipeline:
         augmentation share their geometry, so the serialization depth of the batch is the single forward's; what is per
         batch by default is the random draws (the reference's own batching, ``inference_many(batch=...)``).  With
         share_plan=True and fragment_draws="fragment" every fragment takes its own draws and the batch computes what k
-        single forwards compute (see ``vote``)."""
+        single forwards compute (see ``vote``).  inference_mode / step / reuse_encoder: multi-step voting, see ``vote``."""
+        _check_inference_mode(inference_mode, step, reuse_encoder)  # (before any device work)
         scene = self.prepare(raw, scene_index, draws, max_fragments)
-        return self.vote(model, scene, num_classes, noise_level, lanes, fragment_batch, share_plan, fragment_draws)
+        return self.vote(model, scene, num_classes, noise_level, lanes, fragment_batch, share_plan, fragment_draws,
+                         inference_mode, step, reuse_encoder)
 
     @torch.no_grad()
     def evaluate(self, labels_or_votes, scene, num_classes, ignore_index=-1, reduce=True):

@@ -311,6 +311,15 @@ int cdseg_subm_conv3_f32(const void* x, int ldx, const void* wimg, const float* 
 int cdseg_split16(const float* x, int ldx, long rows, int cols, void* hi, void* lo, int ld16, float lo_scale, void* stream);
 /* out = a + alpha * b (fp32).  ref: default.py:228-236 (add_gaussian_noise) */
 int cdseg_axpy(const float* a, const float* b, float alpha, float* out, long n, void* stream);
+/* The glue of one step of multi-step inference (MSAI / MSFI, ref: default.py:327-349) in one launch over both arrays:
+ *   eps != NULL: c_xt[0..n_c) <- cdseg_ddim_update's result, IN PLACE
+ *   acc != NULL: acc[0..n_l) <- logits (acc_mode 0) | acc + logits (1) | (acc + logits) * scale (2: the last step's mean)
+ * Bit-equal to cdseg_ddim_update / cdseg_axpy.  16-byte accesses where a pair of arrays sits at the same offset from a 16-byte
+ * boundary, scalar head / tail otherwise.  CDSEG_ERR_ARG before any launch: a negative count, a NULL array with a positive
+ * count, an unknown acc_mode, a pointer that is not 4-byte aligned. */
+int cdseg_msi_step(float* c_xt, const float* eps, long n_c, float sqrt_ab_prev, float sqrt_1m_ab, float sqrt_ab,
+                   float sqrt_1m_ab_prev, int final_step, float* acc, const float* logits, long n_l, int acc_mode,
+                   float scale, void* stream);
 
 /* ------------------------------------------------------------------ test-time pipeline
  * ref: datasets/transform.py:821-897 (GridSample mode="test"), engines/test.py:261-278 (softmax vote, arg-max) */
