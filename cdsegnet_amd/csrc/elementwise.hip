@@ -351,6 +351,9 @@ __global__ void count_saturated_kernel(const uint16_t* __restrict__ x, long rows
   }
 }
 
+// base address of a matrix that is read or written in groups of four elements (row strides are checked as multiples of four)
+static bool rows_aligned4(const void* p, int dtype) { return (((uintptr_t)p) & (dtype == CDSEG_F32 ? 15 : 7)) == 0; }
+
 extern "C" {
 
 int cdseg_layernorm(const void* x, int x_dtype, int ldx, const float* gamma, const float* beta, float eps,
@@ -358,6 +361,11 @@ int cdseg_layernorm(const void* x, int x_dtype, int ldx, const float* gamma, con
                     void* out2, int out2_dtype, int ldo2, long m, int c, void* stream) {
   if (m <= 0) return CDSEG_OK;
   if (c <= 0 || (c & 3) || c > 2048 || (ldx & 3) || (ldo & 3) || (res && (ldres & 3)) || (out2 && (ldo2 & 3)))
+    return CDSEG_ERR_ARG;
+  // every access is one group of four elements: 16 bytes of fp32, 8 bytes of the 16-bit type
+  if (!x || !gamma || !beta || !out || !rows_aligned4(x, x_dtype) || !rows_aligned4(out, out_dtype) ||
+      (out2 && !rows_aligned4(out2, out2_dtype)) || !rows_aligned4(gamma, CDSEG_F32) || !rows_aligned4(beta, CDSEG_F32) ||
+      (res && !rows_aligned4(res, CDSEG_F32)) || (colbias && !rows_aligned4(colbias, CDSEG_F32)))
     return CDSEG_ERR_ARG;
   const int nchunk = c >> 2;
   int tpr = 1;
@@ -385,6 +393,9 @@ int cdseg_segment_max(const void* y, int y_dtype, int ldy, const int32_t* seg_st
                       int out2_dtype, int ldo2, void* stream) {
   if (m <= 0) return CDSEG_OK;
   if (c <= 0 || (c & 3) || (ldy & 3) || (ldo & 3) || (out2 && (ldo2 & 3)) || (scale && !shift)) return CDSEG_ERR_ARG;
+  if (!y || !seg_start || !out || !rows_aligned4(y, y_dtype) || !rows_aligned4(out, CDSEG_F32) ||
+      (out2 && !rows_aligned4(out2, out2_dtype)) || (scale && (!rows_aligned4(scale, CDSEG_F32) || !rows_aligned4(shift, CDSEG_F32))))
+    return CDSEG_ERR_ARG;
   const long total = m * (c >> 2);
   long blocks = (total + 255) / 256;
   if (blocks > 8192) blocks = 8192;

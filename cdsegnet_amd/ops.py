@@ -200,6 +200,13 @@ def workspace(nbytes, device):
     return buf
 
 
+def _scratch(nbytes, device):
+    """A fresh byte buffer of exactly nbytes from torch's allocator: the per-call workspaces of the training kernels, the packed
+    weight images and the plan arenas, each sized by its cdseg_*_bytes / *_layout function (one place, so that a test can serve
+    guarded views: tests/test_gpu_workspace_contract.py)."""
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+
+
 # ------------------------------------------------------------------ serialization
 def grid_max(grid):
     _need_gpu(grid)
@@ -470,8 +477,8 @@ class NativePlanCall:
         tot = (ctypes.c_long * 3)()
         check(lib.cdseg_plan_begin_layout(self.sp, self.n, self.nb, off, tot), "plan_begin_layout")
         dev = grid.device
-        self.b32 = torch.empty(tot[0], dtype=torch.int32, device=dev)
-        self.b64 = torch.empty(tot[1], dtype=torch.int64, device=dev)
+        self.b32 = _scratch(4 * tot[0], dev).view(torch.int32)
+        self.b64 = _scratch(8 * tot[1], dev).view(torch.int64)
         self.ws = workspace(tot[2], dev)
         self.boff = list(off)
         io = self.bio = _lib.PlanBeginIO()
@@ -505,8 +512,8 @@ class NativePlanCall:
         info = (ctypes.c_long * n_info)()
         check(lib.cdseg_plan_finish_layout(self.sp, self.n, self.nb, mh, oh, off, info), "plan_finish_layout")
         dev = self.b32.device
-        self.f32 = torch.empty(info[0], dtype=torch.int32, device=dev)
-        self.f64 = torch.empty(max(1, info[1]), dtype=torch.int64, device=dev)
+        self.f32 = _scratch(4 * info[0], dev).view(torch.int32)
+        self.f64 = _scratch(8 * max(1, info[1]), dev).view(torch.int64)
         if info[2] > self.ws.numel():
             self.ws = workspace(info[2], dev)
         pin = pads_pin(info[3])
@@ -719,8 +726,8 @@ def block_rr_pack(channels, wl, wqkv, wp, w1, w2):
     _need_gpu(wl, wqkv, wp, w1, w2)
     lib = _lib.load()
     dev = wp.device
-    head = torch.empty(lib.cdseg_block_rr_img_bytes(channels, 0), dtype=torch.uint8, device=dev) if wl is not None else None
-    tail = torch.empty(lib.cdseg_block_rr_img_bytes(channels, 1), dtype=torch.uint8, device=dev)
+    head = _scratch(lib.cdseg_block_rr_img_bytes(channels, 0), dev) if wl is not None else None
+    tail = _scratch(lib.cdseg_block_rr_img_bytes(channels, 1), dev)
     check(lib.cdseg_block_rr_pack(int(channels), _ptr(wl), _ptr(wqkv), _ptr(head), _ptr(wp), _ptr(w1), _ptr(w2), _ptr(tail),
                                   _stream()), "block_rr_pack")
     return head, tail
@@ -836,7 +843,7 @@ def stem5_pack(w):
     """(32, 125 * 8) bf16 stem weight -> LDS image of the stem kernel (built once per weight)."""
     _need_gpu(w)
     assert is_lp(w.dtype) and tuple(w.shape) == (32, 1000)
-    img = torch.empty(_lib.load().cdseg_stem5_wimg_bytes(), dtype=torch.uint8, device=w.device)
+    img = _scratch(_lib.load().cdseg_stem5_wimg_bytes(), w.device)
     check(_lib.load().cdseg_stem5_pack(_ptr(w), _ptr(img), _stream()), "stem5_pack")
     return img
 
@@ -861,7 +868,7 @@ def subm_conv3_pack(w):
     """(C, 27*C) bf16 weight of a k = 3 submanifold conv -> its MFMA-fragment-order image (built once per weight)."""
     _need_gpu(w)
     c = w.shape[0]
-    img = torch.empty(_lib.load().cdseg_subm_conv3_wimg_bytes(c), dtype=torch.uint8, device=w.device)
+    img = _scratch(_lib.load().cdseg_subm_conv3_wimg_bytes(c), w.device)
     check(_lib.load().cdseg_subm_conv3_pack(_ptr(w), c, _ptr(img), _stream()), "subm_conv3_pack")
     return img
 
@@ -934,7 +941,7 @@ def pool_fused_pack(w):
     _need_gpu(w)
     cout, cin = w.shape
     lib = _lib.load()
-    img = torch.empty(lib.cdseg_pool_fused_img_bytes(cin, cout), dtype=torch.uint8, device=w.device)
+    img = _scratch(lib.cdseg_pool_fused_img_bytes(cin, cout), w.device)
     check(lib.cdseg_pool_fused_pack(_ptr(w), cin, cout, _ptr(img), _stream()), "pool_fused_pack")
     return img
 
@@ -1273,7 +1280,7 @@ def attention_bwd(q, k, v, q_gidx, kv_gidx, widx, patch_start, patch_start_host,
         if t.stride(0) % 4 or t.data_ptr() % 16 or t.stride(1) != 1:
             raise _lib.CdsegError("attention_bwd: gradient rows must be 16-byte aligned")
     lib = _lib.load()
-    ws = torch.empty(max(1, lib.cdseg_attention_bwd_ws_bytes(ps[-1], int(num_heads))), dtype=torch.uint8, device=q.device)
+    ws = _scratch(max(1, lib.cdseg_attention_bwd_ws_bytes(ps[-1], int(num_heads))), q.device)
     check(lib.cdseg_attention_bwd(_ptr(q), _ptr(k), _ptr(v), q.stride(0), k.stride(0), v.stride(0), _ptr(q_gidx),
                                   _ptr(kv_gidx), _ptr(widx), _ptr(patch_start), num_patches, int(num_heads), ps[-1], max(1, max_len),
                                   float(scale), _ptr(dout), dout.stride(0), _ptr(dq), _ptr(dk), _ptr(dv), dq.stride(0),
@@ -1286,7 +1293,7 @@ def layernorm_bwd(x, gamma, dy, dx, accumulate=False, eps=1e-5, dgamma=None, dbe
     _need_gpu(x, dy)
     lib = _lib.load()
     if deterministic:
-        ws = torch.empty(max(16, lib.cdseg_layernorm_bwd_det_ws_bytes(x.shape[0], x.shape[1])), dtype=torch.uint8, device=x.device)
+        ws = _scratch(max(16, lib.cdseg_layernorm_bwd_det_ws_bytes(x.shape[0], x.shape[1])), x.device)
         check(lib.cdseg_layernorm_bwd_det(_ptr(x), x.stride(0), _ptr(gamma), float(eps), _ptr(dy), dy.stride(0), _ptr(dx),
                                           dx.stride(0), int(bool(accumulate)), _ptr(dgamma), _ptr(dbeta), x.shape[0],
                                           x.shape[1], _ptr(ws), ws.numel(), _stream()), "layernorm_bwd (deterministic)")
@@ -1345,7 +1352,7 @@ def wgrad_partition(m, n, k, kvol=1, dtype=torch.float32):
 
 def _wgrad_ws(lib, m, n, k, kvol, lp, device):
     nbytes = lib.cdseg_wgrad_det_ws_bytes(int(m), int(n), int(k), int(kvol), BF16 if lp else F32)
-    return torch.empty(max(16, nbytes), dtype=torch.uint8, device=device)
+    return _scratch(max(16, nbytes), device)
 
 
 def linear_wgrad(x, dy, dw, db=None, xidx=None, deterministic=False):
@@ -1444,7 +1451,7 @@ class TrainBlock:
         self.io = _lib.TrainBlockIO()
         self.io_ref = ctypes.byref(self.io)
         self.derived_bytes = train_block_bytes(self, 0, 0)[2]
-        self.derived = torch.empty(self.derived_bytes, dtype=torch.uint8, device=params[0].device)
+        self.derived = _scratch(self.derived_bytes, params[0].device)
         d.derived, d.derived_bytes = self.derived.data_ptr(), self.derived_bytes
         offs = (ctypes.c_size_t * TB_PARAMS)()
         check(self.lib().cdseg_train_block_grad_offsets(self.ref, offs), "train_block_grad_offsets")
@@ -1684,7 +1691,7 @@ def _a16(t):
 
 
 def _bn_ws(lib, m, c, device):
-    return torch.empty(max(16, lib.cdseg_bn_ws_bytes(int(m), int(c))), dtype=torch.uint8, device=device)
+    return _scratch(max(16, lib.cdseg_bn_ws_bytes(int(m), int(c))), device)
 
 
 def bn_stats(x):
@@ -1820,7 +1827,7 @@ def seg_loss(logits, labels, ignore_index, plan=None):
     lib = _lib.load()
     out = torch.empty(2, dtype=torch.float32, device=logits.device)
     coef = torch.empty((n, plan["present"]), dtype=torch.float32, device=logits.device)
-    ws = torch.empty(max(16, lib.cdseg_seg_loss_ws_bytes(n, c)), dtype=torch.uint8, device=logits.device)
+    ws = _scratch(max(16, lib.cdseg_seg_loss_ws_bytes(n, c)), logits.device)
     check(lib.cdseg_seg_loss_fwd(_ptr(logits), logits.stride(0), _ptr(plan["labels"]), n, c, plan["ignore_index"], 1, None,
                                  plan["hist_host"], _ptr(out), _ptr(coef), _ptr(ws), ws.numel(), _stream()), "seg_loss")
     return out[0], out[1], dict(plan, coef=coef)

@@ -207,7 +207,7 @@ class FusedAdamW(torch.optim.Optimizer):
         check(lib.cdseg_opt_chunks(sizes, count, chunks, ctypes.byref(nchunks)), "opt_chunks")
         self._nchunks = nchunks.value
         self._chunks = torch.tensor(list(chunks), dtype=torch.int32).to(self.device)  # uploaded once per optimizer
-        self._ws = torch.empty(max(256, lib.cdseg_opt_ws_bytes(count, self._nchunks)), dtype=torch.uint8, device=self.device)
+        self._ws = ops._scratch(max(256, lib.cdseg_opt_ws_bytes(count, self._nchunks)), self.device)
         self._out = torch.zeros(3, dtype=torch.float32, device=self.device)
         self.last_grad_norm, self.last_clip_coef, self.last_nonfinite = self._out[0], self._out[1], self._out[2]
         # two host tables, taken in turn: the library copies a table with hipMemcpyAsync from pageable memory, which the

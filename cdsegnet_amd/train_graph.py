@@ -95,6 +95,7 @@ from . import _lib
 from ._lib import DuplicateVoxelsError
 from . import ops
 from .ops import det_kw as _det_kw  # (by name: tests swap `ops` for the CPU emulation, which has no such helper)
+from . import ops as _alloc  # (the allocator of the Block's tape / scratch / gradient slab: never the emulation's; looked up per call)
 from .losses import TRAIN_LOSSES, build_criteria
 from .optim import shadow16 as _shadow16
 
@@ -516,8 +517,8 @@ class _NativeBlock(torch.autograd.Function):
         n = x_in.shape[0]
         tape_b, scratch_b, _, grads_b = ops.train_block_bytes(tb, n, psh[-1])
         dev = x_in.device
-        tape = torch.empty(tape_b, dtype=torch.uint8, device=dev)
-        scratch = torch.empty(scratch_b, dtype=torch.uint8, device=dev)
+        tape = _alloc._scratch(tape_b, dev)
+        scratch = _alloc._scratch(scratch_b, dev)
         x_out = torch.empty_like(x_in)
         ops.train_block_forward(tb, n, x_in, xc, t_rows, scene_offs, mask1, mask2, nbr, gidx, widx, patch_start, psh, tape, scratch,
                                 x_out, **({} if rows is None else dict(rows=rows)))
@@ -545,8 +546,8 @@ class _NativeBlock(torch.autograd.Function):
         dx_in = torch.empty_like(x_in)
         dx_conv = torch.empty_like(x_in) if has_xc else None
         dt_rows = torch.empty_like(t_rows) if has_t else None
-        slab = torch.empty(grads_b, dtype=torch.uint8, device=dev)
-        scratch = torch.empty(scratch_b, dtype=torch.uint8, device=dev)
+        slab = _alloc._scratch(grads_b, dev)
+        scratch = _alloc._scratch(scratch_b, dev)
         ops.train_block_backward(tb, n, x_in, xc, t_rows, scene_offs, mask1, mask2, nbr, gidx, widx, patch_start, psh, tape, scratch,
                                  None, dy, dx_in, dx_conv, dt_rows, slab, **rows)
         grads = ops.train_block_grad_views(tb, slab)

@@ -218,7 +218,10 @@ int cdseg_gemm(const cdseg_gemm_args* args_host, void* stream);
 /* ------------------------------------------------------------------ LayerNorm
  * out = [res +] LayerNorm(x) * gamma + beta [+ colbias]; optional second copy out2.
  * ref: nn.LayerNorm(eps 1e-5) at ptv3.py:365, 367, 381 and the CPE residual ptv3.py:401-404,
- * t-embedding bias ptv3.py:406-411. */
+ * t-embedding bias ptv3.py:406-411.
+ * c % 4 == 0, c <= 2048; every row stride % 4 == 0; every access is a group of four elements, so x / out / out2 are 16-byte
+ * aligned as fp32 and 8-byte aligned as the 16-bit type, gamma / beta / res / colbias 16-byte aligned (CDSEG_ERR_ARG otherwise,
+ * nothing is launched).  res may be out (in place on the residual). */
 int cdseg_layernorm(const void* x, int x_dtype, int ldx, const float* gamma, const float* beta, float eps,
                     const float* res, int ldres, const float* colbias, void* out, int out_dtype, int ldo,
                     void* out2, int out2_dtype, int ldo2, long m, int c, void* stream);
@@ -264,7 +267,9 @@ int cdseg_prof_summary_class(int cls, double* total_ms, long* launches);
 
 /* ------------------------------------------------------------------ pooling reduce
  * out[j] = act(max_{i in run j} y[i] * scale + shift), runs = seg_start (m+1).
- * ref: ptv3.py:510-515 (torch_scatter.segment_csr(..., "max")) + norm/act :548-551 */
+ * ref: ptv3.py:510-515 (torch_scatter.segment_csr(..., "max")) + norm/act :548-551
+ * c % 4 == 0, ldy / ldo / ldo2 % 4 == 0; out, scale and shift 16-byte aligned, y and out2 16-byte aligned as fp32 and 8-byte
+ * aligned as the 16-bit type (CDSEG_ERR_ARG otherwise, nothing is launched).  Every run holds at least one row. */
 int cdseg_segment_max(const void* y, int y_dtype, int ldy, const int32_t* seg_start, long m, int c,
                       const float* scale, const float* shift, int act, float* out, int ldo, void* out2,
                       int out2_dtype, int ldo2, void* stream);
