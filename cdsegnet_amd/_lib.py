@@ -284,6 +284,10 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "cdseg_segment_max_arg": (c_int, [c_void_p, c_int, c_void_p, c_long, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "cdseg_segment_max_bwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_long, c_int, c_void_p, c_int, c_void_p]),
+    "cdseg_fuse_gate_ws_bytes": (c_size_t, [c_long, c_int]),
+    "cdseg_fuse_gate_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p]),
+    "cdseg_fuse_gate_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_long, c_int, c_void_p, c_size_t, c_void_p]),
     "cdseg_opt_chunks": (c_int, [POINTER(c_long), c_int, POINTER(c_int32), POINTER(c_long)]),
     "cdseg_opt_ws_bytes": (c_size_t, [c_int, c_long]),
     "cdseg_grad_norm": (c_int, [POINTER(OptTensor), c_int, c_void_p, c_long, c_void_p, c_float, c_void_p, c_void_p, c_size_t,

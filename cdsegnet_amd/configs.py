@@ -82,11 +82,18 @@ _MODEL = dict(
 )
 
 
-def cdsegnet_config(dataset="scannet"):
+def _fusion(b, tm_feat, tm_bidirectional):
+    """The two Feature Fusion Module switches of every shipped config (`tm_feat = 1.0 # "channel_scale", "b_channel_scale",
+    "lr_scale", "b_lr_scale", 1.0`, `tm_bidirectional = False`); the defaults leave the dict as it was."""
+    b["tm_feat"], b["tm_bidirectional"] = tm_feat, bool(tm_bidirectional)
+
+
+def cdsegnet_config(dataset="scannet", tm_feat=1.0, tm_bidirectional=False):
     """``model`` dict of configs/<dataset>/CDSegNet.py (criteria dropped: the tester
-    calls inference(eval=False), test.py:216)."""
+    calls inference(eval=False), test.py:216).  tm_feat / tm_bidirectional: the fusion ablation switches."""
     m = copy.deepcopy(_MODEL)
     b = m["backbone"]
+    _fusion(b, tm_feat, tm_bidirectional)
     if dataset == "scannet":
         pass
     elif dataset == "scannet200":
@@ -136,11 +143,12 @@ def model_config(dataset="scannet", variant="CDSegNet"):
     return m
 
 
-def mini_config(num_classes=13, in_channels=6, T_dim=64):
+def mini_config(num_classes=13, in_channels=6, T_dim=64, tm_feat=1.0, tm_bidirectional=False):
     """Same architecture, reduced widths/depths (head dim stays 16): the end-to-end
-    golden fixture that fits in a few hundred KB."""
+    golden fixture that fits in a few hundred KB.  tm_feat / tm_bidirectional: the fusion ablation switches."""
     m = copy.deepcopy(_MODEL)
     b = m["backbone"]
+    _fusion(b, tm_feat, tm_bidirectional)
     b.update(
         c_in_channels=in_channels, n_in_channels=in_channels,
         c_enc_depths=(1, 2, 1), c_enc_channels=(16, 32, 32), c_enc_num_head=(1, 2, 2),

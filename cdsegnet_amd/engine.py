@@ -28,6 +28,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import CdsegError, DuplicateVoxelsError
+from .models import fusion_gate
 
 CURVES = ("z", "z-trans", "hilbert", "hilbert-trans")
 
@@ -600,22 +601,41 @@ class Engine:
                 w["t.mlp.w"], w["t.mlp.b"] = torch.cat(tw).contiguous(), torch.cat(tb).contiguous()
                 w["t.table"] = f32(self.model.t_emb_table)
                 self.t_slices = toff
-            cb = bb._tm_dec0.cross_block2
-            conv(cb.q_cpe[0], "x.q_cpe0"); lin(cb.q_cpe[1], "x.q_cpe1"); ln(cb.q_cpe[2], "x.q_cpe2")
-            conv(cb.kv_cpe[0], "x.kv_cpe0"); lin(cb.kv_cpe[1], "x.kv_cpe1"); ln(cb.kv_cpe[2], "x.kv_cpe2")
-            ln(cb.q_norm1[0], "x.q_norm1"); ln(cb.kv_norm1[0], "x.kv_norm1"); ln(cb.q_norm2[0], "x.q_norm2")
-            lin_q(cb.attn.q, "x.q", cb.attn.scale, cb.q_channels); lin(cb.attn.kv, "x.kv"); lin(cb.attn.proj, "x.proj")
-            lin(cb.mlp[0].fc1, "x.fc1"); lin(cb.mlp[0].fc2, "x.fc2")
-            if cb.tm_feat != 1.0:
-                c = cb.q_channels
-                w["x.feat_scale"] = torch.full((c,), cb.tm_feat, dtype=torch.float32, device=device)
-                w["x.feat_zero"] = torch.zeros(c, dtype=torch.float32, device=device)
-            elif (hasattr(ops, "block_rr_pack") and ops.block_rr_ok(cb.q_channels, T) and cb.q_channels in ops.DEEP_CHANNELS
-                  and w["x.fc1.w"].shape[0] == 4 * cb.q_channels):  # (deep.hip's streamed-weight image only: the LDS-resident
-                # C = 32 / 64 pack needs the head weights too)
-                # the cross block's tail (x += proj(attn); h = LN(x); x += MLP(h), ptv3.py:1205-1222) has a Block tail's
-                # shape: one launch on the streamed-weight kernel (csrc/deep.hip) instead of three GEMMs + their second passes
-                _, w["x.tail_img"] = ops.block_rr_pack(cb.q_channels, None, None, w["x.proj.w"], w["x.fc1.w"], w["x.fc2.w"])
+            def xblock(cb, pre):
+                conv(cb.q_cpe[0], pre + ".q_cpe0"); lin(cb.q_cpe[1], pre + ".q_cpe1"); ln(cb.q_cpe[2], pre + ".q_cpe2")
+                conv(cb.kv_cpe[0], pre + ".kv_cpe0"); lin(cb.kv_cpe[1], pre + ".kv_cpe1"); ln(cb.kv_cpe[2], pre + ".kv_cpe2")
+                ln(cb.q_norm1[0], pre + ".q_norm1"); ln(cb.kv_norm1[0], pre + ".kv_norm1"); ln(cb.q_norm2[0], pre + ".q_norm2")
+                lin_q(cb.attn.q, pre + ".q", cb.attn.scale, cb.q_channels); lin(cb.attn.kv, pre + ".kv"); lin(cb.attn.proj, pre + ".proj")
+                lin(cb.mlp[0].fc1, pre + ".fc1"); lin(cb.mlp[0].fc2, pre + ".fc2")
+                learned = isinstance(cb.tm_feat, str)
+                if learned:
+                    # a learned gate alpha * q_shortcut + gamma * attn (models.fusion_gate), folded once per weight version:
+                    # gamma scales the rows of proj (weight and bias, in fp32, before the cast) in all four modes, so the
+                    # proj / tail kernels run as for tm_feat = 1; the two b modes hand them alpha * x as the residual operand
+                    # (run_cross_block), alpha kept here
+                    with torch.no_grad():
+                        alpha, gamma = (f32(v) for v in fusion_gate(cb))
+                        pw = cb.attn.proj.weight.detach().to(device=device, dtype=torch.float32)
+                        w[pre + ".proj.w"] = (gamma[:, None] * pw).to(T).contiguous()
+                        if w[pre + ".proj.b"] is not None:
+                            w[pre + ".proj.b"] = (gamma * w[pre + ".proj.b"]).contiguous()
+                    if cb.tm_feat.startswith("b_"):
+                        w[pre + ".gate_alpha"] = alpha
+                        w[pre + ".gate_zero"] = torch.zeros_like(alpha)
+                if not learned and cb.tm_feat != 1.0:
+                    c = cb.q_channels
+                    w[pre + ".feat_scale"] = torch.full((c,), cb.tm_feat, dtype=torch.float32, device=device)
+                    w[pre + ".feat_zero"] = torch.zeros(c, dtype=torch.float32, device=device)
+                elif (hasattr(ops, "block_rr_pack") and ops.block_rr_ok(cb.q_channels, T) and cb.q_channels in ops.DEEP_CHANNELS
+                      and w[pre + ".fc1.w"].shape[0] == 4 * cb.q_channels):  # (deep.hip's streamed-weight image only: the LDS-resident
+                    # C = 32 / 64 pack needs the head weights too)
+                    # the cross block's tail (x += proj(attn); h = LN(x); x += MLP(h), ptv3.py:1205-1222) has a Block tail's
+                    # shape: one launch on the streamed-weight kernel (csrc/deep.hip) instead of three GEMMs + their second passes
+                    _, w[pre + ".tail_img"] = ops.block_rr_pack(cb.q_channels, None, None, w[pre + ".proj.w"], w[pre + ".fc1.w"], w[pre + ".fc2.w"])
+
+            if bb._tm_dec0.tm_bidirectional:
+                xblock(bb._tm_dec0.cross_block1, "x1")  # (c <- n; runs in front of cross_block2)
+            xblock(bb._tm_dec0.cross_block2, "x")
         self.w = w
         self._tb_cache = {}
         if T == torch.float16:
@@ -1139,10 +1159,12 @@ class Engine:
             for s in range(ns - 1):
                 stage(getattr(getattr(bb, f"_{branch}_dec"), f"dec{s}"), plan.levels[cum[s]])
         if bb.condition:
-            att = bb._tm_dec0.cross_block2.attn
-            for lv in (plan.levels[plan.n_cum[-1]], plan.levels[plan.c_cum[-1]]):
-                lv.nbr(3, True)
-                attn(lv, att.q_patch_size, att.enable_flash)
+            tm = bb._tm_dec0
+            for cb in ([tm.cross_block1] if tm.tm_bidirectional else []) + [tm.cross_block2]:
+                att = cb.attn
+                for lv in (plan.levels[plan.n_cum[-1]], plan.levels[plan.c_cum[-1]]):
+                    lv.nbr(3, True)
+                    attn(lv, att.q_patch_size, att.enable_flash)
 
     def _check_plan(self, plan, input_dict, n, offset_host):
         """A forward was handed a plan: its level-0 size and per-element offsets against the input's HOST values (no device
@@ -1419,64 +1441,76 @@ class Engine:
         out.parent = parent.parent
         return out
 
-    def run_cross_block(self, nst, cst):
-        """ref: ptv3.py:1179-1223 + :988-1055 (cross_block2: n <- c, the NN->CN feature injection)."""
+    def run_cross_block(self, qst, kvst, cb, pre, keep_kv_x=False):
+        """ref: ptv3.py:1179-1223 + :988-1055.  CrossBlock `cb` with the weights of prefix `pre`, `qst` as its q point and
+        `kvst` as its kv point: cross_block2 ("x": n <- c, the NN->CN feature injection) and, in a bidirectional model, in
+        front of it cross_block1 ("x1": c <- n).  keep_kv_x: a later stage reads the kv point's fp32 stream (cross_block2 reads
+        the n point that cross_block1 normed), so a 16-bit engine writes it too."""
         w = self.w
-        cb = self.model.backbone._tm_dec0.cross_block2
         att = cb.attn
-        lv, clv = nst.level, cst.level
+        lv, klv = qst.level, kvst.level
         # the reference pads the kv sequence with the q point's padding plan (ptv3.py:1009): the two bottlenecks must
         # hold the same number of points per batch element.  They are the same voxel set in every shipped config; a
         # scene whose grid is shallower than the pooling depths can end on different levels with equal counts
-        if clv is not lv and list(clv.offs_host) != list(lv.offs_host):
+        if klv is not lv and list(klv.offs_host) != list(lv.offs_host):
             raise CdsegError("cross attention needs the same number of c- and n-branch bottleneck points per batch "
                              "element (ref: ptv3.py:1009 reuses the q padding for kv)")
-        n, cq = nst.x.shape
-        self._cpe(nst, "x.q_cpe", nst.xc)
-        self._cpe(cst, "x.kv_cpe", cst.xc)
+        n, cq = qst.x.shape
+        self._cpe(qst, pre + ".q_cpe", qst.xc)
+        self._cpe(kvst, pre + ".kv_cpe", kvst.xc)
         hq = self._buf(n, cq, self.T)
-        ops.layernorm(nst.x, w["x.q_norm1.g"], w["x.q_norm1.b"], hq)
-        hkv = self._buf(n, cst.x.shape[1], self.T)
-        ops.layernorm(cst.x, w["x.kv_norm1.g"], w["x.kv_norm1.b"], hkv)
-        # the kv point LEAVES the block holding kv_norm1(c + kv_cpe(c)) in feat and sparse_conv_feat (PointSequential
+        ops.layernorm(qst.x, w[pre + ".q_norm1.g"], w[pre + ".q_norm1.b"], hq)
+        hkv = self._buf(n, kvst.x.shape[1], self.T)
+        # the kv point LEAVES the block holding kv_norm1(kv + kv_cpe(kv)) in feat and sparse_conv_feat (PointSequential
         # assigns the LayerNorm output in place, ptv3.py:1190-1196, modules.py:68-73): that is what the c-decoder of the
-        # multi-step path reads next (oracle/model.py: cross_block, `kvp.feat = hkv`)
-        cst.xc = hkv
+        # multi-step path reads next (oracle/model.py: cross_block, `kvp.feat = hkv`), and what cross_block2 takes as its q
+        # point behind cross_block1
+        if keep_kv_x and self.T != torch.float32:
+            hkv32 = self._buf(n, kvst.x.shape[1], torch.float32)
+            ops.layernorm(kvst.x, w[pre + ".kv_norm1.g"], w[pre + ".kv_norm1.b"], hkv, out2=hkv32)
+            kvst.x = hkv32
+        else:
+            ops.layernorm(kvst.x, w[pre + ".kv_norm1.g"], w[pre + ".kv_norm1.b"], hkv)
+        kvst.xc = hkv
         if self.T == torch.float32:
-            cst.x = hkv
+            kvst.x = hkv
         q = self._buf(n, cq, self.T)
-        ops.gemm(hq, w["x.q.w"], q, bias=w["x.q.b"])
+        ops.gemm(hq, w[pre + ".q.w"], q, bias=w[pre + ".q.b"])
         kv = self._buf(n, 2 * cq, self.T)
-        ops.gemm(hkv, w["x.kv.w"], kv, bias=w["x.kv.b"])
+        ops.gemm(hkv, w[pre + ".kv.w"], kv, bias=w[pre + ".kv.b"])
         K = att.q_patch_size
-        q_gidx, widx = lv.slots(nst.curves[att.order_index], K, att.enable_flash)
-        kv_gidx, _ = clv.slots(cst.curves[att.order_index], K, att.enable_flash)
+        q_gidx, widx = lv.slots(qst.curves[att.order_index], K, att.enable_flash)
+        kv_gidx, _ = klv.slots(kvst.curves[att.order_index], K, att.enable_flash)
         _, _, _, _, patch_start, max_len, sum_l2 = lv.pad(K, att.enable_flash)
         work = 64.0 * att.num_heads * lv.attn_l2(K, att.enable_flash)
         self._add_work(work, 4.0 * n * cq * q.element_size())
         o = self._buf(n, cq, self.T)
         ops.attention(q, kv[:, :cq], kv[:, cq:], q_gidx, kv_gidx, widx, patch_start, att.num_heads, max_len, att.scale, o,
                       work=work, flags=ops.ATTN_Q_PRESCALED if self.q_prescaled else 0)
-        if "x.tail_img" in w and n >= ops.DEEP512_MIN_ROWS:
-            nst.xc = self._buf(n, cq, self.T)
-            ops.attn_tail_rr(o, w["x.tail_img"], w["x.proj.b"], w["x.q_norm2.g"], w["x.q_norm2.b"], w["x.fc1.b"], w["x.fc2.b"],
-                             nst.x, nst.xc)
+        if (pre + ".gate_alpha") in w:
+            # blending gate: (1 - gamma) * q_shortcut in a fresh buffer is the residual operand of the proj / tail kernel below
+            # (gamma itself sits in the rows of proj, _prepare)
+            qst.x = ops.fuse_gate_fwd(qst.x, None, w[pre + ".gate_alpha"], w[pre + ".gate_zero"])
+        if (pre + ".tail_img") in w and n >= ops.DEEP512_MIN_ROWS:
+            qst.xc = self._buf(n, cq, self.T)
+            ops.attn_tail_rr(o, w[pre + ".tail_img"], w[pre + ".proj.b"], w[pre + ".q_norm2.g"], w[pre + ".q_norm2.b"],
+                             w[pre + ".fc1.b"], w[pre + ".fc2.b"], qst.x, qst.xc)
             return
-        if "x.tail_img" in w and hasattr(ops, "attn_tail_rr2"):
+        if (pre + ".tail_img") in w and hasattr(ops, "attn_tail_rr2"):
             # few rows (a single scene's bottleneck): the tile's weight stream cut over four workgroups (csrc/deep.hip) - the
             # residual is read from the old rows and the result lands in fresh ones, so no workgroup reads what another writes
             x_new = self._buf(n, cq, torch.float32)
-            nst.xc = self._buf(n, cq, self.T)
-            ops.attn_tail_rr2(o, w["x.tail_img"], w["x.proj.b"], w["x.q_norm2.g"], w["x.q_norm2.b"], w["x.fc1.b"], w["x.fc2.b"],
-                              nst.x, x_new, nst.xc, ws=self.scratch(4 * n * cq * 4 + 256))
-            nst.x = x_new
+            qst.xc = self._buf(n, cq, self.T)
+            ops.attn_tail_rr2(o, w[pre + ".tail_img"], w[pre + ".proj.b"], w[pre + ".q_norm2.g"], w[pre + ".q_norm2.b"],
+                              w[pre + ".fc1.b"], w[pre + ".fc2.b"], qst.x, x_new, qst.xc, ws=self.scratch(4 * n * cq * 4 + 256))
+            qst.x = x_new
             return
-        if cb.tm_feat == 1.0:
-            ops.gemm(o, w["x.proj.w"], nst.x, bias=w["x.proj.b"], res=nst.x)
+        if (pre + ".feat_scale") not in w:
+            ops.gemm(o, w[pre + ".proj.w"], qst.x, bias=w[pre + ".proj.b"], res=qst.x)
         else:  # q_shortcut + feat_scale * attn
-            ops.gemm(o, w["x.proj.w"], nst.x, bias=w["x.proj.b"], scale=w["x.feat_scale"], shift=w["x.feat_zero"],
-                     res=nst.x)
-        self._mlp(nst, "x.q_norm2", "x.fc")
+            ops.gemm(o, w[pre + ".proj.w"], qst.x, bias=w[pre + ".proj.b"], scale=w[pre + ".feat_scale"],
+                     shift=w[pre + ".feat_zero"], res=qst.x)
+        self._mlp(qst, pre + ".q_norm2", pre + ".fc")
 
     # ------------------------------------------------------------------ accounting
     def forward_work(self, plan):
@@ -1520,13 +1554,14 @@ class Engine:
         if bb.condition:
             out["stem"] += 2.0 * occ(lv0, 5) * bb._c_embedding.stem.conv.in_channels * w["c_emb.w"].shape[0]
             stages("c", plan.c_cum, bb.c_num_stages)
-            cb = bb._tm_dec0.cross_block2
-            lq, lc = plan.levels[plan.n_cum[-1]], plan.levels[plan.c_cum[-1]]
-            cq, ck = cb.q_channels, cb.kv_channels
-            out["conv"] += 2.0 * occ(lq, 3) * cq * cq + 2.0 * occ(lc, 3) * ck * ck
-            deep[0] += 2.0 * occ(lq, 3) * cq * cq + 2.0 * occ(lc, 3) * ck * ck
-            out["linear"] += 2.0 * lq.n * (cq * cq * 3 + 2.0 * cq * w["x.fc1.w"].shape[0]) + 2.0 * lc.n * (ck * ck + ck * 2 * cq)
-            out["attention"] += 64.0 * cb.attn.num_heads * lq.attn_l2(cb.attn.q_patch_size, cb.attn.enable_flash)
+            ln_, lc_ = plan.levels[plan.n_cum[-1]], plan.levels[plan.c_cum[-1]]
+            tm = bb._tm_dec0
+            for cb, pre, lq, lc in ([(tm.cross_block1, "x1", lc_, ln_)] if tm.tm_bidirectional else []) + [(tm.cross_block2, "x", ln_, lc_)]:
+                cq, ck = cb.q_channels, cb.kv_channels
+                out["conv"] += 2.0 * occ(lq, 3) * cq * cq + 2.0 * occ(lc, 3) * ck * ck
+                deep[0] += 2.0 * occ(lq, 3) * cq * cq + 2.0 * occ(lc, 3) * ck * ck
+                out["linear"] += 2.0 * lq.n * (cq * cq * 3 + 2.0 * cq * w[pre + ".fc1.w"].shape[0]) + 2.0 * lc.n * (ck * ck + ck * 2 * cq)
+                out["attention"] += 64.0 * cb.attn.num_heads * lq.attn_l2(cb.attn.q_patch_size, cb.attn.enable_flash)
         for s in reversed(range(bb.n_num_stages - 1)):
             lf, lc = plan.levels[plan.n_cum[s]], plan.levels[plan.n_cum[s + 1]]
             pre = f"n_dec{s}.up"
@@ -1952,7 +1987,10 @@ class Engine:
             e = self._eng("x")
             e._fit(nst)
             e._fit(cst)
-            e.run_cross_block(nst, cst)
+            tm = bb._tm_dec0
+            if tm.tm_bidirectional:  # (ptv3.py:1332-1337; it always runs: cross_block2 reads its output, want_c or not)
+                e.run_cross_block(cst, nst, tm.cross_block1, "x1", keep_kv_x=True)
+            e.run_cross_block(nst, cst, tm.cross_block2, "x")
         else:
             nst = self._eng("n_emb").run_embedding(plan, feat, plan.perm0, "n_emb", n_curves)
             plan.finish_pads()

@@ -7,7 +7,9 @@ point_transformer_v3m1_base.py:1340-1755), so released checkpoints load ``strict
 unchanged.  The ``nn.Module`` tree below only OWNS parameters (names/shapes = the reference's);
 the forward pass is executed by ``cdsegnet_amd.engine`` on hand-written HIP kernels.
 Options that every shipped CDSegNet config leaves off (RPE, PDNorm, Restormer fusion,
-bidirectional fusion, FreeU, cls_mode) are accepted by the constructors and rejected loudly.
+FreeU, cls_mode) are accepted by the constructors and rejected loudly.  The two Feature Fusion Module
+switches the shipped configs spell out - learned fusion scales (``tm_feat``) and bidirectional fusion
+(``tm_bidirectional``) - are built.
 """
 import math
 
@@ -198,6 +200,26 @@ class SerializedCrossAttention(nn.Module):
         self.proj = nn.Linear(q_channels, q_channels)
 
 
+# tm_feat mode -> (feat_scale per channel (1, C) or scalar (1,), its initial value)   (ptv3.py:1091-1103)
+FUSION_MODES = {"channel_scale": (True, 1.0), "b_channel_scale": (True, 0.5), "lr_scale": (False, 1.0), "b_lr_scale": (False, 0.5)}
+
+
+def gate_vectors(mode, p, c):
+    """(alpha, gamma), two (c,) vectors in p's dtype, of the learned fusion gate `mode` with parameter p ((1,) or (1, c)):
+    y = alpha * q_shortcut + gamma * attn (ptv3.py:1196-1206).  The sigmoid belongs to the two channel modes only; the two b
+    modes blend (alpha = 1 - gamma).  Differentiable in p."""
+    g = (torch.sigmoid(p) if FUSION_MODES[mode][0] else p).reshape(-1).expand(c)
+    return (1 - g if mode.startswith("b_") else torch.ones_like(g)), g
+
+
+def fusion_gate(cb, dtype=torch.float32):
+    """(alpha, gamma) of CrossBlock `cb`, learned (`gate_vectors` of its feat_scale) or a number f (alpha = 1, gamma = f)."""
+    if isinstance(cb.tm_feat, float):
+        g = torch.full((cb.q_channels,), cb.tm_feat, dtype=dtype)
+        return torch.ones_like(g), g
+    return gate_vectors(cb.tm_feat, cb.feat_scale.to(dtype), cb.q_channels)
+
+
 class CrossBlock(nn.Module):
     """ref: ptv3.py:1058-1223."""
 
@@ -206,9 +228,18 @@ class CrossBlock(nn.Module):
                  tm_feat=1.0, drop_path=0.0):
         super().__init__()
         self.drop_prob = float(drop_path)
-        if not isinstance(tm_feat, (int, float)):
-            raise NotImplementedError(f"tm_feat={tm_feat!r}: learned fusion scales are off in every shipped config")
-        self.tm_feat = float(tm_feat)
+        # the fusion gate (ptv3.py:1091-1103): a number f, or one of FUSION_MODES with a learned `feat_scale` - registered
+        # FIRST, like the reference's, so that the state_dict keys keep its order
+        if isinstance(tm_feat, str):
+            if tm_feat not in FUSION_MODES:
+                raise NotImplementedError(f"tm_feat={tm_feat!r}: the learned fusion scales are {', '.join(map(repr, FUSION_MODES))}")
+            per_channel, init = FUSION_MODES[tm_feat]
+            self.tm_feat = tm_feat
+            self.feat_scale = nn.Parameter(torch.full((1, q_channels) if per_channel else (1,), init))
+        elif isinstance(tm_feat, (int, float)):
+            self.tm_feat = float(tm_feat)
+        else:
+            raise NotImplementedError(f"tm_feat={tm_feat!r}: a number or one of {', '.join(map(repr, FUSION_MODES))}")
         self.q_channels, self.kv_channels = q_channels, kv_channels
         self.q_cpe = PointSequential(SubMConv3d(q_channels, q_channels, 3, bias=True, indice_key=q_cpe_indice_key),
                                      nn.Linear(q_channels, q_channels), nn.LayerNorm(q_channels))
@@ -224,10 +255,18 @@ class CrossBlock(nn.Module):
 
 
 class TransferModule(nn.Module):
-    """ref: ptv3.py:1225-1337 (tm_bidirectional=False: only cross_block2(n <- c))."""
+    """ref: ptv3.py:1225-1337: cross_block2 (n <- c), and in front of it, with tm_bidirectional, cross_block1 (c <- n) - the
+    same block with the roles swapped (:1261-1295), registered first."""
 
-    def __init__(self, **kw):
+    def __init__(self, tm_bidirectional=False, kv_num_heads=None, kv_drop_path=0.0, **kw):
         super().__init__()
+        self.tm_bidirectional = bool(tm_bidirectional)
+        if self.tm_bidirectional:
+            swapped = dict(kw, q_channels=kw["kv_channels"], kv_channels=kw["q_channels"], num_heads=kv_num_heads,
+                           q_patch_size=kw["kv_patch_size"], kv_patch_size=kw["q_patch_size"],
+                           q_cpe_indice_key=kw.get("kv_cpe_indice_key"), kv_cpe_indice_key=kw.get("q_cpe_indice_key"),
+                           drop_path=kv_drop_path)
+            self.cross_block1 = CrossBlock(**swapped)
         self.cross_block2 = CrossBlock(**kw)
 
 
@@ -254,7 +293,7 @@ class PointTransformerV3(nn.Module):
     ):
         super().__init__()
         _reject(enable_rpe=(enable_rpe, False), cls_mode=(cls_mode, False), pdnorm_bn=(pdnorm_bn, False),
-                pdnorm_ln=(pdnorm_ln, False), tm_bidirectional=(tm_bidirectional, False),
+                pdnorm_ln=(pdnorm_ln, False),
                 tm_restomer=(tm_restomer, False), pre_norm=(pre_norm, True))
         self.order = [order] if isinstance(order, str) else list(order)
         for o in self.order:
@@ -344,7 +383,9 @@ class PointTransformerV3(nn.Module):
                 q_patch_size=n_enc_patch_size[-1], kv_patch_size=c_enc_patch_size[-1], mlp_ratio=mlp_ratio,
                 qkv_bias=qkv_bias, qk_scale=qk_scale, order_index=0, q_cpe_indice_key="stage2",
                 kv_cpe_indice_key="stage2", enable_flash=enable_flash, tm_feat=tm_feat,
-                drop_path=c_enc_dp[2] if len(c_enc_dp) > 2 else 0.0)  # (ptv3.py:1735-1736)
+                drop_path=c_enc_dp[2] if len(c_enc_dp) > 2 else 0.0,  # (ptv3.py:1735-1736)
+                tm_bidirectional=tm_bidirectional, kv_num_heads=c_enc_num_head[-1],
+                kv_drop_path=c_enc_dp[2] if len(c_enc_dp) > 2 else 0.0)
 
     def forward(self, c_point=None, n_point=None):
         raise NotImplementedError(

@@ -1760,6 +1760,52 @@ def bn_gelu_bwd(x, dy, mean, invstd, gamma, beta, count, hook=None, out=None):
     return dx, gsums
 
 
+def _fg_rows(what, *ts):
+    for t in ts:
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or t.shape != ts[0].shape):
+            raise _lib.CdsegError(f"{what}: contiguous fp32 (rows, c) tensors of one shape")
+
+
+def _fg_mask(what, m, rows):
+    if m is None:
+        return None
+    if m.dtype != torch.float32 or not m.is_contiguous() or m.numel() != rows:
+        raise _lib.CdsegError(f"{what}: the DropPath factors are one contiguous fp32 value per row")
+    return m
+
+
+def fuse_gate_fwd(s, a, alpha, gamma, m=None, out=None):
+    """The fusion gate of a CrossBlock (cdseg_fuse_gate_fwd): y = alpha * s + gamma * m[:, None] * a on fp32 (rows, c); alpha,
+    gamma (c) per channel, m (rows) the DropPath factors or None; a None: y = alpha * s.  out: the tensor to write (may be s).
+    c up to 512; a width that is no multiple of 4, or an operand off a 16-byte boundary, takes the library's scalar path."""
+    _need_gpu(s, a, m, alpha, gamma)
+    y = torch.empty_like(s) if out is None else out
+    _fg_rows("fuse_gate_fwd", s, a, y)
+    rows, c = s.shape
+    check(_lib.load().cdseg_fuse_gate_fwd(_ptr(s), _ptr(a), _ptr(_fg_mask("fuse_gate_fwd", m, rows)), _ptr(_a16(alpha)),
+                                          _ptr(_a16(gamma)), _ptr(y), rows, c, _stream()), "fuse_gate_fwd")
+    return y
+
+
+def fuse_gate_bwd(dy, s, a, alpha, gamma, m=None):
+    """Backward of `fuse_gate_fwd` (cdseg_fuse_gate_bwd): returns (ds, da, sums) with ds = alpha * dy, da = gamma * m * dy and
+    sums (2 c) fp64 = [sum_r dy m a, sum_r dy s] - the gradients of gamma and of alpha - added in fp64 in an order fixed by the
+    shape (no atomics: equal inputs give equal bits)."""
+    _need_gpu(dy, s, a, m, alpha, gamma)
+    _fg_rows("fuse_gate_bwd", dy, s, a)
+    rows, c = s.shape
+    ds, da = torch.empty_like(s), torch.empty_like(s)
+    if rows == 0:
+        return ds, da, torch.zeros(2 * c, dtype=torch.float64, device=s.device)
+    lib = _lib.load()
+    sums = torch.empty(2 * c, dtype=torch.float64, device=s.device)
+    ws = _scratch(max(16, lib.cdseg_fuse_gate_ws_bytes(rows, c)), s.device)
+    check(lib.cdseg_fuse_gate_bwd(_ptr(dy), _ptr(s), _ptr(a), _ptr(_fg_mask("fuse_gate_bwd", m, rows)), _ptr(_a16(alpha)),
+                                  _ptr(_a16(gamma)), _ptr(ds), _ptr(da), _ptr(sums), rows, c, _ptr(ws), ws.numel(), _stream()),
+          "fuse_gate_bwd")
+    return ds, da, sums
+
+
 def segment_max_arg(y, seg_start, m):
     """(out, arg): out (m, c) fp32 = per-channel maximum over the rows seg_start[j] .. seg_start[j + 1] - 1 of y (the bits of
     `segment_max` without scale / shift / activation), arg (m, c) int32 = the first row that holds it (cdseg_segment_max_arg)."""

@@ -77,6 +77,12 @@ multiplies, GELU, the timestep rows, gradient zero fills, weight transposes, the
 kernels, the derived weights of a Block made once per weight version (ops.train_block_prepare).  The CrossBlock, pooling,
 unpooling, stems, heads and criteria are what they are in the default mode, which is unchanged bit for bit.
 
+Fusion module options (`tm_feat` a learned scale, `tm_bidirectional`; constructor options of the backbone): a learned gate is ONE
+node, `_FuseGate`, over the two kernels of csrc/fusion.hip (`feat_scale` gets its gradient from the backward's two fp64 column sums,
+`gate_dp`; fixed summation order in every mode); a bidirectional model runs `cross_block1` (c <- n) in front of `cross_block2`, with
+the reference's in-place assignments: the n point enters `cross_block2` holding cross_block1's kv_norm1 output.  A numeric `tm_feat`
+without `tm_bidirectional` is the graph it was, bit for bit.  The cross blocks stay autograd nodes under `train_block = "native"`.
+
 Mix3D batches (`model.train_mix3d = "rows"`, default "fold"; read at every forward; no effect on a batch without shared
 voxels): a batch element made of two merged scenes has voxels that hold several points.  "fold" runs the network on the first
 point of every voxel and copies its prediction to the others.  "rows" keeps every point as a row - serialization, attention,
@@ -98,6 +104,7 @@ from .ops import det_kw as _det_kw  # (by name: tests swap `ops` for the CPU emu
 from . import ops as _alloc  # (the allocator of the Block's tape / scratch / gradient slab: never the emulation's; looked up per call)
 from .losses import TRAIN_LOSSES, build_criteria
 from .optim import shadow16 as _shadow16
+from .models import FUSION_MODES as _FUSION_MODES, gate_vectors
 
 
 def _c(t):
@@ -554,6 +561,42 @@ class _NativeBlock(torch.autograd.Function):
         return (None, None, dx_in, dx_conv, dt_rows, None, None, *grads, *([None] * (nw - len(grads))))  # (the 16-bit copies: no gradient)
 
 
+def gate_dp(mode, p, sums):
+    """d loss / d feat_scale (p's shape, fp64) from the two column sums of the gate's backward, sums = [d gamma (c), d alpha (c)]
+    = [sum_r dy m a, sum_r dy s]: gamma = p or sigmoid(p), alpha = 1 or 1 - gamma; a scalar p adds over the channels."""
+    c = sums.numel() // 2
+    d = sums[:c].double()
+    if mode.startswith("b_"):
+        d = d - sums[c:].double()
+    if _FUSION_MODES[mode][0]:
+        sg = torch.sigmoid(p.detach().double().reshape(-1))
+        return (d * sg * (1 - sg)).reshape(p.shape)
+    return d.sum().reshape(p.shape)
+
+
+class _FuseGate(torch.autograd.Function):
+    """The learned gate of a CrossBlock, y = alpha s + gamma m a (`models.gate_vectors`), as one node: forward cdseg_fuse_gate_fwd,
+    backward cdseg_fuse_gate_bwd - ds, da and the two fp64 column sums from which `gate_dp` forms feat_scale's gradient.  The
+    sums run in a fixed order whatever `train_deterministic` says.  fp32 in every train_precision (the Linear outputs are)."""
+
+    @staticmethod
+    def forward(ctx, s, a, m, p, mode):
+        s, a = _c(s.float()), _c(a.float())
+        m = None if m is None else _c(m.float().reshape(-1))
+        alpha, gamma = (_c(v) for v in gate_vectors(mode, p.detach().float(), s.shape[1]))
+        y = ops.fuse_gate_fwd(s, a, alpha, gamma, m)
+        ctx.save_for_backward(s, a, p, alpha, gamma, *(() if m is None else (m,)))
+        ctx.mode = mode
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        s, a, p, alpha, gamma = ctx.saved_tensors[:5]
+        m = ctx.saved_tensors[5] if len(ctx.saved_tensors) > 5 else None
+        ds, da, sums = ops.fuse_gate_bwd(_c(dy.float()), s, a, alpha, gamma, m)
+        return ds, da, None, gate_dp(ctx.mode, p, sums).to(p.dtype), None
+
+
 def _swish(x):  # ptv3.py:30-31
     return x * torch.sigmoid(x)
 
@@ -888,32 +931,37 @@ class TrainGraph:
             out.x = self._lin(torch.cat([par, gathered], dim=-1), up.proj_cat[0])
         return out
 
-    def _cross_block(self, nst, cst, cb, masks):
-        """ref: ptv3.py:1179-1223 + :988-1055 (cross_block2: n <- c)."""
-        lv, clv = nst.level, cst.level
-        if clv is not lv and list(clv.offs_host) != list(lv.offs_host):
+    def _cross_block(self, qst, kvst, cb, name, masks):
+        """ref: ptv3.py:1179-1223 + :988-1055.  CrossBlock `cb` (module path `name`) with `qst` as its q point and `kvst` as its
+        kv point: cross_block2 is (n, c), the cross_block1 of a bidirectional model (c, n).  The kv sequence is padded with the q
+        level's plan (:1009)."""
+        lv, klv = qst.level, kvst.level
+        if klv is not lv and list(klv.offs_host) != list(lv.offs_host):
             raise _engine.CdsegError("cross attention needs the same number of c- and n-branch bottleneck points per batch element")
-        xq = nst.x + self._cpe(lv, nst.x, cb.q_cpe)
-        xkv = cst.x + self._cpe(clv, cst.x, cb.kv_cpe)
+        xq = qst.x + self._cpe(lv, qst.x, cb.q_cpe)
+        xkv = kvst.x + self._cpe(klv, kvst.x, cb.kv_cpe)
         hq, hkv = self._ln(xq, cb.q_norm1[0]), self._ln(xkv, cb.kv_norm1[0])
-        cst.x = hkv  # the kv point leaves the block holding its normed feature (modules.py:68-73)
+        kvst.x = hkv  # the kv point leaves the block holding its normed feature (modules.py:68-73)
         att = cb.attn
         cq = xq.shape[1]
         q = self._lin(hq, att.q)
         kv = self._lin(hkv, att.kv)
         K = att.q_patch_size
-        q_gidx, widx = lv.slots(nst.curves[att.order_index], K, att.enable_flash)
-        kv_gidx, _ = clv.slots(cst.curves[att.order_index], K, att.enable_flash)
+        q_gidx, widx = lv.slots(qst.curves[att.order_index], K, att.enable_flash)
+        kv_gidx, _ = klv.slots(kvst.curves[att.order_index], K, att.enable_flash)
         patch_start, max_len = lv.pad(K, att.enable_flash)[4:6]
         psh = lv.pad_host(K, att.enable_flash)[3].tolist()
         o = attention_core(self.attn_variant, q, kv, cq, q_gidx, kv_gidx, widx, patch_start, psh, att.num_heads, max_len, att.scale)
         a = self._lin(o, att.proj)
-        name = "backbone._tm_dec0.cross_block2.drop_path.0"
-        m = self._mask(nst, name, cb.drop_prob, masks)
-        x = xq + cb.tm_feat * (a if m is None else a * m)
+        name = name + ".drop_path.0"
+        m = self._mask(qst, name, cb.drop_prob, masks)
+        if isinstance(cb.tm_feat, str):  # a learned gate: one node over the two kernels of csrc/fusion.hip
+            x = _FuseGate.apply(xq, a, m, cb.feat_scale, cb.tm_feat)
+        else:
+            x = xq + cb.tm_feat * (a if m is None else a * m)
         h = self._mlp(self._ln(x, cb.q_norm2[0]), cb.mlp[0])
-        m = self._mask(nst, name, cb.drop_prob, masks)
-        nst.x = x + (h if m is None else h * m)
+        m = self._mask(qst, name, cb.drop_prob, masks)
+        qst.x = x + (h if m is None else h * m)
 
     def _rows_plan(self, grid, offset_host, keep, rep, offset_u):
         """The plan of a Mix3D batch in `train_mix3d = "rows"`: today's plan of the V unique voxels (kernel maps, pooled
@@ -1079,7 +1127,12 @@ class TrainGraph:
             cst = enc_stage(cst, "c", 2, c_cum, p_c2, t_scene)
             nst = enc_stage(nst, "n", 3, n_cum, p_n3, None)
             nst = enc_stage(nst, "n", 4, n_cum, p_n4, None)
-            self._cross_block(nst, cst, bb._tm_dec0.cross_block2, masks)
+            # fusion (ptv3.py:1332-1337).  Bidirectional: cross_block1(c <- n) first - the n point leaves it holding
+            # kv_norm1(n + kv_cpe(n)), which is what cross_block2 then takes as its q point, and the c point cross_block2 and the
+            # c-decoder read is cross_block1's output
+            if bb._tm_dec0.tm_bidirectional:
+                self._cross_block(cst, nst, bb._tm_dec0.cross_block1, "backbone._tm_dec0.cross_block1", masks)
+            self._cross_block(nst, cst, bb._tm_dec0.cross_block2, "backbone._tm_dec0.cross_block2", masks)
             for s in reversed(range(bb.c_num_stages - 1)):
                 cst = dec_stage(cst, "c", s, t_scene)
             c_phys = F.linear(cst.x, bb._c_head.weight, bb._c_head.bias) if isinstance(bb._c_head, torch.nn.Linear) else cst.x

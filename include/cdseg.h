@@ -846,6 +846,33 @@ int cdseg_segment_max_arg(const float* y, int ldy, const int32_t* seg_start, lon
 int cdseg_segment_max_bwd(const float* dout, int lddo, const int32_t* arg, int lda, const int32_t* cluster, long n, int c,
                           float* dy, int lddy, void* stream);
 
+/* ------------------------------------------------------------------ gate of the Feature Fusion Module (csrc/fusion.hip)
+ * ref: CrossBlock, ptv3.py:1196-1206: q_point.feat = q_shortcut + feat_scale * attn, or (1 - feat_scale) * q_shortcut +
+ * feat_scale * attn, with attn behind DropPath.  Contiguous fp32 (rows, c) tensors; s = q_shortcut, a = the projected
+ * attention output, m (rows) = the per-row DropPath factor mask / keep (NULL = 1), alpha and gamma (c) = the per-channel
+ * factors the caller derives from the mode (a scalar mode passes a broadcast vector; alpha = 1 or 1 - gamma):
+ *   forward   y[r][j] = alpha[j] s[r][j] + gamma[j] m[r] a[r][j]       (a NULL, then m NULL too: y = alpha s).  y may be s.
+ *   backward  ds = alpha dy,  da = gamma m dy  (ds may be dy), and sums (2 c doubles) = [sum_r dy m a (c), sum_r dy s (c)]:
+ *             the gradient of every mode's feat_scale is a host expression of the two (d gamma = sums[j], d alpha = sums[c + j]).
+ * Every element-wise expression is evaluated in fp64 from the fp32 operands and rounded to fp32 once; the column sums are
+ * accumulated and returned in fp64.  Two paths, chosen per call: with c a multiple of 4 and every tensor and per-channel vector
+ * 16-byte aligned every lane moves 16 bytes; any other width or alignment takes a scalar path with the same arithmetic.
+ * Summation order: block b owns rows_per_block consecutive rows (64 at least, 256 blocks at most: a function of rows alone);
+ * on the 16-byte path a lane adds its rows by ascending index and the block's row slots are added by ascending slot, as in the
+ * BatchNorm sums above, on the scalar path one thread adds a column's rows of the block by ascending index; the block partials
+ * (in ws, cdseg_fuse_gate_ws_bytes) are added by a second launch by ascending block index.  No float atomics: equal inputs on
+ * the same path give equal bits.  Nothing outside y / ds, da, sums and ws_bytes of ws is written.
+ * Status codes, checked before any launch; rows = 0 returns CDSEG_OK without one:
+ *   CDSEG_ERR_UNSUPPORTED  c outside [1, 512].
+ *   CDSEG_ERR_ARG          a NULL operand other than m (and a in the forward); m without a; a tensor or vector that is not
+ *                          4-byte aligned; sums not 8-byte, ws not 16-byte aligned; rows < 0.
+ *   CDSEG_ERR_WORKSPACE    ws NULL or ws_bytes below the query. */
+size_t cdseg_fuse_gate_ws_bytes(long rows, int c);
+int cdseg_fuse_gate_fwd(const float* s, const float* a, const float* m, const float* alpha, const float* gamma, float* y,
+                        long rows, int c, void* stream);
+int cdseg_fuse_gate_bwd(const float* dy, const float* s, const float* a, const float* m, const float* alpha, const float* gamma,
+                        float* ds, float* da, double* sums, long rows, int c, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ fused optimizer step (csrc/optim.hip)
  * ref: engines/train.py:216-271 (run_step: scaler.unscale_, clip_grad_norm_, scaler.step(optimizer)) on torch.optim.AdamW.
  * One tensor table describes the parameters; a work list cuts them into chunks of at most CDSEG_OPT_CHUNK elements (a
