@@ -294,6 +294,11 @@ SIGNATURES = {
                                 c_void_p]),
     "cdseg_adamw_step": (c_int, [POINTER(OptTensor), c_int, POINTER(OptGroup), c_int, c_void_p, c_long, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_size_t, c_void_p]),
+    "cdseg_route_enable": (c_int, [c_int]),
+    "cdseg_route_clear": (None, []),
+    "cdseg_route_read": (c_int, [POINTER(c_int32), c_int]),
+    "cdseg_route_catalog": (c_int, [ctypes.c_char_p, c_size_t]),
+    "cdseg_route_note": (c_int, [POINTER(c_int32)]),
     "cdseg_prof_enable": (c_int, [c_int]),
     "cdseg_prof_summary": (c_int, [POINTER(ctypes.c_double), POINTER(c_long)]),
     "cdseg_prof_summary_class": (c_int, [c_int, POINTER(ctypes.c_double), POINTER(c_long)]),

@@ -45,6 +45,7 @@
 
 #include "common.h"
 #include "prof.h"
+#include "route.h"
 
 namespace {
 
@@ -1071,6 +1072,9 @@ extern "C" int cdseg_attention_ex(const void* q, const void* k, const void* v, i
   if (!attr_ok) return CDSEG_ERR_LAUNCH;
   CdsegProfToken tok;
   const bool prof = cdseg_prof_begin(CDSEG_PROF_ATTENTION, s, &tok);
+  cdseg_route_rec(dtype == CDSEG_BF16 ? (wide16 ? CDSEG_RK_ATTN_B16_WIDE : CDSEG_RK_ATTN_B16) : (dtype == CDSEG_F32X3 ? CDSEG_RK_ATTN_X3 : CDSEG_RK_ATTN_F32),
+                  0, 0, 1, 0, 0, dtype << CDSEG_ROUTE_F_CT_SHIFT,
+                  dtype == CDSEG_BF16 ? (wide16 ? BF_WAVES_WIDE : BF_WAVES) : (dtype == CDSEG_F32X3 ? X3_THREADS / 64 : ATTN_THREADS / 64));
   if (dtype == CDSEG_BF16) {
     if (wide16) hipLaunchKernelGGL(attn_bf16_kernel<BF_WAVES_WIDE>, grid, block, SMEM_BF16, s, p);
     else hipLaunchKernelGGL(attn_bf16_kernel<BF_WAVES>, grid, block, SMEM_BF16, s, p);

@@ -24,6 +24,7 @@
 
 #include "common.h"
 #include "deep.h"
+#include "route.h"
 
 namespace {
 
@@ -394,9 +395,11 @@ extern "C" int cdseg_cpe_head_rr(const void* y, int ldy, const void* head_img, c
   hipStream_t s = (hipStream_t)stream;
   if (channels == 32) {
     constexpr int lds = RRCfg<32>::HEAD_W + RRCfg<32>::HEAD_P;
+    cdseg_route_rec(CDSEG_RK_HEAD_RR_32, 0, 0, 1, 0, 0, 0, 0);
     hipLaunchKernelGGL(head_rr_kernel<32>, dim3(rr_grid(n, lds)), dim3(RR_WAVES * 64), lds, s, p);
   } else {
     constexpr int lds = RRCfg<64>::HEAD_W + RRCfg<64>::HEAD_P;
+    cdseg_route_rec(CDSEG_RK_HEAD_RR_64, 0, 0, 1, 0, 0, 0, 0);
     hipLaunchKernelGGL(head_rr_kernel<64>, dim3(rr_grid(n, lds)), dim3(RR_WAVES * 64), lds, s, p);
   }
   CDSEG_CHECK_LAUNCH();
@@ -420,6 +423,7 @@ extern "C" int cdseg_attn_tail_rr(const void* o, int ldo, const void* tail_img, 
   hipStream_t s = (hipStream_t)stream;
   if (channels == 32) {
     constexpr int lds = RRCfg<32>::TAIL_W + RRCfg<32>::TAIL_P;
+    cdseg_route_rec(CDSEG_RK_TAIL_RR_32, 0, 0, 1, 0, 0, 0, 0);
     hipLaunchKernelGGL(tail_rr_kernel<32>, dim3(rr_grid(n, lds)), dim3(RR_WAVES * 64), lds, s, p);
   } else {
     constexpr int lds = RRCfg<64>::TAIL_W + RRCfg<64>::TAIL_P;
@@ -429,6 +433,7 @@ extern "C" int cdseg_attn_tail_rr(const void* o, int ldo, const void* tail_img, 
         return CDSEG_ERR_LAUNCH;
       attr_done = true;
     }
+    cdseg_route_rec(CDSEG_RK_TAIL_RR_64, 0, 0, 1, 0, 0, 0, 0);
     hipLaunchKernelGGL(tail_rr_kernel<64>, dim3(rr_grid(n, lds)), dim3(RR_WAVES * 64), lds, s, p);
   }
   CDSEG_CHECK_LAUNCH();

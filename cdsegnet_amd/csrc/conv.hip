@@ -30,6 +30,7 @@
 
 #include "common.h"
 #include "prof.h"
+#include "route.h"
 
 namespace {
 
@@ -406,6 +407,8 @@ int launch_conv_ll(const ConvP& p0, int per_cu, const void* wimg, hipStream_t s)
   }
   CdsegProfToken tok;
   const bool prof = cdseg_prof_begin(CDSEG_PROF_CONV, s, &tok);
+  cdseg_route_rec(p.yf ? (C == 32 ? CDSEG_RK_CONV_LL_32_F32 : CDSEG_RK_CONV_LL_64_F32) : (C == 32 ? CDSEG_RK_CONV_LL_32 : CDSEG_RK_CONV_LL_64),
+                  WAVES * K::ROWS_PER_WAVE, 0, 1, 0, 0, CDSEG_ROUTE_F_GATHER, WAVES);
   hipLaunchKernelGGL((conv_ll_kernel<C, WAVES, NB, OCC>), dim3(grid), dim3(WAVES * 64), K::LDS_BYTES, s, p, (const uint4*)wimg);
   if (prof) cdseg_prof_end(tok, s);
   if (hipGetLastError() != hipSuccess) return CDSEG_ERR_LAUNCH;

@@ -27,6 +27,7 @@
 #include <atomic>
 
 #include "deep.h"
+#include "route.h"
 
 namespace {
 
@@ -708,6 +709,11 @@ int launch_head(const DeepHeadP& p, hipStream_t s) {
       return CDSEG_ERR_LAUNCH;
     attr_done = true;
   }
+  constexpr int rid = C == 128 ? (BM == 128 ? CDSEG_RK_DEEP_HEAD_128_128 : CDSEG_RK_DEEP_HEAD_128_32)
+                    : C == 256 ? (BM == 128 ? CDSEG_RK_DEEP_HEAD_256_128 : CDSEG_RK_DEEP_HEAD_256_32)
+                               : (BM == 64 ? CDSEG_RK_DEEP_HEAD_512_64 : CDSEG_RK_DEEP_HEAD_512_32);
+  static_assert(C == 512 ? ((BM == 64 && NS == 2) || (BM == 32 && NS == 1)) : ((BM == 128 || BM == 32) && NS == 1), "csrc/route.h names this kernel");
+  cdseg_route_rec(rid, BM, 0, 1, 0, 0, 0, p.nsplit | (p.ysplits > 1 ? p.ysplits << 8 : 0));
   hipLaunchKernelGGL((deep_head_kernel<C, BM, NS>), dim3((unsigned)((p.n + BM - 1) / BM) * (unsigned)p.nsplit), dim3(2 * C / NS), lds, s, p);
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
@@ -722,6 +728,11 @@ int launch_tail(const DeepTailP& p, hipStream_t s) {
       return CDSEG_ERR_LAUNCH;
     attr_done = true;
   }
+  constexpr int rid = C == 128 ? (BM == 128 ? CDSEG_RK_DEEP_TAIL_128_128 : CDSEG_RK_DEEP_TAIL_128_32)
+                    : C == 256 ? (BM == 128 ? CDSEG_RK_DEEP_TAIL_256_128 : CDSEG_RK_DEEP_TAIL_256_32)
+                               : (BM == 64 ? CDSEG_RK_DEEP_TAIL_512_64 : CDSEG_RK_DEEP_TAIL_512_32);
+  static_assert(C == 512 ? ((BM == 64 && NS == 2) || (BM == 32 && NS == 1)) : ((BM == 128 || BM == 32) && NS == 1), "csrc/route.h names this kernel");
+  cdseg_route_rec(rid, BM, 0, 1, 0, 0, 0, p.nsplit);
   hipLaunchKernelGGL((deep_tail_kernel<C, BM, NS>), dim3((unsigned)((p.n + BM - 1) / BM) * (unsigned)p.nsplit), dim3(2 * C / NS), lds, s, p);
   CDSEG_CHECK_LAUNCH();
   if (p.nsplit > 1) {

@@ -31,6 +31,7 @@
 
 #include "common.h"
 #include "prof.h"
+#include "route.h"
 
 // row-count window in which a C = 128 sparse conv takes the 8-wave 256 x 128 tile (MIN 0 = never).  Measured
 // (tools/bench_conv.py 2 <scenes>, profiles/r05_conv128.txt): 14 k rows (one scene) 42.2 -> 37.2 us, but 114 k rows (8 scenes)
@@ -1349,6 +1350,18 @@ int launch_bn(GemmP p, size_t ws_bytes, hipStream_t s) {
   else nblk = (unsigned)gm * (unsigned)slices;
   const dim3 grid(nblk);
   bool launched = false;
+  // launch record (csrc/route.h): the fields every arm below shares; each arm adds its kernel id and tile
+  constexpr int RCT = kIsX3<CT> ? CDSEG_RT_x3 : (sizeof(CT) == 2 ? CDSEG_RT_b16 : CDSEG_RT_f32);
+  constexpr bool RKL = NCH == 16;
+  auto route = [&](int id, int tbm, int tbn) {
+    if (!tl_cdseg_route_on) return;
+    const int ctype = kIsX3<CT> ? CDSEG_F32X3 : (sizeof(CT) == 2 ? CDSEG_BF16 : CDSEG_F32);
+    cdseg_route_push(id, tbm, tbn, p.splits, p.fix, p.xmode,
+                     (p.vec_ok ? CDSEG_ROUTE_F_VEC_OK : 0) | (GATHER ? CDSEG_ROUTE_F_GATHER : 0) |
+                         (p.kshift < 0 ? CDSEG_ROUTE_F_KDIV : (p.kshift < 6 ? CDSEG_ROUTE_F_KSHIFT_LT6 : 0)) |
+                         (ctype << CDSEG_ROUTE_F_CT_SHIFT),
+                     0);
+  };
   // bf16, K a multiple of 64, wide outputs: the LDS-DMA pipelined main loop
   if constexpr (NCH == 16 && sizeof(CT) == 2) {
     static const int dma_on = cdseg_knob("CDSEG_GEMM_DMA", 1);
@@ -1365,6 +1378,7 @@ int launch_bn(GemmP p, size_t ws_bytes, hipStream_t s) {
             return CDSEG_ERR_LAUNCH;
           aq128 = true;
         }
+        route(cdseg_route_dma_id<256, true, 128, 2, true>(), 256, 128);
         hipLaunchKernelGGL((gemm_dma_kernel<256, true, 128, 2, true>), grid, dim3(Q::NT), Q::LDS, s, p);
       }
       if (!launched && sq && dma_on) {
@@ -1377,6 +1391,7 @@ int launch_bn(GemmP p, size_t ws_bytes, hipStream_t s) {
             return CDSEG_ERR_LAUNCH;
           aq = true;
         }
+        route(cdseg_route_dma_id<256, true, 256, 2, true>(), 256, 256);
         hipLaunchKernelGGL((gemm_dma_kernel<256, true, 256, 2, true>), grid, dim3(Q::NT), Q::LDS, s, p);
       }
       if (!launched && wide && dma_on && p.kshift >= 6) {
@@ -1389,6 +1404,7 @@ int launch_bn(GemmP p, size_t ws_bytes, hipStream_t s) {
             return CDSEG_ERR_LAUNCH;
           aw = true;
         }
+        route(cdseg_route_dma_id<128, true, 256, 3>(), 128, 256);
         hipLaunchKernelGGL((gemm_dma_kernel<128, true, 256, 3>), grid, dim3(512), W::LDS, s, p);
       }
     }
@@ -1405,6 +1421,7 @@ int launch_bn(GemmP p, size_t ws_bytes, hipStream_t s) {
           a256 = true;
         }
         constexpr int lds256 = DmaCfg<256, GATHER>::LDS;
+        route(cdseg_route_dma_id<256, GATHER>(), 256, 128);
         hipLaunchKernelGGL((gemm_dma_kernel<256, GATHER>), grid, dim3(1024), lds256, s, p);
       } else if (bm == 128) {
         static std::atomic<bool> a128{false};  // (a concurrent first call sets the attribute twice: harmless)
@@ -1415,6 +1432,7 @@ int launch_bn(GemmP p, size_t ws_bytes, hipStream_t s) {
           a128 = true;
         }
         constexpr int lds128 = DmaCfg<128, GATHER>::LDS;
+        route(cdseg_route_dma_id<128, GATHER>(), 128, 128);
         hipLaunchKernelGGL((gemm_dma_kernel<128, GATHER>), grid, dim3(512), lds128, s, p);
       } else {
         static std::atomic<bool> a64{false};  // (a concurrent first call sets the attribute twice: harmless)
@@ -1425,6 +1443,7 @@ int launch_bn(GemmP p, size_t ws_bytes, hipStream_t s) {
           a64 = true;
         }
         constexpr int lds64 = DmaCfg<64, GATHER>::LDS;
+        route(cdseg_route_dma_id<64, GATHER>(), 64, 128);
         hipLaunchKernelGGL((gemm_dma_kernel<64, GATHER>), grid, dim3(256), lds64, s, p);
       }
     }
@@ -1440,6 +1459,7 @@ int launch_bn(GemmP p, size_t ws_bytes, hipStream_t s) {
           return CDSEG_ERR_LAUNCH;
         attr_done256 = true;
       }
+      route(cdseg_route_gemm_id<RCT, 128, RKL, GATHER, 256>(), 256, 128);
       hipLaunchKernelGGL((gemm_kernel<CT, 128, 16, GATHER, 256>), grid, dim3(1024), smem, s, p);
     }
   }
@@ -1447,8 +1467,10 @@ int launch_bn(GemmP p, size_t ws_bytes, hipStream_t s) {
     if (tall && !launched) {
       launched = true;
       if (bn == 32) {
+        route(cdseg_route_gemm_id<RCT, 32, RKL, GATHER, 128>(), 128, 32);
         hipLaunchKernelGGL((gemm_kernel<CT, 32, 16, GATHER, 128>), grid, dim3(512), 0, s, p);
       } else if (bn == 64) {
+        route(cdseg_route_gemm_id<RCT, 64, RKL, GATHER, 128>(), 128, 64);
         hipLaunchKernelGGL((gemm_kernel<CT, 64, 16, GATHER, 128>), grid, dim3(512), 0, s, p);
       } else {
         constexpr int smem = gemm_smem_bytes<CT, 128, 16, 128>();  // 65 KB: above the static LDS limit
@@ -1459,6 +1481,7 @@ int launch_bn(GemmP p, size_t ws_bytes, hipStream_t s) {
             return CDSEG_ERR_LAUNCH;
           attr_done = true;
         }
+        route(cdseg_route_gemm_id<RCT, 128, RKL, GATHER, 128>(), 128, 128);
         hipLaunchKernelGGL((gemm_kernel<CT, 128, 16, GATHER, 128>), grid, dim3(512), smem, s, p);
       }
     }
@@ -1467,8 +1490,10 @@ int launch_bn(GemmP p, size_t ws_bytes, hipStream_t s) {
     if (tall_x3 && !launched) {
       launched = true;
       if (bn == 32) {
+        route(cdseg_route_gemm_id<RCT, 32, RKL, false, 128>(), 128, 32);
         hipLaunchKernelGGL((gemm_kernel<CT, 32, NCH, false, 128>), grid, dim3(512), 0, s, p);
       } else if (bn == 64) {
+        route(cdseg_route_gemm_id<RCT, 64, RKL, false, 128>(), 128, 64);
         hipLaunchKernelGGL((gemm_kernel<CT, 64, NCH, false, 128>), grid, dim3(512), 0, s, p);
       } else {
         constexpr int smem = gemm_smem_bytes<CT, 128, NCH, 128>();
@@ -1480,17 +1505,26 @@ int launch_bn(GemmP p, size_t ws_bytes, hipStream_t s) {
               return CDSEG_ERR_LAUNCH;
             attr_x3 = true;
           }
+          route(cdseg_route_gemm_id<RCT, 128, RKL, false, 128>(), 128, 128);
           hipLaunchKernelGGL((gemm_kernel<CT, 128, NCH, false, 128>), grid, dim3(512), smem, s, p);
         } else {
+          route(cdseg_route_gemm_id<RCT, 128, RKL, false, 128>(), 128, 128);
           hipLaunchKernelGGL((gemm_kernel<CT, 128, NCH, false, 128>), grid, dim3(512), 0, s, p);
         }
       }
     }
   }
   if (!launched) {
-    if (bn == 32) hipLaunchKernelGGL((gemm_kernel<CT, 32, NCH, GATHER>), grid, dim3(256), 0, s, p);
-    else if (bn == 64) hipLaunchKernelGGL((gemm_kernel<CT, 64, NCH, GATHER>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((gemm_kernel<CT, 128, NCH, GATHER>), grid, dim3(256), 0, s, p);
+    if (bn == 32) {
+      route(cdseg_route_gemm_id<RCT, 32, RKL, GATHER, 64>(), 64, 32);
+      hipLaunchKernelGGL((gemm_kernel<CT, 32, NCH, GATHER>), grid, dim3(256), 0, s, p);
+    } else if (bn == 64) {
+      route(cdseg_route_gemm_id<RCT, 64, RKL, GATHER, 64>(), 64, 64);
+      hipLaunchKernelGGL((gemm_kernel<CT, 64, NCH, GATHER>), grid, dim3(256), 0, s, p);
+    } else {
+      route(cdseg_route_gemm_id<RCT, 128, RKL, GATHER, 64>(), 64, 128);
+      hipLaunchKernelGGL((gemm_kernel<CT, 128, NCH, GATHER>), grid, dim3(256), 0, s, p);
+    }
   }
   if (hipGetLastError() != hipSuccess) return CDSEG_ERR_LAUNCH;
   if (p.fix == 2) {
@@ -1501,6 +1535,7 @@ int launch_bn(GemmP p, size_t ws_bytes, hipStream_t s) {
     if (tl_leave_partials && p.vec_ok && p.bias && !p.scale && p.act == CDSEG_ACT_NONE && !p.res && !p.add_src && !p.out2 &&
         !p.out_idx && !p.colbias) {
       tl_partial_splits = p.splits;
+      cdseg_route_or_flags(CDSEG_ROUTE_F_PARTIALS);
       return CDSEG_OK;
     }
     const long groups = p.M * (long)(p.N >> 2);

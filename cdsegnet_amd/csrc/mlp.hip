@@ -11,6 +11,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "route.h"
 
 namespace {
 
@@ -281,6 +282,10 @@ int launch_mlp(const MlpP& p, hipStream_t s) {
     attr_done = true;
   }
   const dim3 grid((unsigned)((p.n + BM - 1) / BM));
+  constexpr int rid = PROJ ? (C == 32 ? CDSEG_RK_TAIL_32_64 : CDSEG_RK_TAIL_64_64)
+                           : (C == 32 ? CDSEG_RK_MLP_32_64 : (C == 64 ? CDSEG_RK_MLP_64_64 : (BM == 128 ? CDSEG_RK_MLP_128_128 : CDSEG_RK_MLP_128_64)));
+  static_assert((PROJ ? C <= 64 : C <= 128) && HT == 64 && (BM == 64 || (BM == 128 && C == 128 && !PROJ)), "csrc/route.h names this kernel");
+  cdseg_route_rec(rid, BM, 0, 1, 0, 0, 0, BM);
   hipLaunchKernelGGL((mlp_fused_kernel<C, HT, PROJ, BM>), grid, dim3(4 * BM), LDS, s, p);
   return hipGetLastError() == hipSuccess ? CDSEG_OK : CDSEG_ERR_LAUNCH;
 }
@@ -848,6 +853,7 @@ int launch_head_stream(const HeadP& p, hipStream_t s) {
   static const int per_cu = cdseg_knob("CDSEG_HEAD_STREAM_WGS", 2);
   const long tiles = (p.n + 127) / 128, cap = 256L * (per_cu < 1 ? 1 : per_cu);
   const dim3 grid((unsigned)(tiles < cap ? tiles : cap));
+  cdseg_route_rec(C == 32 ? CDSEG_RK_HEAD_STREAM_32 : CDSEG_RK_HEAD_STREAM_64, 128, 0, 1, 0, 0, 0, 128);
   hipLaunchKernelGGL((cpe_head_stream_kernel<C>), grid, dim3(512), LDS, s, p);
   return hipGetLastError() == hipSuccess ? CDSEG_OK : CDSEG_ERR_LAUNCH;
 }
@@ -880,10 +886,12 @@ extern "C" int cdseg_cpe_head_fused(const void* y, int ldy, const void* wl, cons
     return channels == 32 ? launch_head_stream<32>(p, (hipStream_t)stream) : launch_head_stream<64>(p, (hipStream_t)stream);
   if (bm == 128 && n >= 128 * 512) {  // enough 128-row workgroups to fill the chip twice
     const dim3 grid((unsigned)((n + 127) / 128));
+    cdseg_route_rec(channels == 32 ? CDSEG_RK_HEAD_32_128 : CDSEG_RK_HEAD_64_128, 128, 0, 1, 0, 0, 0, 128);
     if (channels == 32) hipLaunchKernelGGL((cpe_head_fused_kernel<32, 128>), grid, dim3(512), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL((cpe_head_fused_kernel<64, 128>), grid, dim3(512), 0, (hipStream_t)stream, p);
   } else {
     const dim3 grid((unsigned)((n + 63) / 64));
+    cdseg_route_rec(channels == 32 ? CDSEG_RK_HEAD_32_64 : CDSEG_RK_HEAD_64_64, 64, 0, 1, 0, 0, 0, 64);
     if (channels == 32) hipLaunchKernelGGL((cpe_head_fused_kernel<32, 64>), grid, dim3(256), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL((cpe_head_fused_kernel<64, 64>), grid, dim3(256), 0, (hipStream_t)stream, p);
   }

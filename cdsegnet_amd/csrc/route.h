@@ -1,0 +1,152 @@
+// Launch record of the C ABI (include/cdseg.h: cdseg_route_enable / _clear / _read / _catalog): which kernel each host-side
+// chooser picked, per host thread.  Host code only.  Off by default: a recording site then costs one thread-local test.
+//
+// ONE table names every kernel a chooser can launch; a kernel id is an index into it.  The recording sites take their ids
+// from this table (the GEMM arms by a compile-time search on their template arguments, the others by enumerator), and
+// cdseg_route_catalog prints it: the catalogue cannot list a kernel the code does not name, nor the reverse.
+#pragma once
+#include <stdint.h>
+
+#include "../../include/cdseg.h"
+
+// record: 8 int32 (layout and flag bits: include/cdseg.h)
+#define CDSEG_ROUTE_ID 0
+#define CDSEG_ROUTE_BM 1
+#define CDSEG_ROUTE_BN 2
+#define CDSEG_ROUTE_SPLITS 3
+#define CDSEG_ROUTE_FIX 4
+#define CDSEG_ROUTE_XMODE 5
+#define CDSEG_ROUTE_FLAGS 6
+#define CDSEG_ROUTE_AUX 7
+
+// gemm_kernel<CT, BN, NCH, GATHER, BM> instantiations of launch_bn: ct (b16 = the build's 16-bit type), column tile, K step class
+// (kshort: the whole reduction is at most 64 long), plain / gather, row tile
+#define CDSEG_RG_BN(X, ct, k, g, bm) X(ct, 32, k, g, bm) X(ct, 64, k, g, bm) X(ct, 128, k, g, bm)
+#define CDSEG_RG_CT(X, ct)                                                                                    \
+  CDSEG_RG_BN(X, ct, kshort, plain, 64) CDSEG_RG_BN(X, ct, kshort, gather, 64) CDSEG_RG_BN(X, ct, klong, plain, 64) \
+  CDSEG_RG_BN(X, ct, klong, gather, 64) CDSEG_RG_BN(X, ct, klong, gather, 128)
+#define CDSEG_ROUTE_GEMM_KERNELS(X)                                                          \
+  CDSEG_RG_CT(X, b16) CDSEG_RG_CT(X, f32) CDSEG_RG_CT(X, x3)                                 \
+  CDSEG_RG_BN(X, x3, kshort, plain, 128) CDSEG_RG_BN(X, x3, klong, plain, 128) X(b16, 128, klong, gather, 256)
+// gemm_dma_kernel<BM, GATHER, BN, stages, SQ> instantiations: row tile, plain / gather, column tile, ring stages, the 8-wave
+// square loop or not
+#define CDSEG_ROUTE_DMA_KERNELS(Y)                                                                              \
+  Y(64, plain, 128, 2, ring) Y(128, plain, 128, 2, ring) Y(256, plain, 128, 2, ring) Y(64, gather, 128, 2, ring) \
+  Y(128, gather, 128, 2, ring) Y(256, gather, 128, 2, ring) Y(128, gather, 256, 3, ring) Y(256, gather, 256, 2, sq) \
+  Y(256, gather, 128, 2, sq)
+// every other chooser: enumerator, name
+#define CDSEG_ROUTE_OTHER_KERNELS(Z)                                  \
+  Z(MLP_32_64, "mlp_fused_kernel<32,64,mlp,64>")                      \
+  Z(MLP_64_64, "mlp_fused_kernel<64,64,mlp,64>")                      \
+  Z(MLP_128_64, "mlp_fused_kernel<128,64,mlp,64>")                    \
+  Z(MLP_128_128, "mlp_fused_kernel<128,64,mlp,128>")                  \
+  Z(TAIL_32_64, "mlp_fused_kernel<32,64,proj,64>")                    \
+  Z(TAIL_64_64, "mlp_fused_kernel<64,64,proj,64>")                    \
+  Z(HEAD_STREAM_32, "cpe_head_stream_kernel<32>")                     \
+  Z(HEAD_STREAM_64, "cpe_head_stream_kernel<64>")                     \
+  Z(HEAD_32_128, "cpe_head_fused_kernel<32,128>")                     \
+  Z(HEAD_64_128, "cpe_head_fused_kernel<64,128>")                     \
+  Z(HEAD_32_64, "cpe_head_fused_kernel<32,64>")                       \
+  Z(HEAD_64_64, "cpe_head_fused_kernel<64,64>")                       \
+  Z(DEEP_HEAD_128_128, "deep_head_kernel<128,128,1>")                 \
+  Z(DEEP_HEAD_128_32, "deep_head_kernel<128,32,1>")                   \
+  Z(DEEP_HEAD_256_128, "deep_head_kernel<256,128,1>")                 \
+  Z(DEEP_HEAD_256_32, "deep_head_kernel<256,32,1>")                   \
+  Z(DEEP_HEAD_512_64, "deep_head_kernel<512,64,2>")                   \
+  Z(DEEP_HEAD_512_32, "deep_head_kernel<512,32,1>")                   \
+  Z(DEEP_TAIL_128_128, "deep_tail_kernel<128,128,1>")                 \
+  Z(DEEP_TAIL_128_32, "deep_tail_kernel<128,32,1>")                   \
+  Z(DEEP_TAIL_256_128, "deep_tail_kernel<256,128,1>")                 \
+  Z(DEEP_TAIL_256_32, "deep_tail_kernel<256,32,1>")                   \
+  Z(DEEP_TAIL_512_64, "deep_tail_kernel<512,64,2>")                   \
+  Z(DEEP_TAIL_512_32, "deep_tail_kernel<512,32,1>")                   \
+  Z(HEAD_RR_32, "head_rr_kernel<32>")                                 \
+  Z(HEAD_RR_64, "head_rr_kernel<64>")                                 \
+  Z(TAIL_RR_32, "tail_rr_kernel<32>")                                 \
+  Z(TAIL_RR_64, "tail_rr_kernel<64>")                                 \
+  Z(CONV_LL_32, "conv_ll_kernel<32>")                                 \
+  Z(CONV_LL_64, "conv_ll_kernel<64>")                                 \
+  Z(CONV_LL_32_F32, "conv_ll_kernel<32>:f32out")                      \
+  Z(CONV_LL_64_F32, "conv_ll_kernel<64>:f32out")                      \
+  Z(ATTN_B16, "attn_bf16_kernel<narrow>")                             \
+  Z(ATTN_B16_WIDE, "attn_bf16_kernel<16>")                            \
+  Z(ATTN_X3, "attn_x3_kernel")                                        \
+  Z(ATTN_F32, "attn_f32_kernel")
+
+enum {
+  CDSEG_RT_b16 = 0, CDSEG_RT_f32 = 1, CDSEG_RT_x3 = 2,
+  CDSEG_RT_kshort = 0, CDSEG_RT_klong = 1,
+  CDSEG_RT_plain = 0, CDSEG_RT_gather = 1,
+  CDSEG_RT_ring = 0, CDSEG_RT_sq = 1,
+};
+
+struct CdsegRouteEntry {
+  const char* name;
+  int key;  // GEMM arms: their template arguments, packed (0 for the kernels addressed by enumerator)
+};
+
+constexpr int cdseg_route_gemm_key(int ct, int bn, int klong, int gather, int bm) {
+  return (1 << 28) | (ct << 24) | (klong << 23) | (gather << 22) | ((bn / 32) << 12) | (bm / 32);
+}
+constexpr int cdseg_route_dma_key(int bm, int gather, int bn, int stages, int sq) {
+  return (2 << 28) | (stages << 24) | (sq << 23) | (gather << 22) | ((bn / 32) << 12) | (bm / 32);
+}
+
+inline constexpr CdsegRouteEntry kCdsegRouteTable[] = {
+#define CDSEG_RX(ct, bn, k, g, bm) \
+  {"gemm_kernel<" #ct "," #bn "," #k "," #g "," #bm ">", cdseg_route_gemm_key(CDSEG_RT_##ct, bn, CDSEG_RT_##k, CDSEG_RT_##g, bm)},
+    CDSEG_ROUTE_GEMM_KERNELS(CDSEG_RX)
+#undef CDSEG_RX
+#define CDSEG_RY(bm, g, bn, st, sq) \
+  {"gemm_dma_kernel<" #bm "," #g "," #bn "," #st "," #sq ">", cdseg_route_dma_key(bm, CDSEG_RT_##g, bn, st, CDSEG_RT_##sq)},
+    CDSEG_ROUTE_DMA_KERNELS(CDSEG_RY)
+#undef CDSEG_RY
+#define CDSEG_RZ(sym, name) {name, 0},
+    CDSEG_ROUTE_OTHER_KERNELS(CDSEG_RZ)
+#undef CDSEG_RZ
+};
+constexpr int kCdsegRouteCount = (int)(sizeof(kCdsegRouteTable) / sizeof(kCdsegRouteTable[0]));
+
+constexpr int cdseg_route_find(int key) {
+  for (int i = 0; i < kCdsegRouteCount; ++i)
+    if (kCdsegRouteTable[i].key == key) return i;
+  return -1;
+}
+
+// enumerators of the kernels addressed by name: CDSEG_RK_<sym> = their index in the table
+enum {
+#define CDSEG_RX(ct, bn, k, g, bm) CDSEG_RK_G_##ct##_##bn##_##k##_##g##_##bm,
+  CDSEG_ROUTE_GEMM_KERNELS(CDSEG_RX)
+#undef CDSEG_RX
+#define CDSEG_RY(bm, g, bn, st, sq) CDSEG_RK_D_##bm##_##g##_##bn##_##st##_##sq,
+  CDSEG_ROUTE_DMA_KERNELS(CDSEG_RY)
+#undef CDSEG_RY
+#define CDSEG_RZ(sym, name) CDSEG_RK_##sym,
+  CDSEG_ROUTE_OTHER_KERNELS(CDSEG_RZ)
+#undef CDSEG_RZ
+  CDSEG_RK_COUNT
+};
+static_assert(CDSEG_RK_COUNT == kCdsegRouteCount, "one table");
+
+// ids of the GEMM arms from their template arguments; a launch arm whose instantiation the table lacks does not compile
+template <int CT, int BN, bool KLONG, bool GATHER, int BM>
+constexpr int cdseg_route_gemm_id() {
+  constexpr int id = cdseg_route_find(cdseg_route_gemm_key(CT, BN, KLONG, GATHER, BM));
+  static_assert(id >= 0, "gemm_kernel instantiation missing from CDSEG_ROUTE_GEMM_KERNELS");
+  return id;
+}
+template <int BM, bool GATHER, int BN = 128, int STAGES = 2, bool SQ = false>
+constexpr int cdseg_route_dma_id() {
+  constexpr int id = cdseg_route_find(cdseg_route_dma_key(BM, GATHER, BN, STAGES, SQ));
+  static_assert(id >= 0, "gemm_dma_kernel instantiation missing from CDSEG_ROUTE_DMA_KERNELS");
+  return id;
+}
+
+extern thread_local bool tl_cdseg_route_on;
+void cdseg_route_push(int id, int bm, int bn, int splits, int fix, int xmode, int flags, int aux);
+void cdseg_route_or_flags(int flags);  // into the newest record of this thread
+
+// the recording site: immediately before the hipLaunchKernelGGL it describes
+static inline void cdseg_route_rec(int id, int bm, int bn, int splits, int fix, int xmode, int flags, int aux) {
+  if (tl_cdseg_route_on) cdseg_route_push(id, bm, bn, splits, fix, xmode, flags, aux);
+}

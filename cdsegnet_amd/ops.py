@@ -4,6 +4,7 @@ Each function mirrors one reference call site (cited in include/cdseg.h) and is 
 marshalling layer: PyTorch provides device memory and the stream, every computation runs in
 the hand-written HIP kernels of libcdseg_hip.so.  No fallbacks: tensors must live on a GPU.
 """
+import collections
 import ctypes
 import os
 import threading
@@ -106,6 +107,64 @@ def attention_prof_summary():
 
 
 PROF_ATTENTION, PROF_CONV, PROF_CONV_DEEP = 0, 1, 2  # include/cdseg.h
+
+
+# ------------------------------------------------------------------ launch record (include/cdseg.h: cdseg_route_*)
+ROUTE_WORDS = 8
+ROUTE_F_VEC_OK, ROUTE_F_GATHER, ROUTE_F_PARTIALS, ROUTE_F_KDIV, ROUTE_F_KSHIFT_LT6, ROUTE_F_CT_SHIFT = 1, 2, 4, 8, 16, 5
+
+
+class Route(collections.namedtuple("Route", "kernel bm bn splits fix xmode flags aux")):
+    """One recorded launch: `kernel` is the catalogue name; the flag bits as properties."""
+    __slots__ = ()
+    vec_ok = property(lambda r: bool(r.flags & ROUTE_F_VEC_OK))
+    gather = property(lambda r: bool(r.flags & ROUTE_F_GATHER))
+    partials = property(lambda r: bool(r.flags & ROUTE_F_PARTIALS))
+    kdiv = property(lambda r: bool(r.flags & ROUTE_F_KDIV))
+    kshift_lt6 = property(lambda r: bool(r.flags & ROUTE_F_KSHIFT_LT6))
+    compute = property(lambda r: (r.flags >> ROUTE_F_CT_SHIFT) & 3)
+
+
+def route_catalog(lib=None):
+    """Names of every kernel id compiled into the (calling thread's active) build, in id order."""
+    lib = lib or _lib.load()
+    need = lib.cdseg_route_catalog(None, 0)
+    buf = ctypes.create_string_buffer(need)
+    assert lib.cdseg_route_catalog(buf, need) == need
+    return buf.value.decode().split("\n")
+
+
+def route_read(lib=None, capacity=64):
+    """(launches recorded by this thread since the last clear, the newest `capacity` of them as Route tuples, oldest first)."""
+    lib = lib or _lib.load()
+    rec = (ctypes.c_int32 * (ROUTE_WORDS * max(capacity, 1)))(*([-1] * (ROUTE_WORDS * max(capacity, 1))))
+    count = lib.cdseg_route_read(rec, capacity)
+    names = route_catalog(lib)
+    # the library writes min(count, its ring, capacity) records and nothing behind them: a kernel id is never negative, so the
+    # rows written are the ones whose id no longer holds the -1 put there (no ring size is assumed on this side)
+    rows = [list(rec[ROUTE_WORDS * i:ROUTE_WORDS * (i + 1)]) for i in range(min(count, capacity))]
+    rows = [r for r in rows if r[0] >= 0]
+    return count, [Route(names[r[0]], *r[1:]) for r in rows]
+
+
+class record_routes:
+    """`with ops.record_routes() as rr: ...` - afterwards rr.count / rr.routes hold what the calling thread's launches in the
+    active build recorded inside the block (which kernel each host-side chooser picked).  Tests and diagnostics only."""
+
+    def __enter__(self):
+        self.lib = _lib.load()
+        self.prev = self.lib.cdseg_route_enable(1)
+        self.lib.cdseg_route_clear()
+        self.count, self.routes = 0, []
+        return self
+
+    def __exit__(self, *exc):
+        self.count, self.routes = route_read(self.lib)
+        self.lib.cdseg_route_enable(self.prev)
+        return False
+
+    def kernels(self):
+        return [r.kernel for r in self.routes]
 
 
 def prof_summary(cls):

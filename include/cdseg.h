@@ -254,6 +254,37 @@ int cdseg_attention_ex(const void* q, const void* k, const void* v, int ldq, int
  * of block ids (may exceed `capacity`; at most `capacity` rows are written), or a negative status. */
 long cdseg_attention_schedule(int num_patches, int num_heads, int max_len, int dtype, int32_t* table, long capacity);
 
+/* Launch record, host only: which kernel each host-side chooser of this library picked (csrc/route.h).  Almost every launch
+ * is routed among template instantiations by row / column / reduction thresholds; with recording on, each chooser notes its
+ * choice immediately before the launch it describes, per calling host thread, in a ring of the newest 64 launches (one
+ * cdseg_block_forward leaves at most ten).  Off by default: a launch then pays one thread-local test.  Records of a call that
+ * returns an error describe the launches attempted up to the error.
+ *   record = 8 int32: [0] kernel id = line number in the catalogue; [1] row tile; [2] column tile (0: none); [3] split-K
+ *   slices; [4] fix (0; 1 = split-K second pass; 2 = row finish of the fused LayerNorm); [5] xmode (cdseg_gemm's block id ->
+ *   tile mapping, 0 / 1 / 2); [6] flags; [7] aux: the deep-stage head / tail: workgroups per row tile (the head, when it
+ *   reads the conv's split-K partial planes: | their count << 8); attention: waves per block; fused MLP / tail / head: rows
+ *   per workgroup; sparse conv: waves per block.
+ * cdseg_route_enable: returns the previous state.  cdseg_route_clear: forget this thread's records.  cdseg_route_read: the
+ * number of launches recorded since the last clear (may exceed both the ring and `capacity`); writes the newest
+ * min(count, 64, capacity) records, oldest first (rec may be NULL with capacity 0).  cdseg_route_catalog: the names of every
+ * kernel id compiled into this library, in id order, separated by '\n' and terminated by '\0' - the table the recording
+ * sites take their ids from; returns the bytes needed (nothing is written if `bytes` is smaller).
+ * TEST HOOK, not part of the product interface: cdseg_route_note appends one record as a chooser would (a no-op while
+ * recording is off; CDSEG_ERR_ARG for an id outside the catalogue).  It exists so that the ring can be exercised on a machine
+ * without a GPU (tests/test_cpu_routes.py); a record it appends describes no launch. */
+#define CDSEG_ROUTE_WORDS 8
+#define CDSEG_ROUTE_F_VEC_OK 1     /* every epilogue access of cdseg_gemm is a 16-byte group */
+#define CDSEG_ROUTE_F_GATHER 2     /* rows gathered through a kernel map */
+#define CDSEG_ROUTE_F_PARTIALS 4   /* split-K partial planes left in the workspace for the consuming kernel */
+#define CDSEG_ROUTE_F_KDIV 8       /* K is no power of two: the gather locates a column by division */
+#define CDSEG_ROUTE_F_KSHIFT_LT6 16 /* K is a power of two below 64 */
+#define CDSEG_ROUTE_F_CT_SHIFT 5   /* bits 5-6: compute type (CDSEG_F32 / CDSEG_BF16 / CDSEG_F32X3) */
+int cdseg_route_enable(int on);
+void cdseg_route_clear(void);
+int cdseg_route_read(int32_t* rec_host, int capacity);
+int cdseg_route_catalog(char* buf_host, size_t bytes);
+int cdseg_route_note(const int32_t* rec_host);
+
 /* HIP-event timing of the attention launches on their own stream (bench.py's live roofline measurement):
  * enable(1) starts recording, summary() (after a device sync) returns the summed durations. */
 int cdseg_prof_enable(int on);

@@ -202,8 +202,10 @@ def _run16(launch, q_dev, k_dev, v_dev, H, flags, store8=False, scale=SCALE):
         out = wide[:, :C]
     else:
         out = torch.full((n, C), float("nan"), dtype=q_dev.dtype, device="cuda")
-    O.attention(q_dev, k_dev, v_dev, gq, gkv, widx, ps, H, launch.max_len, scale, out, flags=flags)
+    with O.record_routes() as rr:  # which kernel cdseg_attention_ex picked (include/cdseg.h cdseg_route_*)
+        O.attention(q_dev, k_dev, v_dev, gq, gkv, widx, ps, H, launch.max_len, scale, out, flags=flags)
     torch.cuda.synchronize()
+    out.routes = rr.routes  # the launch record of this call rides on the tensor it produced
     return out
 
 
@@ -265,7 +267,11 @@ def test_attention_16bit_redo_rows_vs_fp64(ops, lp, name, lens, H, flags, cross,
     qp, k, v = _base_rows(n, H, rng)
     rows = _assign_shifts(launch, qp, k, H, lpt)
     q_dev, k_dev, v_dev, q_eff, k_eff, v_eff = _operands(qp, k, v, lpt, flags)
-    out = _run16(launch, q_dev, k_dev, v_dev, H, flags, store8=store8).float().cpu().numpy().astype(np.float64)
+    out_dev = _run16(launch, q_dev, k_dev, v_dev, H, flags, store8=store8)
+    # ... and the kernel the library recorded next to the predicate re-derived from its schedule table
+    assert [(r.kernel, r.aux) for r in out_dev.routes] == [("attn_bf16_kernel<16>", 16) if wide16 else ("attn_bf16_kernel<narrow>", 8)], \
+        (name, wide16, out_dev.routes)
+    out = out_dev.float().cpu().numpy().astype(np.float64)
     ids = _sample(launch) if len(patches) > 8 else None
     ref, l2d = _oracle(q_eff, k_eff, v_eff, launch, H, ids)
     checked = np.nonzero(np.isfinite(ref[:, 0]))[0]

@@ -54,10 +54,12 @@ def _case(ops, lp, n, C, tb):
     xb, qb = d["x0"].clone(), {f: torch.empty(n, 3 * C, dtype=bf, device="cuda") for f in flagsets}
     for f in flagsets:
         xb.copy_(d["x0"])
-        for a in range(0, n, CHUNK):
-            b = min(a + CHUNK, n)
-            ops.cpe_head_fused(d["y"][a:b], d["wl"], d["bl"], d["lnp"], xb[a:b], d["cb"], d["ln1"], d["wq"], d["bq"], qb[f][a:b],
-                               qkv_flags=f)
+        with ops.record_routes() as rr:
+            for a in range(0, n, CHUNK):
+                b = min(a + CHUNK, n)
+                ops.cpe_head_fused(d["y"][a:b], d["wl"], d["bl"], d["lnp"], xb[a:b], d["cb"], d["ln1"], d["wq"], d["bq"], qb[f][a:b],
+                                   qkv_flags=f)
+        assert rr.count == -(-n // CHUNK) and set(rr.kernels()) == {f"cpe_head_fused_kernel<{C},64>"}, rr.routes
     torch.cuda.synchronize()
     d.update(xa=xa, qa=qa, xb=xb, qb=qb, flagsets=flagsets)
     return d
@@ -87,7 +89,11 @@ def test_stream_head_equals_gemm_sequence_and_64_row_kernel_bit_for_bit(ops, lp,
     bf = LP()
     for flags in d["flagsets"]:
         x, qkv = d["x0"].clone(), torch.full((n, 3 * C), float("nan"), dtype=bf, device="cuda")
-        _run(ops, d, x, qkv, flags=flags)
+        with ops.record_routes() as rr:
+            _run(ops, d, x, qkv, flags=flags)
+        # the launch record: the persistent kernel from 65 536 rows, the 64-row kernel one row below
+        want = (f"cpe_head_stream_kernel<{C}>", 128) if n >= 65536 else (f"cpe_head_fused_kernel<{C},64>", 64)
+        assert [(r.kernel, r.aux) for r in rr.routes] == [want], (n, C, rr.routes)
         _check(d, C, x, qkv, flags, f"flags={flags}")
         # the same call again: equal bits
         x2, qkv2 = d["x0"].clone(), torch.full((n, 3 * C), float("nan"), dtype=bf, device="cuda")

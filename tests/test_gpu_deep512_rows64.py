@@ -61,10 +61,15 @@ def test_deep512_rows64_equals_the_32_row_form_bit_for_bit(ops, lp, M, tb, two_b
     chunks = [(a, min(a + CHUNK, M)) for a in range(0, M, CHUNK)]
     # ---- head: x, qkv
     x_new, qkv_new = nan(M, C), nan(M, 3 * C, dt=bf)
-    head((0, M), x0, x_new, qkv_new)
+    with ops.record_routes() as rr:
+        head((0, M), x0, x_new, qkv_new)
+    # the launch record: 64-row tiles (8 waves, NS = 2) from DEEP512_ROWS64_MIN rows, one workgroup per tile
+    assert [(r.kernel, r.bm, r.aux) for r in rr.routes] == [("deep_head_kernel<512,64,2>", 64, 1)], rr.routes
     x_ref, qkv_ref = nan(M, C), nan(M, 3 * C, dt=bf)
-    for r in chunks:
-        head(r, x0, x_ref, qkv_ref)
+    with ops.record_routes() as rr:
+        for r in chunks:
+            head(r, x0, x_ref, qkv_ref)
+    assert rr.count == len(chunks) and set(rr.kernels()) == {"deep_head_kernel<512,32,1>"}, rr.routes
     torch.cuda.synchronize()
     assert torch.equal(x0, D("x0")), "the rows read must stay untouched"
     assert bool(torch.isfinite(x_new).all()) and bool(torch.isfinite(qkv_new[:, :2 * C].float()).all())
@@ -72,10 +77,14 @@ def test_deep512_rows64_equals_the_32_row_form_bit_for_bit(ops, lp, M, tb, two_b
     # ---- tail: x, xc (the reference chunks get no workspace: the unsplit 32-row form)
     ws = torch.empty(4 * M * C * 4 + 64, dtype=torch.uint8, device="cuda") if two_buffers else None
     xt_new, xc_new = nan(M, C), nan(M, C, dt=bf)
-    tail((0, M), x0, xt_new, xc_new, ws)
+    with ops.record_routes() as rr:
+        tail((0, M), x0, xt_new, xc_new, ws)
+    assert [(r.kernel, r.bm, r.aux) for r in rr.routes] == [("deep_tail_kernel<512,64,2>", 64, 1)], rr.routes  # no split, workspace or not
     xt_ref, xc_ref = nan(M, C), nan(M, C, dt=bf)
-    for r in chunks:
-        tail(r, x0, xt_ref, xc_ref, None)
+    with ops.record_routes() as rr:
+        for r in chunks:
+            tail(r, x0, xt_ref, xc_ref, None)
+    assert rr.count == len(chunks) and {(r.kernel, r.aux) for r in rr.routes} == {("deep_tail_kernel<512,32,1>", 1)}, rr.routes
     torch.cuda.synchronize()
     assert bool(torch.isfinite(xt_new).all())
     same_tx, same_xc = torch.equal(xt_new, xt_ref), torch.equal(_i16(xc_new), _i16(xc_ref))
