@@ -288,6 +288,12 @@ SIGNATURES = {
     "cdseg_fuse_gate_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p]),
     "cdseg_fuse_gate_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_long, c_int, c_void_p, c_size_t, c_void_p]),
+    "cdseg_skip_partition": (c_int, [c_long, c_int, POINTER(c_long), POINTER(c_int)]),
+    "cdseg_skip_stats_ws_bytes": (c_size_t, [c_long, c_int]),
+    "cdseg_skip_stats": (c_int, [c_void_p, c_int, c_int, c_long, c_int, c_void_p, c_long, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "cdseg_skip_fold": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "cdseg_skip_merge": (c_int, [c_void_p, c_int, c_long, c_int, c_void_p, c_int, ctypes.c_double, c_long, ctypes.c_double,
+                                 c_void_p, c_void_p, c_int, c_void_p, c_long, c_void_p]),
     "cdseg_opt_chunks": (c_int, [POINTER(c_long), c_int, POINTER(c_int32), POINTER(c_long)]),
     "cdseg_opt_ws_bytes": (c_size_t, [c_int, c_long]),
     "cdseg_grad_norm": (c_int, [POINTER(OptTensor), c_int, c_void_p, c_long, c_void_p, c_float, c_void_p, c_void_p, c_size_t,

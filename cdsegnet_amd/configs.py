@@ -88,12 +88,33 @@ def _fusion(b, tm_feat, tm_bidirectional):
     b["tm_feat"], b["tm_bidirectional"] = tm_feat, bool(tm_bidirectional)
 
 
-def cdsegnet_config(dataset="scannet", tm_feat=1.0, tm_bidirectional=False):
+def _skip(b, skip_connection_mode, skip_connection_scale, skip_connection_scale_i, b_factor, s_factor):
+    """The five skip-connection switches of every shipped config (`skip_connection_mode = "cat" # "cat", "add", "cat_all"`,
+    `b_factor`, `s_factor`, `skip_connection_scale = True`, `skip_connection_scale_i = False`); None keeps the default."""
+    if skip_connection_mode is not None:
+        if skip_connection_mode not in ("cat", "add", "cat_all"):
+            raise ValueError(f"skip_connection_mode={skip_connection_mode!r}")
+        b["skip_connection_mode"] = skip_connection_mode
+    if skip_connection_scale is not None:
+        b["skip_connection_scale"] = bool(skip_connection_scale)
+    if skip_connection_scale_i is not None:
+        b["skip_connection_scale_i"] = bool(skip_connection_scale_i)
+    for name, v in (("b_factor", b_factor), ("s_factor", s_factor)):
+        if v is not None:
+            if len(v) != 4:
+                raise ValueError(f"{name}: one factor per n-decoder stage (4), got {v!r}")
+            b[name] = [float(x) for x in v]
+
+
+def cdsegnet_config(dataset="scannet", tm_feat=1.0, tm_bidirectional=False, skip_connection_mode=None,
+                    skip_connection_scale=None, skip_connection_scale_i=None, b_factor=None, s_factor=None):
     """``model`` dict of configs/<dataset>/CDSegNet.py (criteria dropped: the tester
-    calls inference(eval=False), test.py:216).  tm_feat / tm_bidirectional: the fusion ablation switches."""
+    calls inference(eval=False), test.py:216).  tm_feat / tm_bidirectional: the fusion ablation switches; skip_connection_* /
+    b_factor / s_factor: the skip-connection switches (`_skip`)."""
     m = copy.deepcopy(_MODEL)
     b = m["backbone"]
     _fusion(b, tm_feat, tm_bidirectional)
+    _skip(b, skip_connection_mode, skip_connection_scale, skip_connection_scale_i, b_factor, s_factor)
     if dataset == "scannet":
         pass
     elif dataset == "scannet200":
@@ -143,12 +164,15 @@ def model_config(dataset="scannet", variant="CDSegNet"):
     return m
 
 
-def mini_config(num_classes=13, in_channels=6, T_dim=64, tm_feat=1.0, tm_bidirectional=False):
+def mini_config(num_classes=13, in_channels=6, T_dim=64, tm_feat=1.0, tm_bidirectional=False, skip_connection_mode=None,
+                skip_connection_scale=None, skip_connection_scale_i=None, b_factor=None, s_factor=None):
     """Same architecture, reduced widths/depths (head dim stays 16): the end-to-end
-    golden fixture that fits in a few hundred KB.  tm_feat / tm_bidirectional: the fusion ablation switches."""
+    golden fixture that fits in a few hundred KB.  tm_feat / tm_bidirectional: the fusion ablation switches; skip_connection_* /
+    b_factor / s_factor: the skip-connection switches."""
     m = copy.deepcopy(_MODEL)
     b = m["backbone"]
     _fusion(b, tm_feat, tm_bidirectional)
+    _skip(b, skip_connection_mode, skip_connection_scale, skip_connection_scale_i, b_factor, s_factor)
     b.update(
         c_in_channels=in_channels, n_in_channels=in_channels,
         c_enc_depths=(1, 2, 1), c_enc_channels=(16, 32, 32), c_enc_num_head=(1, 2, 2),

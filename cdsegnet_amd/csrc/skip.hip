@@ -1,0 +1,348 @@
+// Skip-connection options of SerializedUnpooling: the post-activation skip scale of the 'add' mode and FreeU's Fourier filter
+// of the skip feature.
+// ref: ptv3.py:42-100 (Fourier_filter / freeU), :607-626 (scaling, FreeU, merge).  Definitions and limits: include/cdseg.h.
+//
+// The reference filters x (1, C, N) with a 2-D FFT whose mask is constant along the channel-frequency axis and scales the
+// N-frequencies 0 and -1 only.  The real part it keeps is therefore, per channel c and REFERENCE row n (theta_n = 2 pi n / N):
+//   y[n][c] = x[n][c] + k (S0_c + A_c cos theta_n + B_c sin theta_n),   k = (float32(s) - 1) / N,
+//   S0_c = sum_m x[m][c],  A_c = sum_m x[m][c] cos theta_m,  B_c = sum_m x[m][c] sin theta_m
+// - three column sums (cdseg_skip_stats) and one element-wise pass (cdseg_skip_merge) that also applies the skip scale f and
+// adds the unpooled child row.  The operator is I + k P with P symmetric: its backward is the same pair of calls.
+// Thread map as in fusion.hip: on the vector path (c a multiple of 4, operands aligned for 4 elements per access) a row is
+// covered by L = c / 4 lanes, a 256-thread block holds R = 256 / L rows at a time and a thread keeps ONE column group for its
+// lifetime; the scalar path (any other c or alignment) moves one element per access with the same arithmetic.
+// Arithmetic: cos / sin in fp64 (sincospi(2 n / N)), every element-wise expression in fp64 from the stored operands and rounded
+// to fp32 once.  The sums are accumulated in fp64: chunk b owns the rows [b rows_per_chunk, ...), a thread adds its rows by
+// ascending index, the R row slots of a block by ascending slot through LDS, the chunk partials (workspace) in a second launch:
+// by ascending chunk index inside each of 16 segments of consecutive chunks, then the segment sums by ascending segment.  No float
+// atomics: a sum is a function of (n, c), the path and the data alone.
+#include <hip/hip_runtime.h>
+
+#include "common.h"
+
+namespace {
+
+constexpr int SK_THREADS = 256;
+constexpr int SK_MIN_C = 1, SK_MAX_C = 512;
+constexpr long SK_MIN_ROWS = 64;    // rows of a chunk at least
+constexpr long SK_MAX_CHUNKS = 256; // chunk partials at most: 16 segments of 16 in the finish
+constexpr long SK_MAX_GRID = 4096;  // merge: grid-strided beyond
+
+inline void sk_partition(long n, long& rows_per_chunk, int& chunks) {
+  long rpc = (n + SK_MAX_CHUNKS - 1) / SK_MAX_CHUNKS;
+  rpc = rpc < SK_MIN_ROWS ? SK_MIN_ROWS : (rpc + 63) / 64 * 64;
+  rows_per_chunk = rpc;
+  chunks = n > 0 ? (int)((n + rpc - 1) / rpc) : 0;
+}
+
+struct SkP {
+  const void* src;         // stats: the skip feature, fp32 or the build's 16-bit type
+  float* x;                // merge: the fp32 stream, in place
+  const float* child;
+  const int32_t* ref; const int32_t* cluster;
+  const double* stats;     // merge: [S0 A B] (3 c), or the folded [u0 u1 u2]
+  double* ws;
+  double k, f, inv_n2;     // inv_n2 = 2 / N: theta_n / pi = n inv_n2
+  long n, rows_per_chunk;
+  int c, ld, ldchild, folded;
+};
+
+__device__ __forceinline__ void sk_angle(const SkP& p, long row, double& cs, double& sn) {
+  const long n = p.ref ? (long)p.ref[row] : row;
+  sincospi((double)n * p.inv_n2, &sn, &cs);
+}
+
+template <bool LP>
+__device__ __forceinline__ void sk_load4(const void* base, long off, double v[4]) {
+  if constexpr (LP) {
+    const uint2 u = *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(base) + off);
+    float a, b, c, d;
+    unpack_bf16x2(u.x, a, b);
+    unpack_bf16x2(u.y, c, d);
+    v[0] = a; v[1] = b; v[2] = c; v[3] = d;
+  } else {
+    const float4 u = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(base) + off);
+    v[0] = u.x; v[1] = u.y; v[2] = u.z; v[3] = u.w;
+  }
+}
+
+// ws[chunk][3 c] = the chunk's [S0 A B].
+template <bool LP>
+__global__ __launch_bounds__(SK_THREADS) void sk_stats_kernel(SkP p) {
+  __shared__ double red[SK_THREADS * 12];  // R row slots x 3 c sums (R * c <= 1024)
+  const int c = p.c, L = c >> 2, R = SK_THREADS / L;
+  const int r = (int)threadIdx.x / L, l = (int)threadIdx.x - r * L;
+  if (r < R) {
+    double s0[4] = {0.0, 0.0, 0.0, 0.0}, a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
+    const long row0 = (long)blockIdx.x * p.rows_per_chunk;
+    const long row1 = row0 + p.rows_per_chunk < p.n ? row0 + p.rows_per_chunk : p.n;
+    for (long i = row0 + r; i < row1; i += R) {
+      double v[4], cs, sn;
+      sk_load4<LP>(p.src, i * p.ld + 4 * l, v);
+      sk_angle(p, i, cs, sn);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        s0[e] += v[e];
+        a[e] += v[e] * cs;
+        b[e] += v[e] * sn;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      red[r * 3 * c + 4 * l + e] = s0[e];
+      red[r * 3 * c + c + 4 * l + e] = a[e];
+      red[r * 3 * c + 2 * c + 4 * l + e] = b[e];
+    }
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < 3 * c; j += SK_THREADS) {
+    double t = red[j];
+    for (int q = 1; q < R; ++q) t += red[q * 3 * c + j];
+    p.ws[(long)blockIdx.x * 3 * c + j] = t;
+  }
+}
+
+template <bool LP>
+__global__ __launch_bounds__(SK_THREADS) void sk_stats_scalar_kernel(SkP p) {
+  const int c = p.c;
+  const long row0 = (long)blockIdx.x * p.rows_per_chunk;
+  const long row1 = row0 + p.rows_per_chunk < p.n ? row0 + p.rows_per_chunk : p.n;
+  for (int j = threadIdx.x; j < c; j += SK_THREADS) {
+    double s0 = 0.0, a = 0.0, b = 0.0;
+    for (long i = row0; i < row1; ++i) {
+      double cs, sn;
+      sk_angle(p, i, cs, sn);
+      const long off = i * p.ld + j;
+      const double v = LP ? (double)bf16_to_f32(reinterpret_cast<const bf16_t*>(p.src)[off])
+                          : (double)reinterpret_cast<const float*>(p.src)[off];
+      s0 += v;
+      a += v * cs;
+      b += v * sn;
+    }
+    double* w = p.ws + (long)blockIdx.x * 3 * c;
+    w[j] = s0;
+    w[c + j] = a;
+    w[2 * c + j] = b;
+  }
+}
+
+// The finish: output i = the sum of its `chunks` partials.  A serial chain over up to 256 partials is bound by the latency of its
+// loads (45 us measured), so the chain is cut into SK_SEGS segments of seg = ceil(chunks / SK_SEGS) consecutive chunks: thread
+// (g, o) of a block adds segment g of output blockIdx * 16 + o by ascending chunk index (its loads are independent and in flight
+// together), thread (0, o) then adds the segment sums by ascending segment.  The order is a function of `chunks` alone.
+constexpr int SK_SEGS = 16;
+
+__global__ __launch_bounds__(256) void sk_reduce_kernel(const double* __restrict__ ws, int chunks, int count, double* __restrict__ out) {
+  __shared__ double red[SK_SEGS][16];
+  const int o = threadIdx.x & 15, g = threadIdx.x >> 4;
+  const int i = blockIdx.x * 16 + o;
+  const int seg = (chunks + SK_SEGS - 1) / SK_SEGS;
+  const int b0 = g * seg, b1 = b0 + seg < chunks ? b0 + seg : chunks;
+  double t = 0.0;
+  if (i < count && b0 < b1) {
+    const double* p = ws + i;
+    t = p[(long)b0 * count];
+#pragma unroll 16
+    for (int b = b0 + 1; b < b1; ++b) t += p[(long)b * count];
+  }
+  red[g][o] = t;
+  __syncthreads();
+  if (g == 0 && i < count) {
+    double v = red[0][o];
+    const int segs = (chunks + seg - 1) / seg;
+    for (int q = 1; q < segs; ++q) v += red[q][o];
+    out[i] = v;
+  }
+}
+
+// One element of the merge: v = x; with stats v += k (S0 + A cos + B sin), all of it times f (folded: only the added term is
+// times f, x carries f already); then + child.
+__device__ __forceinline__ float sk_element(const SkP& p, double x, double s0, double a, double b, double cs, double sn,
+                                            bool filt, bool has_child, double ch) {
+  double v;
+  if (filt) {
+    const double t = p.k * (s0 + a * cs + b * sn);
+    v = p.folded ? x + p.f * t : p.f * (x + t);
+  } else {
+    v = p.f * x;
+  }
+  if (has_child) v += ch;
+  return (float)v;
+}
+
+__global__ __launch_bounds__(SK_THREADS) void sk_merge_kernel(SkP p) {
+  const int c = p.c, L = c >> 2, R = SK_THREADS / L;
+  const int r = (int)threadIdx.x / L, l = (int)threadIdx.x - r * L;
+  if (r >= R) return;
+  const bool filt = p.stats != nullptr, has_child = p.child != nullptr;
+  double s0[4] = {0.0, 0.0, 0.0, 0.0}, a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
+  if (filt) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      s0[e] = p.stats[4 * l + e];
+      a[e] = p.stats[c + 4 * l + e];
+      b[e] = p.stats[2 * c + 4 * l + e];
+    }
+  }
+  for (long i = (long)blockIdx.x * R + r; i < p.n; i += (long)gridDim.x * R) {
+    float* xp = p.x + i * p.ld + 4 * l;
+    const float4 xv = *reinterpret_cast<const float4*>(xp);
+    const float x4[4] = {xv.x, xv.y, xv.z, xv.w};
+    float c4[4] = {0.f, 0.f, 0.f, 0.f};
+    if (has_child) {
+      const float4 cv = *reinterpret_cast<const float4*>(p.child + (long)p.cluster[i] * p.ldchild + 4 * l);
+      c4[0] = cv.x; c4[1] = cv.y; c4[2] = cv.z; c4[3] = cv.w;
+    }
+    double cs = 1.0, sn = 0.0;
+    if (filt) sk_angle(p, i, cs, sn);
+    float o[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = sk_element(p, (double)x4[e], s0[e], a[e], b[e], cs, sn, filt, has_child, (double)c4[e]);
+    *reinterpret_cast<float4*>(xp) = make_float4(o[0], o[1], o[2], o[3]);
+  }
+}
+
+__global__ __launch_bounds__(SK_THREADS) void sk_merge_scalar_kernel(SkP p) {
+  const long total = p.n * p.c;
+  const bool filt = p.stats != nullptr, has_child = p.child != nullptr;
+  for (long t = (long)blockIdx.x * SK_THREADS + threadIdx.x; t < total; t += (long)gridDim.x * SK_THREADS) {
+    const long i = t / p.c;
+    const int j = (int)(t - i * p.c);
+    double cs = 1.0, sn = 0.0, s0 = 0.0, a = 0.0, b = 0.0;
+    if (filt) {
+      sk_angle(p, i, cs, sn);
+      s0 = p.stats[j]; a = p.stats[p.c + j]; b = p.stats[2 * p.c + j];
+    }
+    const double ch = has_child ? (double)p.child[(long)p.cluster[i] * p.ldchild + j] : 0.0;
+    float* xp = p.x + i * p.ld + j;
+    *xp = sk_element(p, (double)*xp, s0, a, b, cs, sn, filt, has_child, ch);
+  }
+}
+
+// u[j][o] = sum_i W[o][i] stats[j][i], j = 0..2: block o, lane q adds i = q, q + 64, ... by ascending i, the 64 lane sums are
+// added by ascending lane.
+template <bool LP>
+__global__ __launch_bounds__(64) void sk_fold_kernel(const void* __restrict__ w, int ldw, int cin, int cout,
+                                                     const double* __restrict__ stats, double* __restrict__ u) {
+  __shared__ double red[3 * 64];
+  const int o = blockIdx.x, q = threadIdx.x;
+  double t[3] = {0.0, 0.0, 0.0};
+  for (int i = q; i < cin; i += 64) {
+    const long off = (long)o * ldw + i;
+    const double wv = LP ? (double)bf16_to_f32(reinterpret_cast<const bf16_t*>(w)[off]) : (double)reinterpret_cast<const float*>(w)[off];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) t[j] += wv * stats[j * cin + i];
+  }
+#pragma unroll
+  for (int j = 0; j < 3; ++j) red[j * 64 + q] = t[j];
+  __syncthreads();
+  if (q < 3) {
+    double v = red[q * 64];
+    for (int e = 1; e < 64; ++e) v += red[q * 64 + e];
+    u[q * cout + o] = v;
+  }
+}
+
+int sk_width_status(int c) { return (c < SK_MIN_C || c > SK_MAX_C) ? CDSEG_ERR_UNSUPPORTED : CDSEG_OK; }
+
+bool sk_aligned(uintptr_t mask, const void* p) { return (((uintptr_t)p) & mask) == 0; }
+
+}  // namespace
+
+extern "C" {
+
+int cdseg_skip_partition(long n, int c, long* rows_per_chunk, int* chunks) {
+  if (n < 0 || !rows_per_chunk || !chunks) return CDSEG_ERR_ARG;
+  const int st = sk_width_status(c);
+  if (st != CDSEG_OK) return st;
+  sk_partition(n, *rows_per_chunk, *chunks);
+  return CDSEG_OK;
+}
+
+size_t cdseg_skip_stats_ws_bytes(long n, int c) {
+  if (n <= 0 || sk_width_status(c) != CDSEG_OK) return 0;
+  long rpc;
+  int chunks;
+  sk_partition(n, rpc, chunks);
+  return (size_t)chunks * 3 * (size_t)c * sizeof(double);
+}
+
+int cdseg_skip_stats(const void* x, int dtype, int ldx, long n, int c, const int32_t* ref_of_row, long n_total, double* stats,
+                     void* ws, size_t ws_bytes, void* stream) {
+  if (n < 0 || (dtype != CDSEG_F32 && dtype != CDSEG_BF16)) return CDSEG_ERR_ARG;
+  const int st = sk_width_status(c);
+  if (st != CDSEG_OK) return st;
+  if (n >= (1L << 31) || n_total >= (1L << 31)) return CDSEG_ERR_UNSUPPORTED;  // the row map is int32
+  if (n == 0) return CDSEG_OK;
+  const bool lp = dtype == CDSEG_BF16;
+  if (!x || !stats || ldx < c || n_total < n || !sk_aligned(lp ? 1 : 3, x) || !sk_aligned(3, ref_of_row) || !sk_aligned(7, stats))
+    return CDSEG_ERR_ARG;
+  if (ws && !sk_aligned(15, ws)) return CDSEG_ERR_ARG;
+  if (!ws || ws_bytes < cdseg_skip_stats_ws_bytes(n, c)) return CDSEG_ERR_WORKSPACE;
+  SkP p = {};
+  p.src = x; p.ref = ref_of_row; p.ws = (double*)ws; p.n = n; p.c = c; p.ld = ldx; p.inv_n2 = 2.0 / (double)n_total;
+  int chunks;
+  sk_partition(n, p.rows_per_chunk, chunks);
+  hipStream_t q = (hipStream_t)stream;
+  const bool vec = (c & 3) == 0 && (ldx & 3) == 0 && sk_aligned(lp ? 7 : 15, x);
+  if (vec && lp)
+    hipLaunchKernelGGL(sk_stats_kernel<true>, dim3((unsigned)chunks), dim3(SK_THREADS), 0, q, p);
+  else if (vec)
+    hipLaunchKernelGGL(sk_stats_kernel<false>, dim3((unsigned)chunks), dim3(SK_THREADS), 0, q, p);
+  else if (lp)
+    hipLaunchKernelGGL(sk_stats_scalar_kernel<true>, dim3((unsigned)chunks), dim3(SK_THREADS), 0, q, p);
+  else
+    hipLaunchKernelGGL(sk_stats_scalar_kernel<false>, dim3((unsigned)chunks), dim3(SK_THREADS), 0, q, p);
+  CDSEG_CHECK_LAUNCH();
+  hipLaunchKernelGGL(sk_reduce_kernel, dim3((unsigned)cdiv(3 * c, 16)), dim3(256), 0, q, (const double*)ws, chunks, 3 * c, stats);
+  CDSEG_CHECK_LAUNCH();
+  return CDSEG_OK;
+}
+
+int cdseg_skip_fold(const void* w, int dtype, int ldw, int cout, int cin, const double* stats, double* u, void* stream) {
+  if (dtype != CDSEG_F32 && dtype != CDSEG_BF16) return CDSEG_ERR_ARG;
+  if (sk_width_status(cin) != CDSEG_OK || sk_width_status(cout) != CDSEG_OK) return CDSEG_ERR_UNSUPPORTED;
+  const bool lp = dtype == CDSEG_BF16;
+  if (!w || !stats || !u || ldw < cin || !sk_aligned(lp ? 1 : 3, w) || !sk_aligned(7, stats) || !sk_aligned(7, u)) return CDSEG_ERR_ARG;
+  if (lp)
+    hipLaunchKernelGGL(sk_fold_kernel<true>, dim3((unsigned)cout), dim3(64), 0, (hipStream_t)stream, w, ldw, cin, cout, stats, u);
+  else
+    hipLaunchKernelGGL(sk_fold_kernel<false>, dim3((unsigned)cout), dim3(64), 0, (hipStream_t)stream, w, ldw, cin, cout, stats, u);
+  CDSEG_CHECK_LAUNCH();
+  return CDSEG_OK;
+}
+
+int cdseg_skip_merge(float* x, int ldx, long n, int c, const double* stats, int folded, double s, long n_total, double f,
+                     const int32_t* ref_of_row, const float* child, int ldchild, const int32_t* cluster, long n_child, void* stream) {
+  if (n < 0) return CDSEG_ERR_ARG;
+  const int st = sk_width_status(c);
+  if (st != CDSEG_OK) return st;
+  if (n >= (1L << 31) || n_total >= (1L << 31) || n_child >= (1L << 31)) return CDSEG_ERR_UNSUPPORTED;
+  if (n == 0) return CDSEG_OK;
+  if (!x || ldx < c || !sk_aligned(3, x) || !sk_aligned(3, ref_of_row) || !sk_aligned(3, child) || !sk_aligned(3, cluster) ||
+      !sk_aligned(7, stats) || (stats && n_total < n) || (folded && !stats) || (child && (!cluster || n_child <= 0 || ldchild < c)) ||
+      (!child && cluster) || !(f == f) || !(s == s))
+    return CDSEG_ERR_ARG;
+  SkP p = {};
+  p.x = x; p.ld = ldx; p.n = n; p.c = c; p.stats = stats; p.folded = folded ? 1 : 0; p.f = f; p.ref = stats ? ref_of_row : nullptr;
+  p.child = child; p.ldchild = ldchild; p.cluster = cluster;
+  if (stats) {
+    p.k = ((double)(float)s - 1.0) / (double)n_total;  // the reference's mask is a float32 tensor
+    p.inv_n2 = 2.0 / (double)n_total;
+  }
+  const bool vec = (c & 3) == 0 && (ldx & 3) == 0 && sk_aligned(15, x) && (!child || ((ldchild & 3) == 0 && sk_aligned(15, child)));
+  if (vec) {
+    const int R = SK_THREADS / (c >> 2);
+    long blocks = (n + (long)R * 4 - 1) / ((long)R * 4);  // about four rows a thread
+    blocks = blocks < 1 ? 1 : (blocks > SK_MAX_GRID ? SK_MAX_GRID : blocks);
+    hipLaunchKernelGGL(sk_merge_kernel, dim3((unsigned)blocks), dim3(SK_THREADS), 0, (hipStream_t)stream, p);
+  } else {
+    long blocks = (n * c + (long)SK_THREADS * 4 - 1) / ((long)SK_THREADS * 4);
+    blocks = blocks < 1 ? 1 : (blocks > SK_MAX_GRID ? SK_MAX_GRID : blocks);
+    hipLaunchKernelGGL(sk_merge_scalar_kernel, dim3((unsigned)blocks), dim3(SK_THREADS), 0, (hipStream_t)stream, p);
+  }
+  CDSEG_CHECK_LAUNCH();
+  return CDSEG_OK;
+}
+
+}  // extern "C"

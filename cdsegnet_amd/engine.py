@@ -126,6 +126,13 @@ class Level:
             return ops.sort_pairs(self.code4[curve], None, end_bit=end_bit)[1]
         return _shared(self._order, curve, build, self.shared)
 
+    def ref_of_row(self, curve):
+        """physical row -> rank on a curve, the inverse of `order` (None = identity for z)."""
+        order = self.order(curve)
+        if order is None:
+            return None
+        return _shared(self._order, ("inverse", curve), lambda: ops.invert_perm(order), self.shared)
+
     def nbr(self, ksize, kmajor=False):
         # offset-major tables: a wave searches one offset of 64 consecutive z-ordered points (same cache lines);
         # an open-addressing hash table was measured and is NOT faster (two dependent random reads per lookup)
@@ -311,6 +318,14 @@ class Plan:
             m = self.levels[b].n
             return (cluster[fine.row_vox.long()], fine.row_start[seg[:m + 1].long()])
         return _shared(self._row_links, b, build, self.shared)
+
+
+def skip_modules(bb):
+    """The SerializedUnpooling modules of a backbone, n-decoder first."""
+    for name in ("_n_dec", "_c_dec"):
+        if hasattr(bb, name):  # (an unconditional backbone has no c-decoder)
+            for dec in getattr(bb, name)._modules.values():
+                yield dec.up
 
 
 def _per_element(perm):
@@ -540,9 +555,7 @@ class Engine:
             lin(mod.proj_skip[0], pre + ".skip")
             bn(mod.proj_skip[1], pre + ".skip_bn")
             if mod.skip_connection_mode == "cat":
-                f = (2 ** -0.5 if mod.skip_connection_scale else 1.0)
-                if mod.skip_connection_scale_i is not None:
-                    f *= 0.8 ** (int(mod.skip_connection_scale_i) - 1)
+                f = mod.skip_scale
                 wc = mod.proj_cat[0].weight.detach().float()
                 c = wc.shape[0]
                 w[pre + ".cat_a.w"] = (wc[:, :c] * f).to(device=device, dtype=T).contiguous()
@@ -1403,29 +1416,54 @@ class Engine:
         out.parent = st
         return out
 
+    def _skip_ref(self, plan, parent):
+        """physical row -> REFERENCE row of the skip feature's level (None = identity): the caller's order at level 0
+        (plan.perm0), above it the rank on the curve that was first in the order list when the level was pooled
+        (ptv3.py:489-493).  The Fourier filter of FreeU runs over the reference's rows."""
+        if parent.parent is None:
+            return plan.perm0
+        curve = parent.parent.curves[0]
+        if isinstance(curve, tuple):
+            if len(set(curve)) != 1:
+                raise ValueError("a model that filters its skip features (s_factor != 1) has no per-fragment draws: the "
+                                 "reference's filter runs over the rows of the whole batch in ONE order")
+            curve = curve[0]
+        return parent.level.ref_of_row(curve)
+
     def run_unpooling(self, plan, st, pre, mod):
-        """ref: ptv3.py:597-630.  xc keeps the PRE-merge, unscaled skip feature: the reference leaves
+        """ref: ptv3.py:597-630.  xc keeps the PRE-merge, unscaled, unfiltered skip feature: the reference leaves
         sparse_conv_feat stale there and the next CPE conv reads it.
-        'add' (n-branch): x = f * skip + child[cluster];  'cat' (c-branch): x = proj_cat([f * skip, child[cluster]])
-        with f = 2^-0.5 (skip_connection_scale) * 0.8^(i-1) (skip_connection_scale_i, False -> 1.25)."""
+        'add' (n-branch): x = f * F(skip) + child[cluster];  'cat' (c-branch): x = proj_cat([f * F(skip), child[cluster]])
+        with f = 2^-0.5 (skip_connection_scale) * 0.8^(i-1) (skip_connection_scale_i, False -> 1.25) and F the Fourier filter
+        of FreeU over all rows of the level (mod.skip_filter; csrc/skip.hip), the identity in every shipped config.
+        Without a filter, 'cat' and 'add' with f = 1 are the launches they always were."""
         w = self.w
         parent = st.parent
         fine, coarse = parent.level, st.level
         cluster, _ = plan.link(fine.cum, coarse.cum)
         cout = w[pre + ".proj.w"].shape[0]
-        f = (2 ** -0.5 if mod.skip_connection_scale else 1.0)
-        if mod.skip_connection_scale_i is not None:
-            f *= 0.8 ** (int(mod.skip_connection_scale_i) - 1)
+        f = mod.skip_scale
+        s = mod.skip_filter
         x = self._buf(fine.n, cout, torch.float32)
         xc = self._buf(fine.n, cout, self.T)
         if mod.skip_connection_mode == "add":
-            assert f == 1.0, "rejected by SerializedUnpooling.__init__"
             child = self._buf(coarse.n, cout, torch.float32)
             ops.gemm(st.xc, w[pre + ".proj.w"], child, bias=w[pre + ".proj.b"], scale=w[pre + ".proj_bn.scale"],
                      shift=w[pre + ".proj_bn.shift"], act=ops.ACT_GELU)
-            ops.gemm(parent.xc, w[pre + ".skip.w"], x, bias=w[pre + ".skip.b"], scale=w[pre + ".skip_bn.scale"],
-                     shift=w[pre + ".skip_bn.shift"], act=ops.ACT_GELU, add_src=child, add_idx=cluster, out2=xc,
-                     out2_pre_add=True)
+            if f == 1.0 and s is None:
+                ops.gemm(parent.xc, w[pre + ".skip.w"], x, bias=w[pre + ".skip.b"], scale=w[pre + ".skip_bn.scale"],
+                         shift=w[pre + ".skip_bn.shift"], act=ops.ACT_GELU, add_src=child, add_idx=cluster, out2=xc,
+                         out2_pre_add=True)
+            else:
+                # the GEMM's add epilogue has no post-activation scalar: the skip goes to x (and its 16-bit copy to xc) as it
+                # is, one more pass scales / filters it and adds the child rows
+                ops.gemm(parent.xc, w[pre + ".skip.w"], x, bias=w[pre + ".skip.b"], scale=w[pre + ".skip_bn.scale"],
+                         shift=w[pre + ".skip_bn.shift"], act=ops.ACT_GELU, out2=xc)
+                if s is None:
+                    ops.skip_merge(x, f=f, child=child, cluster=cluster)
+                else:
+                    ref = self._skip_ref(plan, parent)
+                    ops.skip_merge(x, ops.skip_stats(x, ref, fine.n), s, f, ref, fine.n, child, cluster)
         else:
             # proj_cat([f*par, child[inv]]) = par @ (f*Wa)^T + (child @ Wb^T)[inv] + b
             child = self._buf(coarse.n, cout, self.T)
@@ -1436,6 +1474,12 @@ class Engine:
             ops.gemm(parent.xc, w[pre + ".skip.w"], xc, bias=w[pre + ".skip.b"], scale=w[pre + ".skip_bn.scale"],
                      shift=w[pre + ".skip_bn.shift"], act=ops.ACT_GELU)
             ops.gemm(xc, w[pre + ".cat_a.w"], x, bias=w[pre + ".cat.b"], add_src=z, add_idx=cluster)
+            if s is not None:
+                # proj_cat is linear: the filter's k (S0 + A cos + B sin) arrives behind it as k (u0 + u1 cos + u2 sin) with
+                # u = (f Wa) [S0 A B] - no n x C pass over a filtered copy, and xc stays the unfiltered skip
+                ref = self._skip_ref(plan, parent)
+                u = ops.skip_fold(w[pre + ".cat_a.w"], ops.skip_stats(xc, ref, fine.n))
+                ops.skip_merge(x, u, s, 1.0, ref, fine.n, folded=True)
         self._sat_note(xc)
         out = State(fine, x, xc, parent.curves)
         out.parent = parent.parent
@@ -1708,6 +1752,10 @@ class Engine:
     # -- shared set-up -------------------------------------------------------------------------------
     def _setup(self, input_dict, noise_level, draws, n_backbone_calls, always_noise=False, plan=None):
         m, bb = self.model, self.model.backbone
+        if draws is not None and (draws.get("per_fragment") or any(_per_element(p) for p in draws.get("perms") or ())):
+            if any(up.skip_filter is not None for up in skip_modules(bb)):
+                raise ValueError("per-fragment draws on a model that filters its skip features (s_factor != 1): the reference's "
+                                 "Fourier filter runs over the rows of the whole batch in one order (ptv3.py:614-620)")
         feat = input_dict["feat"]
         dev = feat.device  # CPU tensors are rejected by every op (cdsegnet_amd.ops): no CPU fallback
         self.prepare(dev)

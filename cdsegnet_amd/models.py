@@ -7,13 +7,15 @@ point_transformer_v3m1_base.py:1340-1755), so released checkpoints load ``strict
 unchanged.  The ``nn.Module`` tree below only OWNS parameters (names/shapes = the reference's);
 the forward pass is executed by ``cdsegnet_amd.engine`` on hand-written HIP kernels.
 Options that every shipped CDSegNet config leaves off (RPE, PDNorm, Restormer fusion,
-FreeU, cls_mode) are accepted by the constructors and rejected loudly.  The two Feature Fusion Module
-switches the shipped configs spell out - learned fusion scales (``tm_feat``) and bidirectional fusion
-(``tm_bidirectional``) - are built.
+cls_mode) are accepted by the constructors and rejected loudly.  The switches the shipped configs spell out
+next to their defaults are built: learned fusion scales (``tm_feat``), bidirectional fusion
+(``tm_bidirectional``) and the five skip-connection switches (``skip_connection_mode``,
+``skip_connection_scale``, ``skip_connection_scale_i``, ``b_factor``, ``s_factor``).
 """
 import math
-
+import numbers
 import threading
+import warnings
 
 import numpy as np
 import torch
@@ -136,14 +138,34 @@ class SerializedPooling(nn.Module):
         self.act = PointSequential(nn.GELU())
 
 
+_B_FACTOR_WARNED = False
+
+
+def _warn_b_factor():
+    """Once per process: what a b_factor != 1 does."""
+    global _B_FACTOR_WARNED
+    if not _B_FACTOR_WARNED:
+        _B_FACTOR_WARNED = True
+        warnings.warn("b_factor != 1 has the reference's effect, which is none: freeU takes the channel count from the channel "
+                      "MEAN (one channel), so C_num = 0 and no backbone channel is scaled "
+                      "(point_transformer_v3m1_base.py:81-96).  It only switches the skip filter on, with s_factor as given")
+
+
 class SerializedUnpooling(nn.Module):
     """ref: ptv3.py:558-630."""
 
     def __init__(self, in_channels, skip_channels, out_channels, skip_connection_mode="add", b=1.0, s=1.0,
                  skip_connection_scale=False, skip_connection_scale_i=False):
         super().__init__()
-        if b != 1 or s != 1:
-            raise NotImplementedError("FreeU (b/s factors != 1) is off in every shipped config; not on the hot path")
+        for name, v in (("b", b), ("s", s)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v):
+                raise ValueError(f"SerializedUnpooling({name}={v!r}): a FreeU factor is a finite number")
+        # FreeU (ptv3.py:68-100, :614-620).  s: the Fourier filter of the skip feature (csrc/skip.hip).  b has the reference's
+        # effect, which is none: freeU reads the channel count AFTER the channel mean has made that dimension 1 (ptv3.py:81-84),
+        # so C_num = 0 and `b_feat[:, :0]` scales no channel (:96); b != 1 only switches the filter on with whatever s is
+        self.b, self.s = float(b), float(s)
+        if self.b != 1.0:
+            _warn_b_factor()
         bn = lambda c: nn.BatchNorm1d(c, eps=1e-3, momentum=0.01)  # noqa: E731
         self.proj = PointSequential(nn.Linear(in_channels, out_channels), bn(out_channels), nn.GELU())
         self.proj_skip = PointSequential(nn.Linear(skip_channels, out_channels), bn(out_channels), nn.GELU())
@@ -152,22 +174,23 @@ class SerializedUnpooling(nn.Module):
         self.skip_connection_scale_i = skip_connection_scale_i
         if skip_connection_mode == "cat":
             self.proj_cat = PointSequential(nn.Linear(out_channels * 2, out_channels))
-        elif skip_connection_mode == "add":
-            # skip scaling (ptv3.py:607-611; note skip_connection_scale_i=False still scales by 0.8^(0-1) = 1.25) is folded
-            # into proj_cat's weight in 'cat' mode; the 'add' epilogue has no post-activation scalar, so the combination
-            # (off in every shipped config) is rejected HERE and not in the middle of a forward
-            f = (2 ** -0.5 if skip_connection_scale else 1.0)
-            if skip_connection_scale_i is not None:
-                f *= 0.8 ** (int(skip_connection_scale_i) - 1)
-            if f != 1.0:
-                raise NotImplementedError(
-                    f"SerializedUnpooling(skip_connection_mode='add') with a skip scale of {f:g} "
-                    f"(skip_connection_scale={skip_connection_scale!r}, skip_connection_scale_i={skip_connection_scale_i!r}): "
-                    "the 'add' epilogue has no post-activation scalar.  No shipped CDSegNet / PTv3 config asks for it; use "
-                    "skip_connection_mode='cat' (the scale is folded into proj_cat) or skip_connection_scale=False with "
-                    "skip_connection_scale_i=None")
-        else:
+        elif skip_connection_mode != "add":
             raise ValueError(f"skip_connection_mode={skip_connection_mode!r}")
+
+    @property
+    def skip_scale(self):
+        """f of ptv3.py:607-611: 2^-0.5 (skip_connection_scale) times 0.8^(i-1) (skip_connection_scale_i; note that False still
+        scales by 0.8^(0-1) = 1.25).  'cat' folds it into proj_cat's weight, 'add' applies it in cdseg_skip_merge."""
+        f = 2 ** -0.5 if self.skip_connection_scale else 1.0
+        if self.skip_connection_scale_i is not None:
+            f *= 0.8 ** (int(self.skip_connection_scale_i) - 1)
+        return f
+
+    @property
+    def skip_filter(self):
+        """The s of the Fourier filter this module runs, or None: the reference filters when b != 1 or s != 1 (ptv3.py:614);
+        with s == 1 the filter is the identity (k = 0) and no launch is spent on it."""
+        return self.s if float(np.float32(self.s)) != 1.0 else None
 
 
 class Embedding(nn.Module):

@@ -1865,6 +1865,77 @@ def fuse_gate_bwd(dy, s, a, alpha, gamma, m=None):
     return ds, da, sums
 
 
+def _sk_rows(what, t, dtypes):
+    if t.dim() != 2 or t.stride(1) != 1 or t.dtype not in dtypes:
+        raise _lib.CdsegError(f"{what}: a (rows, c) tensor with unit column stride, dtype one of {dtypes}")
+
+
+def _sk_map(what, m, n):
+    if m is not None and (m.dtype != torch.int32 or not m.is_contiguous() or m.numel() != n):
+        raise _lib.CdsegError(f"{what}: the row map is one contiguous int32 value per row")
+    return m
+
+
+def skip_partition(n, c):
+    """(rows_per_chunk, chunks) of `skip_stats` for an (n, c) feature: host only, a function of the shape."""
+    rpc, chunks = ctypes.c_long(0), ctypes.c_int(0)
+    check(_lib.load().cdseg_skip_partition(int(n), int(c), ctypes.byref(rpc), ctypes.byref(chunks)), "skip_partition")
+    return rpc.value, chunks.value
+
+
+def skip_stats(x, ref_of_row=None, n_total=None):
+    """[S0 A B] (3 c) fp64 of the skip feature x (n, c), fp32 or the active build's 16-bit type (cdseg_skip_stats): the three
+    column sums behind FreeU's Fourier filter, with cos / sin of 2 pi m / n_total at the REFERENCE row m = ref_of_row[r]
+    (int32, physical row -> reference row; None = identity).  fp64 sums in an order fixed by the shape: equal inputs give
+    equal bits.  No host read."""
+    _need_gpu(x, ref_of_row)
+    _sk_rows("skip_stats", x, (torch.float32, LP_DTYPES[_lib.active()]))
+    n, c = x.shape
+    n_total = n if n_total is None else int(n_total)
+    if n == 0:
+        return torch.zeros(3 * c, dtype=torch.float64, device=x.device)
+    lib = _lib.load()
+    stats = torch.empty(3 * c, dtype=torch.float64, device=x.device)
+    ws = _scratch(max(16, lib.cdseg_skip_stats_ws_bytes(n, c)), x.device)
+    check(lib.cdseg_skip_stats(_ptr(x), dt(x), x.stride(0), n, c, _ptr(_sk_map("skip_stats", ref_of_row, n)), n_total, _ptr(stats),
+                               _ptr(ws), ws.numel(), _stream()), "skip_stats")
+    return stats
+
+
+def skip_fold(w, stats):
+    """u (3 cout) fp64 = [W S0, W A, W B] for the (cout, cin) matrix w (fp32 or the 16-bit type) and `skip_stats`' output:
+    what the filter adds behind a Linear that reads the filtered feature (cdseg_skip_fold)."""
+    _need_gpu(w, stats)
+    _sk_rows("skip_fold", w, (torch.float32, LP_DTYPES[_lib.active()]))
+    cout, cin = w.shape
+    assert stats.dtype == torch.float64 and stats.is_contiguous() and stats.numel() == 3 * cin
+    u = torch.empty(3 * cout, dtype=torch.float64, device=w.device)
+    check(_lib.load().cdseg_skip_fold(_ptr(w), dt(w), w.stride(0), cout, cin, _ptr(stats), _ptr(u), _stream()), "skip_fold")
+    return u
+
+
+def skip_merge(x, stats=None, s=1.0, f=1.0, ref_of_row=None, n_total=None, child=None, cluster=None, folded=False):
+    """In place on the fp32 stream x (n, c) (cdseg_skip_merge), k = (float32(s) - 1) / n_total:
+        x = f * (x + k * (S0 + A cos t_r + B sin t_r)) + child[cluster]
+        folded (stats = `skip_fold`'s u, x carries f already):  x = x + f * k * (u0 + u1 cos t_r + u2 sin t_r) + child[cluster]
+    stats None: f * x + child[cluster]; child None: the scaled / filtered skip alone.  Returns x."""
+    _need_gpu(x, stats, ref_of_row, child, cluster)
+    _sk_rows("skip_merge", x, (torch.float32,))
+    n, c = x.shape
+    n_total = n if n_total is None else int(n_total)
+    if stats is not None:
+        assert stats.dtype == torch.float64 and stats.is_contiguous() and stats.numel() == 3 * c
+    if child is not None:
+        _sk_rows("skip_merge", child, (torch.float32,))
+        assert child.shape[1] == c and cluster is not None
+        _sk_map("skip_merge", cluster, n)
+    check(_lib.load().cdseg_skip_merge(_ptr(x), x.stride(0), n, c, _ptr(stats), int(bool(folded)), float(s), n_total, float(f),
+                                       _ptr(_sk_map("skip_merge", ref_of_row, n)), _ptr(child),
+                                       0 if child is None else child.stride(0), _ptr(cluster),
+                                       0 if child is None else child.shape[0], _stream()), "skip_merge")
+    return x
+
+
 def segment_max_arg(y, seg_start, m):
     """(out, arg): out (m, c) fp32 = per-channel maximum over the rows seg_start[j] .. seg_start[j + 1] - 1 of y (the bits of
     `segment_max` without scale / shift / activation), arg (m, c) int32 = the first row that holds it (cdseg_segment_max_arg)."""

@@ -597,6 +597,27 @@ class _FuseGate(torch.autograd.Function):
         return ds, da, None, gate_dp(ctx.mode, p, sums).to(p.dtype), None
 
 
+def _skip_filter(x, ref_of_row, s):
+    y = _c(x.float()).clone()
+    n = y.shape[0]
+    return ops.skip_merge(y, ops.skip_stats(y, ref_of_row, n), s, 1.0, ref_of_row, n)
+
+
+class _SkipFilter(torch.autograd.Function):
+    """FreeU's Fourier filter of a skip feature (ptv3.py:42-66, :614-620) over the two kernels of csrc/skip.hip:
+    y = x + k P x with P symmetric, so the backward is the same pair of calls on the incoming gradient.  The sums run in fp64
+    in an order fixed by the shape whatever `train_deterministic` says.  fp32 in every train_precision."""
+
+    @staticmethod
+    def forward(ctx, x, ref_of_row, s):
+        ctx.ref, ctx.s = ref_of_row, s
+        return _skip_filter(x, ref_of_row, s)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _skip_filter(dy, ctx.ref, ctx.s), None, None
+
+
 def _swish(x):  # ptv3.py:30-31
     return x * torch.sigmoid(x)
 
@@ -916,11 +937,13 @@ class TrainGraph:
         par = _bn_gelu(self._lin(parent.x, up.proj_skip[0]), up.proj_skip[1], self.train_norm)
         out = _St(fine, None, parent.curves, parent.ref_order, parent=parent.parent)
         out.conv = par  # what the next Block's CPE conv reads: the skip feature before scaling and merging
-        f = 2 ** -0.5 if up.skip_connection_scale else 1.0
-        if up.skip_connection_scale_i is not None:
-            f *= 0.8 ** (int(up.skip_connection_scale_i) - 1)
+        f = up.skip_scale
         if f != 1.0:
             par = par * f
+        if up.skip_filter is not None:  # FreeU: over all rows of the level, in the reference's row order
+            if getattr(parent, "ref_of_row", None) is None:  # physical row -> reference row
+                parent.ref_of_row = ops.invert_perm(_c(parent.ref_order.to(torch.int32)))
+            par = _SkipFilter.apply(par, parent.ref_of_row, up.skip_filter)
         if self.det:  # the index backward would add a pooled row's (up to eight) children with atomics
             gathered = _GatherRuns.apply(child, cluster.long(), seg[:coarse.n + 1], None)
         else:
@@ -1042,6 +1065,9 @@ class TrainGraph:
                 plan = self._rows_plan(grid, offset_host, keep, rep, offset_u)
                 rep = None
             else:
+                if any(up.skip_filter is not None for up in _engine.skip_modules(bb)):
+                    raise ValueError("a folded Mix3D batch (train_mix3d = 'fold') on a model that filters its skip features "
+                                     "(s_factor != 1): the reference filters over all N rows; use train_mix3d = 'rows'")
                 if not getattr(self, "_warned_duplicates", False):
                     self._warned_duplicates = True
                     warnings.warn(f"training batch with {e.count} points in already occupied voxels (Mix3D): folded onto the "

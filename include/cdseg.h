@@ -904,6 +904,50 @@ int cdseg_fuse_gate_fwd(const float* s, const float* a, const float* m, const fl
 int cdseg_fuse_gate_bwd(const float* dy, const float* s, const float* a, const float* m, const float* alpha, const float* gamma,
                         float* ds, float* da, double* sums, long rows, int c, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ skip-connection options (csrc/skip.hip)
+ * ref: SerializedUnpooling.forward, ptv3.py:607-626, and freeU / Fourier_filter, :42-100.  The reference scales the skip
+ * feature by f, filters it over ALL N rows of the batch (FreeU) and merges it with the unpooled child.  Its 2-D FFT mask is
+ * constant along the channel frequencies and scales the row frequencies 0 and -1 by s, so that the real part it keeps is, per
+ * channel j and REFERENCE row m (theta_m = 2 pi m / N):
+ *   y[m][j] = x[m][j] + k (S0_j + A_j cos theta_m + B_j sin theta_m),        k = (float32(s) - 1) / N   (fp64, rounded once)
+ *   S0_j = sum_m x[m][j],   A_j = sum_m x[m][j] cos theta_m,   B_j = sum_m x[m][j] sin theta_m
+ * The operator is I + k P with P symmetric: the backward is the same two calls on the gradient.
+ *   ref_of_row (n) int32   physical row -> reference row (NULL = identity); its values enter arithmetic only.  n_total = N.
+ *   cdseg_skip_stats       stats (3 c doubles, on the device) = [S0 A B] of x: (n, c), fp32 or the build's 16-bit type
+ *                          (dtype), row stride ldx.  cos / sin in fp64 (sincospi(2 m / N)), sums in fp64 in an order fixed by
+ *                          (n, c) and the path: chunk b of cdseg_skip_partition owns rows_per_chunk consecutive rows (64 at
+ *                          least, 256 chunks at most), a lane adds its rows by ascending index, the row slots of a block by
+ *                          ascending slot, and a finish launch adds the chunk partials (in ws): by ascending chunk index
+ *                          inside each of 16 segments of ceil(chunks / 16) consecutive chunks, then the segment sums by
+ *                          ascending segment (one chain over 256 partials is bound by the latency of its loads).  No float
+ *                          atomics, no host read: equal inputs on the same path give equal bits.
+ *   cdseg_skip_fold        u (3 cout doubles) = [W S0, W A, W B] for a (cout, cin) matrix W (dtype, row stride ldw): what the
+ *                          filter adds behind a Linear that reads the filtered feature (proj_cat of the 'cat' mode).  fp64,
+ *                          fixed order.
+ *   cdseg_skip_merge       in place on the fp32 stream x (n, c), row stride ldx; every part may be absent:
+ *                            x[r][j] = f (x[r][j] + k (S0_j + A_j cos theta_r + B_j sin theta_r)) + child[cluster[r]][j]
+ *                            folded != 0 (stats holds u, x carries f already):
+ *                            x[r][j] = x[r][j] + f k (u0_j + u1_j cos theta_r + u2_j sin theta_r) + child[cluster[r]][j]
+ *                          stats NULL: f x + child[cluster]; child NULL (then cluster NULL): the scaled / filtered skip alone.
+ *                          Evaluated in fp64 from the fp32 operands, rounded to fp32 once.  child: fp32 (n_child, c), row
+ *                          stride ldchild; cluster (n) int32 in [0, n_child).
+ * Two paths, chosen per call: c a multiple of 4 with operands and row strides aligned for 4 elements per access (16 bytes of
+ * fp32, 8 of the 16-bit type), else a scalar path with the same arithmetic.  LDS only for the block's reduction, no scratch.
+ * Nothing outside stats / u / x and ws_bytes of ws is written.
+ * Status codes, checked before any launch; n = 0 returns CDSEG_OK without one:
+ *   CDSEG_ERR_UNSUPPORTED  c (cin, cout) outside [1, 512]; 2^31 rows or more.
+ *   CDSEG_ERR_ARG          a NULL x / stats / u / w; dtype neither CDSEG_F32 nor CDSEG_BF16; a row stride below the width; a
+ *                          pointer not aligned to its element (stats, u: 8 bytes; ws: 16); n < 0; n_total < n with a filter;
+ *                          folded without stats; child without cluster or with n_child <= 0, cluster without child; NaN f or s.
+ *   CDSEG_ERR_WORKSPACE    ws NULL or ws_bytes below the query. */
+int cdseg_skip_partition(long n, int c, long* rows_per_chunk, int* chunks);
+size_t cdseg_skip_stats_ws_bytes(long n, int c);
+int cdseg_skip_stats(const void* x, int dtype, int ldx, long n, int c, const int32_t* ref_of_row, long n_total, double* stats,
+                     void* ws, size_t ws_bytes, void* stream);
+int cdseg_skip_fold(const void* w, int dtype, int ldw, int cout, int cin, const double* stats, double* u, void* stream);
+int cdseg_skip_merge(float* x, int ldx, long n, int c, const double* stats, int folded, double s, long n_total, double f,
+                     const int32_t* ref_of_row, const float* child, int ldchild, const int32_t* cluster, long n_child, void* stream);
+
 /* ------------------------------------------------------------------ fused optimizer step (csrc/optim.hip)
  * ref: engines/train.py:216-271 (run_step: scaler.unscale_, clip_grad_norm_, scaler.step(optimizer)) on torch.optim.AdamW.
  * One tensor table describes the parameters; a work list cuts them into chunks of at most CDSEG_OPT_CHUNK elements (a
