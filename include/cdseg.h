@@ -89,7 +89,8 @@ int cdseg_sort_curves(const int64_t* codes, const int* rows, int count, long n, 
 int cdseg_invert_perm(const int32_t* perm, long n, int32_t* inv, void* stream);
 int cdseg_widen_i32(const int32_t* src, long n, int64_t* dst, void* stream);
 
-/* row gathers / scatters (rows of row_bytes % 4 == 0 bytes); idx < 0 gathers zeros / skips */
+/* row gathers / scatters (rows of row_bytes % 4 == 0 bytes); idx < 0 gathers zeros / skips.  cdseg_gather_i32 has NO sentinel:
+ * every idx entry names an element of src (a negative one is read out of bounds). */
 int cdseg_gather_rows(const void* src, const int32_t* idx, long n_out, int row_bytes, void* dst, void* stream);
 int cdseg_scatter_rows(const void* src, const int32_t* idx, long n_in, int row_bytes, void* dst, void* stream);
 int cdseg_gather_i32(const int32_t* src, const int32_t* idx, long n, int32_t* dst, void* stream);
@@ -101,7 +102,8 @@ int cdseg_plan_gather_grid(const void* grid, int grid_elem_bytes, const int32_t*
 /* ------------------------------------------------------------------ pooling structure
  * ref: ptv3.py:477-492 (code >> 3*depth, torch.unique, sort(cluster), idx_ptr, head).
  * On z-sorted points a cluster is a contiguous run: cluster ids are an inclusive scan of the
- * run-start flags, seg_start (count+1 entries) are the run starts, *count_dev the number of runs. */
+ * run-start flags, seg_start (count+1 entries) are the run starts, *count_dev the number of runs.  What seg_start holds behind
+ * those count+1 entries is undefined (cdseg_pool_levels: every row of seg_start likewise). */
 int cdseg_pool_level(const int64_t* zcode_sorted, long n, int shift_bits, int32_t* cluster, int32_t* seg_start,
                      int32_t* count_dev, void* ws, size_t ws_bytes, void* stream);
 /* All pooling levels of a scene in one flag / scan / finish pass (replaces one cdseg_pool_level per level).
@@ -178,6 +180,8 @@ int cdseg_slots_select(const int32_t* const* gidx_src, const int32_t* const* wid
  * epilogue: v = acc + bias; v = v*scale + shift (folded eval BatchNorm1d, ref: ptv3.py:1440);
  *           v = act(v); [out2 = v if out2_pre_add]; v += res; v += add_src[add_idx[m]];
  *           out[out_idx ? out_idx[m] : m] = v; [out2 = v otherwise]
+ *         out_idx[m] < 0: row m is written nowhere (neither out nor out2).  add_idx has no sentinel: every entry names a row
+ *         of add_src.
  * kvol <= 128 (k=5 stem: 125), K % 8 == 0. */
 typedef struct cdseg_gemm_args {
   const void* A;          /* (M, lda) a_dtype; with nbr: the gather source (rows indexed by nbr) */
@@ -325,7 +329,8 @@ int cdseg_gemv(const float* w, const float* b, const float* x, int n, int k, int
 int cdseg_randn(float* out, long n, uint64_t seed, uint64_t offset, void* stream);
 int cdseg_cast(const void* src, int src_dtype, void* dst, int dst_dtype, long n, void* stream);
 /* dst[i, 0:cpad] = cast(src[idx[i], 0:cin]), zero padded (idx NULL = identity): stem input rows in the
- * engine's point order, padded to a 16-byte multiple so the stem conv runs on the gathered GEMM */
+ * engine's point order, padded to a 16-byte multiple so the stem conv runs on the gathered GEMM.  No sentinel: every idx entry
+ * names a row of src. */
 int cdseg_gather_pad_cast(const float* src, int ld_src, const int32_t* idx, long n, int cin, int cpad, void* dst,
                           int dst_dtype, void* stream);
 /* DDIM update of the noise-branch input on a uniform timestep t (ref: default.py:192-214, dm_target="noise"):
@@ -379,7 +384,8 @@ int cdseg_max_run(const int32_t* seg_start, long m, int32_t* out_dev, void* stre
 /* fragment `frag`: idx_part[v] = idx_sort[seg_start[v] + frag % count_v].  ref: transform.py:862-864 */
 int cdseg_fragment_select(const int32_t* idx_sort, const int32_t* seg_start, long m, int frag, int32_t* idx_part,
                           void* stream);
-/* pred[idx[i], :] += softmax(logits[i, :]).  ref: engines/test.py:261-267 */
+/* pred[idx[i], :] += softmax(logits[i, :]).  ref: engines/test.py:261-267.  No sentinel and no atomics: every idx entry names a
+ * row of pred, no row twice (the members of one fragment). */
 int cdseg_softmax_vote(const float* logits, int ldl, const int32_t* idx, long m, int c, float* pred, int ldp,
                        void* stream);
 /* out[i] = first arg-max of row i.  ref: engines/test.py:278 */
@@ -469,7 +475,7 @@ int cdseg_knn1(const float* ref_xyz, const int32_t* ref_offset, long n, const fl
                long m, int nb, const float* origin, float cell, int32_t* idx, float* dist2, void* ws, size_t ws_bytes,
                void* stream);
 /* out (3,k) int64: per-class intersection, prediction and target counts over rows with target != ignore_index;
- * pred_idx (n) or NULL: row i is predicted pred[pred_idx[i]]. */
+ * pred_idx (n) or NULL: row i is predicted pred[pred_idx[i]] (no sentinel: every entry names an element of pred). */
 int cdseg_iou_counts(const int32_t* pred, const int32_t* pred_idx, const int32_t* target, long n, int k, int ignore_index,
                      int64_t* out, void* stream);
 

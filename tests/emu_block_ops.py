@@ -122,17 +122,25 @@ def gelu_bwd_cast(u, dg, variant=None):
 
 
 def train_block_forward(tb, n, x_in, x_conv, t_rows, scene_offs, mask1, mask2, nbr, gidx, widx, patch_start, patch_start_host,
-                        tape, scratch, x_out):
+                        tape, scratch, x_out, rows=None):
+    """rows = (row_vox (n), row_start (V + 1)): the row level of a Mix3D batch, as in csrc/trainblock.hip - the CPE (conv, Linear,
+    LayerNorm) runs on the first row of every voxel with `nbr` over the V voxels, and every row adds its voxel's term."""
     assert tb.derived is not None, "train_block_prepare has not run"
     P = [p.detach() for p in tb.params]
     c = tb.channels
     mmv = tb.variant if tb.mm_lp else None
     T = {}
-    T["xc"] = E.cast(x_conv, tb.t16()) if tb.mm_lp else x_conv
+    xv = x_conv if rows is None else x_conv[rows[1][:-1].long()]  # gather_first
+    T["xc"] = E.cast(xv, tb.t16()) if tb.mm_lp else xv
     T["yc"] = _lin(tb, T["xc"], 0, T["xc"].dtype, nbr=nbr)
     T["z"] = _lin(tb, T["yc"], 1)
     x0 = torch.empty_like(x_in)
-    E.layernorm(T["z"], P[4], P[5], x0, eps=tb.eps[0], res=x_in)
+    if rows is None:
+        E.layernorm(T["z"], P[4], P[5], x0, eps=tb.eps[0], res=x_in)
+    else:  # residual_rows: x + LN(z)[row_vox], then the timestep row below
+        pe = torch.empty_like(T["z"])
+        E.layernorm(T["z"], P[4], P[5], pe, eps=tb.eps[0])
+        x0.copy_(x_in + pe[rows[0].long()])
     if t_rows is not None:
         residual(x0, None, None, t_rows, scene_offs, out=x0)
     T["x0"] = x0
@@ -155,23 +163,24 @@ def train_block_forward(tb, n, x_in, x_conv, t_rows, scene_offs, mask1, mask2, n
 
 
 def train_block_backward(tb, n, x_in, x_conv, t_rows, scene_offs, mask1, mask2, nbr, gidx, widx, patch_start, patch_start_host,
-                         tape, scratch, x_out, dy, dx_in, dx_conv, dt_rows, slab):
+                         tape, scratch, x_out, dy, dx_in, dx_conv, dt_rows, slab, rows=None):
     T = _TAPES[tape.data_ptr()]
     P = [p.detach() for p in tb.params]
     c = tb.channels
     mmv = tb.variant if tb.mm_lp else None
     slab.zero_()
+    det = {"deterministic": True} if tb.deterministic else {}  # the fixed-order reductions, asked for as ops.det_kw does
     G = train_block_grad_views(tb, slab)
     op = (lambda t: t.to(tb.t16())) if tb.mm_lp else (lambda t: t)
     dhm = scale_cast(dy, mask2, mmv)
-    E.linear_wgrad(T["g"].float(), dhm.float(), G[16], G[17])
+    E.linear_wgrad(T["g"].float(), dhm.float(), G[16], G[17], **det)
     du = gelu_bwd_cast(T["u"], _dgrad(tb, dhm, 5), mmv)
-    E.linear_wgrad(T["h2"].float(), du.float(), G[14], G[15])
+    E.linear_wgrad(T["h2"].float(), du.float(), G[14], G[15], **det)
     dh2 = _dgrad(tb, du, 4)
     dx_in.copy_(dy)
-    E.layernorm_bwd(T["x1"], P[12], dh2, dx_in, accumulate=True, eps=tb.eps[2], dgamma=G[12], dbeta=G[13])
+    E.layernorm_bwd(T["x1"], P[12], dh2, dx_in, accumulate=True, eps=tb.eps[2], dgamma=G[12], dbeta=G[13], **det)
     da = scale_cast(dx_in, mask1, mmv)
-    E.linear_wgrad(T["o"].float(), da.float(), G[10], G[11])
+    E.linear_wgrad(T["o"].float(), da.float(), G[10], G[11], **det)
     do = _dgrad(tb, da, 3)
     if tb.attn_lp:
         do = do.to(tb.t16())
@@ -180,20 +189,34 @@ def train_block_backward(tb, n, x_in, x_conv, t_rows, scene_offs, mask1, mask2, 
     E.attention_bwd(q[:, :c], q[:, c:2 * c], q[:, 2 * c:], gidx, gidx, widx, patch_start, patch_start_host, tb.heads, tb.scale,
                     do.float(), dqkv[:, :c], dqkv[:, c:2 * c], dqkv[:, 2 * c:])
     dq = op(dqkv)
-    E.linear_wgrad(T["h1"].float(), dq.float(), G[8], G[9])
+    E.linear_wgrad(T["h1"].float(), dq.float(), G[8], G[9], **det)
     dh1 = _dgrad(tb, dq, 2)
-    E.layernorm_bwd(T["x0"], P[6], dh1, dx_in, accumulate=True, eps=tb.eps[1], dgamma=G[6], dbeta=G[7])
+    E.layernorm_bwd(T["x0"], P[6], dh1, dx_in, accumulate=True, eps=tb.eps[1], dgamma=G[6], dbeta=G[7], **det)
     if t_rows is not None:
         offs = [int(v) for v in scene_offs]
         dt_rows.copy_(torch.stack([dx_in[offs[b]:offs[b + 1]].sum(0) for b in range(len(offs) - 1)]))
-    dz = torch.empty_like(dx_in)
-    E.layernorm_bwd(T["z"], P[4], dx_in, dz, accumulate=False, eps=tb.eps[0], dgamma=G[4], dbeta=G[5])
+    dpe = dx_in
+    if rows is not None:  # run_sum: a voxel's term collects the gradients of its rows, in ascending row order
+        rs = [int(v) for v in rows[1]]
+        dpe = torch.zeros((len(rs) - 1, c), dtype=torch.float32)
+        for v in range(len(rs) - 1):
+            for i in range(rs[v], rs[v + 1]):
+                dpe[v] += dx_in[i]
+    dz = torch.empty_like(dpe)
+    E.layernorm_bwd(T["z"], P[4], dpe, dz, accumulate=False, eps=tb.eps[0], dgamma=G[4], dbeta=G[5], **det)
     dz = op(dz)
-    E.linear_wgrad(T["yc"].float(), dz.float(), G[2], G[3])
+    E.linear_wgrad(T["yc"].float(), dz.float(), G[2], G[3], **det)
     dyc = op(_dgrad(tb, dz, 1))
-    E.conv_wgrad(T["xc"].float(), nbr, dyc.float(), G[0].view(c, 27, c), G[1])
+    E.conv_wgrad(T["xc"].float(), nbr, dyc.float(), G[0].view(c, 27, c), G[1], **det)
     dxc = _dgrad(tb, dyc, 0, nbr=nbr)
-    if dx_conv is None:
+    if rows is not None:  # scatter_first: the conv read the first row of every voxel only
+        first = rows[1][:-1].long()
+        if dx_conv is None:
+            dx_in[first] += dxc
+        else:
+            dx_conv.zero_()
+            dx_conv[first] = dxc
+    elif dx_conv is None:
         dx_in += dxc
     else:
         dx_conv.copy_(dxc)

@@ -5,6 +5,7 @@ tests/emu_rows_ops.py's.  Tests set ``cdsegnet_amd.train_graph.ops`` and ``engin
 product."""
 import torch
 
+from cdsegnet_amd._lib import CdsegError
 from tests import emu_rows_ops
 
 
@@ -13,6 +14,8 @@ def __getattr__(name):  # every op this file does not define
 
 
 def fuse_gate_fwd(s, a, alpha, gamma, m=None, out=None):
+    if a is None and m is not None:  # (cdseg_fuse_gate_fwd: CDSEG_ERR_ARG before any launch)
+        raise CdsegError("fuse_gate_fwd failed: DropPath factors without the attention operand")
     y = alpha.double() * s.double()
     if a is not None:
         mm = 1.0 if m is None else m.double().reshape(-1, 1)

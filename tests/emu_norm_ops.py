@@ -1,20 +1,25 @@
 """TEST INFRASTRUCTURE: the PyTorch-CPU emulation of the ops of cdsegnet_amd/csrc/norm.hip (train-mode BatchNorm + GELU, the
-pooling maximum with its arg-max), same signatures as cdsegnet_amd.ops; everything else is tests/emu_ops.py's.  Tests set
+pooling maximum with its arg-max), same signatures as cdsegnet_amd.ops; everything else is tests/emu_rows_ops.py's (tests/emu_ops.py and the contiguous-run sum
+the deterministic training mode needs).  Tests set
 ``cdsegnet_amd.train_graph.ops`` (and ``engine.ops``) to this module.  Never imported by the product."""
 import math
 
 import torch
 import torch.nn.functional as F
 
-from tests import emu_ops
+from cdsegnet_amd._lib import CdsegError
+from tests import emu_rows_ops
 
 
 def __getattr__(name):  # every op this file does not define
-    return getattr(emu_ops, name)
+    return getattr(emu_rows_ops, name)
 
 
 def bn_partition(m, c):
-    """The launch rule of csrc/norm.hip restated: at most 256 blocks of at least 256 rows, a multiple of 64 beyond that."""
+    """The launch rule of csrc/norm.hip restated: at most 256 blocks of at least 256 rows, a multiple of 64 beyond that; like the
+    library, only for the kernels' widths (multiples of 16 up to 512) and m >= 0."""
+    if m < 0 or c < 16 or c > 512 or c % 16:
+        raise CdsegError(f"bn_partition failed: no kernel for ({m}, {c})")
     rpb = -(-m // 256)
     rpb = 256 if rpb < 256 else -(-rpb // 64) * 64
     return rpb, (-(-m // rpb) if m > 0 else 0)

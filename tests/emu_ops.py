@@ -16,6 +16,12 @@ F32, BF16 = 0, 1
 
 
 LP_DTYPES = {"bf16": torch.bfloat16, "f16": torch.float16}
+_POISON = -12345  # what an emulation writes where include/cdseg.h leaves a region undefined: host code that reads it fails here
+
+
+def _rows_named(what, idx, rows):
+    """An index list without a sentinel (include/cdseg.h): every entry names a row.  The kernel would read or write out of bounds."""
+    assert idx is None or idx.numel() == 0 or (int(idx.min()) >= 0 and int(idx.max()) < rows), f"{what}: an entry names no row"
 
 
 def is_lp(dtype):
@@ -35,8 +41,8 @@ def encode(grid, batch, depth, order):
     return torch.from_numpy(S.encode(grid.numpy(), None if batch is None else batch.numpy(), depth, name))
 
 
-def encode4(grid, batch, depth):
-    return torch.stack([encode(grid, batch, depth, o) for o in S.ORDERS])
+def encode4(grid_i32, batch_i32, depth):
+    return torch.stack([encode(grid_i32, batch_i32, depth, o) for o in S.ORDERS])
 
 
 def sort_pairs(keys, vals=None, end_bit=64):
@@ -57,8 +63,8 @@ def invert_perm(perm):
     return inv
 
 
-def widen(x):
-    return x.long()
+def widen(x_i32):
+    return x_i32.long()
 
 
 def gather_rows(src, idx):
@@ -74,20 +80,22 @@ def scatter_rows(src, idx, out):
 
 
 def gather_i32(src, idx):
+    _rows_named("gather_i32 idx", idx, src.numel())
     return src[idx.long()]
 
 
-def plan_gather_grid(grid, perm, zs, depth):
-    return grid[perm.long()].int(), (zs >> (3 * depth)).int()
+def plan_gather_grid(grid, perm, zcode_sorted, depth):
+    return grid[perm.long()].int(), (zcode_sorted >> (3 * depth)).int()
 
 
-def pool_level(zs, shift, count_out=None):
-    sh = zs >> shift
+def pool_level(zcode_sorted, shift_bits, count_out=None):
+    zs = zcode_sorted
+    sh = zs >> shift_bits
     flag = torch.ones_like(sh, dtype=torch.int32)
     flag[1:] = (sh[1:] != sh[:-1]).int()
     cluster = (torch.cumsum(flag, 0) - 1).int()
     m = int(cluster[-1]) + 1
-    seg = torch.full((len(zs) + 1,), -12345, dtype=torch.int32)
+    seg = torch.full((len(zs) + 1,), _POISON, dtype=torch.int32)
     seg[:m] = torch.nonzero(flag).flatten().int()
     seg[m] = len(zs)
     cnt = torch.tensor([m], dtype=torch.int32)
@@ -97,7 +105,8 @@ def pool_level(zs, shift, count_out=None):
     return cluster, seg, cnt
 
 
-def pool_levels(zs, shifts, last_idx):
+def pool_levels(zcode_sorted, shifts, last_idx):
+    zs = zcode_sorted
     cl, sg, meta = [], [], []
     for sh in shifts:
         c, s_, cnt = pool_level(zs, sh)
@@ -129,8 +138,8 @@ def coarse_orders(clusters, orders, sizes):
     return res
 
 
-def pool_gather(seg, m, n_fine, pd, grid_f, batch_f, code4_f):
-    h = seg[:m].long()
+def pool_gather(seg_start, m, n_fine, pooling_depth, grid_f, batch_f, code4_f):
+    h, pd = seg_start[:m].long(), pooling_depth
     return grid_f[h] >> pd, batch_f[h], code4_f[:, h] >> (3 * pd)
 
 
@@ -138,19 +147,20 @@ def pad_plan_batch(items, nb):
     return [pad_plan(o, a, b, k, n) for o, a, b, k, n in items]
 
 
-def nbr_table(zs, grid, batch, depth, ksize, kmajor=False):
-    t = torch.from_numpy(OM.subm_neighbors(grid.numpy(), batch.numpy(), ksize)).int()
+def nbr_table(zcode_sorted, grid_i32, batch_i32, depth, ksize, kmajor=False):
+    t = torch.from_numpy(OM.subm_neighbors(grid_i32.numpy(), batch_i32.numpy(), ksize)).int()
     return t.t().contiguous() if kmajor else t
 
 
-def nbr_table_from_parent(zs, grid, cluster, parent_nbr3, seg_start, m, depth, ksize, kmajor=False):
-    batch = (zs >> (3 * depth)).int()
-    return nbr_table(zs, grid, batch, depth, ksize, kmajor)
+def nbr_table_from_parent(zcode_sorted, grid_i32, cluster, parent_nbr3, seg_start, m, depth, ksize, kmajor=False):
+    batch = (zcode_sorted >> (3 * depth)).int()
+    return nbr_table(zcode_sorted, grid_i32, batch, depth, ksize, kmajor)
 
 
-def nbr_table_from_info(grid, cluster, parent_nbr3, cinfo, m, depth, ksize, kmajor=False):
+def nbr_table_from_info(grid_i32, cluster, parent_nbr3, child_info_words, m, depth, ksize, kmajor=False):
     """The kernel's own algebra (csrc/serialize.hip: nbr_from_info_kernel), so that the host-logic tests check the derivation
     end to end: target = first child + popcount(occupancy below the target's octant)."""
+    grid, cinfo = grid_i32, child_info_words
     g = grid.numpy().astype(np.int64)
     n, r, kv = len(g), ksize // 2, ksize ** 3
     pn, info, cl = parent_nbr3.numpy().astype(np.int64), cinfo.numpy().astype(np.int64), cluster.numpy().astype(np.int64)
@@ -202,7 +212,7 @@ def _act(v, act):
 
 def gemm(A, W, out, *, bias=None, scale=None, shift=None, act=ACT_NONE, res=None, add_src=None, add_idx=None,
          nbr=None, out_idx=None, out2=None, out2_pre_add=False, M=None, kvol=1, colbias=None, ln_pre=None,
-         ln_post=None, ln_out=None, ln_eps=1e-5, nbr_kmajor=False, cache=True):
+         nbr_kmajor=False, ln_post=None, ln_out=None, ln_eps=1e-5, cache=True):
     assert A.dtype == W.dtype
     Af, Wf = A.float(), W.float()
     if nbr is not None and nbr_kmajor:
@@ -223,31 +233,40 @@ def gemm(A, W, out, *, bias=None, scale=None, shift=None, act=ACT_NONE, res=None
     v = _act(v, act)
     if ln_pre is not None:
         v = F.layer_norm(v, (v.shape[1],), ln_pre[0], ln_pre[1], ln_eps)
+    live = None if out_idx is None else out_idx >= 0  # out_idx[m] < 0: row m is written nowhere (out, out2)
+
+    def put2(val):
+        if live is None:
+            out2.copy_(val.to(out2.dtype))
+        else:
+            out2[live] = val[live].to(out2.dtype)
     if out2 is not None and out2_pre_add:
-        out2.copy_(v.to(out2.dtype))
+        put2(v)
     if res is not None:
         v = v + res
     if colbias is not None:
         v = v + colbias
     if add_src is not None:
+        _rows_named("gemm add_idx", add_idx, add_src.shape[0])
         v = v + add_src[add_idx.long()]
     if out_idx is not None:
-        out[out_idx.long()] = v.to(out.dtype)
+        _rows_named("gemm out_idx", out_idx[live], out.shape[0])
+        out[out_idx[live].long()] = v[live].to(out.dtype)
     else:
         out.copy_(v.to(out.dtype))
     if out2 is not None and not out2_pre_add:
-        out2.copy_(v.to(out2.dtype))
+        put2(v)
     if ln_post is not None:
         ln_out.copy_(F.layer_norm(v, (v.shape[1],), ln_post[0], ln_post[1], ln_eps).to(ln_out.dtype))
     return out
 
 
 def stem5_ok(cout, dtype):
-    return cout == 32 and dtype == torch.bfloat16
+    return cout == 32 and is_lp(dtype)
 
 
-def child_info(zs, seg, m):
-    zs, seg = zs.long(), seg.long()
+def child_info(zcode_sorted, seg_start, m):
+    zs, seg = zcode_sorted.long(), seg_start.long()
     info = torch.zeros(int(m), dtype=torch.int64)
     for p in range(int(m)):
         occ = 0
@@ -290,7 +309,9 @@ def stem5(x8, wimg, scale, shift, grid, cluster, parent_nbr3, cinfo, depth, out,
 
 
 def subm_conv3_ok(x):
-    return x.dtype == torch.bfloat16 and x.dim() == 2 and x.shape[1] in (32, 64)
+    n = x.shape[0]
+    return (is_lp(x.dtype) and x.dim() == 2 and x.shape[1] in (32, 64) and x.stride(0) == x.shape[1] and
+            n * 27 * 4 < 2 ** 31 and n * x.shape[1] * 2 < 2 ** 31 - 65536)
 
 
 def subm_conv3_pack(w):
@@ -306,7 +327,7 @@ DEEP_CHANNELS = (128, 256, 512)
 
 
 def block_rr_ok(channels, dtype):
-    return dtype == torch.bfloat16 and (channels in (32, 64) or channels in DEEP_CHANNELS)
+    return is_lp(dtype) and (channels in (32, 64) or channels in DEEP_CHANNELS)
 
 
 def block_rr_head_on(channels=32):
@@ -326,39 +347,39 @@ def attn_tail_rr(o, tail_img, bp, ln_g, ln_b, b1, b2, x, xc=None, eps=1e-5):
 
 
 def cpe_head_fused_ok(y):
-    return y.dtype == torch.bfloat16 and y.shape[1] in (32, 64)
+    return is_lp(y.dtype) and y.shape[1] in (32, 64)
 
 
 def cpe_head_fused(y, wl, bl, lnp, x, colbias, ln1, wqkv, bqkv, qkv, eps=1e-5, qkv_flags=0):
-    # (qkv_flags = ATTN_V_BF16 only matters in the IEEE-half build; the emulation's 16-bit type is bfloat16)
+    # (qkv_flags = ATTN_V_BF16 only matters in the IEEE-half build: the emulation keeps one 16-bit type, y's, throughout)
     c = x.shape[1]
     v = F.layer_norm(y.float() @ wl.float().t() + bl, (c,), lnp[0], lnp[1], eps)
     x += v
     if colbias is not None:
         x += colbias
-    h = F.layer_norm(x, (c,), ln1[0], ln1[1], eps).to(torch.bfloat16)
+    h = F.layer_norm(x, (c,), ln1[0], ln1[1], eps).to(y.dtype)
     qkv.copy_((h.float() @ wqkv.float().t() + bqkv).to(qkv.dtype))
     return qkv
 
 
 def attn_tail_fused_ok(o, hidden):
     c = o.shape[1]
-    return o.dtype == torch.bfloat16 and c in (32, 64) and hidden == 4 * c
+    return is_lp(o.dtype) and c in (32, 64) and hidden == 4 * c
 
 
 def attn_tail_fused(o, wp, bp, ln_g, ln_b, w1, b1, w2, b2, x, xc=None, eps=1e-5):
     x += o.float() @ wp.float().t() + bp
-    h = F.layer_norm(x, (x.shape[1],), ln_g, ln_b, eps).to(torch.bfloat16)
+    h = F.layer_norm(x, (x.shape[1],), ln_g, ln_b, eps).to(o.dtype)
     return mlp_fused(h, w1, b1, w2, b2, x, xc)
 
 
 def mlp_fused_ok(h, hidden):
     c = h.shape[1]
-    return h.dtype == torch.bfloat16 and c in (32, 64, 128) and hidden == 4 * c
+    return is_lp(h.dtype) and c in (32, 64, 128) and hidden == 4 * c
 
 
 def mlp_fused(h, w1, b1, w2, b2, x, xc=None):
-    u = F.gelu(h.float() @ w1.float().t() + b1).to(torch.bfloat16)
+    u = F.gelu(h.float() @ w1.float().t() + b1).to(h.dtype)
     x += u.float() @ w2.float().t() + b2
     if xc is not None:
         xc.copy_(x.to(xc.dtype))
@@ -429,9 +450,17 @@ def gemv(w, b, x, act=ACT_NONE):
     return _act(w @ x + b, act)
 
 
-def randn(shape, seed, offset, device):
-    g = torch.Generator().manual_seed((seed + offset) & 0x7FFFFFFF)
-    return torch.randn(shape, generator=g)
+def randn(shape, seed, offset, device, out=None):
+    """The device generator's stream (Philox4x32-10 keyed by seed, counter offset, Box-Muller: oracle/philox.py), so that
+    (seed, offset) is a pair as on the device; `out`: filled in place and returned."""
+    from oracle import philox
+    n = int(np.prod(tuple(shape), dtype=np.int64))
+    v = torch.from_numpy(philox.randn(n, int(seed) & (2 ** 64 - 1), int(offset)).copy()).reshape(tuple(shape))
+    if out is None:
+        return v
+    assert tuple(out.shape) == tuple(shape) and out.dtype == torch.float32 and out.is_contiguous()
+    out.copy_(v)
+    return out
 
 
 def cast(src, dtype):
@@ -439,6 +468,7 @@ def cast(src, dtype):
 
 
 def gather_pad_cast(src, idx, cpad, dtype):
+    _rows_named("gather_pad_cast idx", idx, src.shape[0])
     rows = src if idx is None else src[idx.long()]
     out = torch.zeros(rows.shape[0], cpad)
     out[:, :src.shape[1]] = rows
@@ -523,6 +553,7 @@ def fragment_select(idx_sort, seg_start, m, frag):
 
 
 def softmax_vote(logits, idx, pred):
+    _rows_named("softmax_vote idx", idx, pred.shape[0])
     pred[idx.long()] += torch.softmax(logits.float(), -1)
     return pred
 
@@ -547,6 +578,7 @@ def knn1(ref_xyz, ref_offset, qry_xyz, qry_offset, origin, cell, want_dist=False
 
 
 def iou_counts(pred, target, num_classes, ignore_index=-1, pred_idx=None):
+    _rows_named("iou_counts pred_idx", pred_idx, pred.numel())
     p = pred.long() if pred_idx is None else pred.long()[pred_idx.long()]
     t = target.long()
     keep = t != ignore_index
@@ -576,7 +608,8 @@ def attention_bwd(q, k, v, q_gidx, kv_gidx, widx, patch_start, patch_start_host,
     dv += vv.grad
 
 
-def layernorm_bwd(x, gamma, dy, dx, accumulate=False, eps=1e-5, dgamma=None, dbeta=None):
+def layernorm_bwd(x, gamma, dy, dx, accumulate=False, eps=1e-5, dgamma=None, dbeta=None, deterministic=False):
+    """deterministic: accepted, a no-op here - torch's CPU sums run in a fixed order already."""
     with torch.enable_grad():
         xr = x.detach().clone().requires_grad_(True)
         g = gamma.detach().clone().requires_grad_(True)
@@ -600,7 +633,13 @@ def gelu_bwd(u, dy):
     return ur.grad
 
 
-def linear_wgrad(x, dy, dw, db=None, xidx=None):
+def linear_wgrad(x, dy, dw, db=None, xidx=None, deterministic=False):
+    """deterministic: accepted, a no-op here - torch's CPU sums run in a fixed order already."""
+    return _linear_wgrad(x, dy, dw, db, xidx)
+
+
+def _linear_wgrad(x, dy, dw, db=None, xidx=None):
+    x, dy = x.float(), dy.float()  # 16-bit operands: exact products, fp32 sums (never a 16-bit matmul)
     if xidx is None:
         dw += dy.t() @ x
     else:
@@ -611,9 +650,10 @@ def linear_wgrad(x, dy, dw, db=None, xidx=None):
     return dw
 
 
-def conv_wgrad(x, nbr_kmajor, dy, dw3, db=None):
+def conv_wgrad(x, nbr_kmajor, dy, dw3, db=None, deterministic=False):
+    """deterministic: accepted, a no-op here like `linear_wgrad`'s."""
     for o in range(nbr_kmajor.shape[0]):
-        linear_wgrad(x, dy, dw3[:, o, :], None, xidx=nbr_kmajor[o])
+        _linear_wgrad(x, dy, dw3[:, o, :], None, xidx=nbr_kmajor[o])
     if db is not None:
-        db += dy.sum(0)
+        db += dy.float().sum(0)
     return dw3

@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE: what the PyTorch-CPU emulation of the op layer (tests/emu_ops.py) lacks for test-time voting on shared
 geometry (cdsegnet_amd.engine: Level.slots on a tuple of curves, per-fragment device noise): the element-wise composition of
-slot plans behind cdseg_slots_select, and `randn` into a row slice.  Every other op is tests/emu_ops.py's.  Tests set
+slot plans behind cdseg_slots_select.  Every other op is tests/emu_ops.py's (`randn` into a row slice among them).  Tests set
 ``cdsegnet_amd.engine.ops`` to this module.  Never imported by the product."""
 import torch
 
@@ -22,11 +22,3 @@ def slots_select(sources, offs_pad, choice, n_pad):
         assert sources[c] is not None, "a chosen source must exist"
         gidx[a:e], widx[a:e] = sources[c][0][a:e], sources[c][1][a:e]
     return gidx, widx
-
-
-def randn(shape, seed, offset, device, out=None):
-    v = emu_ops.randn(shape, seed, offset, device)
-    if out is None:
-        return v
-    out.copy_(v)
-    return out

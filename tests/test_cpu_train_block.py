@@ -207,13 +207,14 @@ def test_bytes_is_a_function_of_the_shape(c, heads, hidden):
 
 
 # ------------------------------------------------------------------------------------------ the step on the emulated ops
-def _mini(monkeypatch):
+def _mini(monkeypatch, emu_name="emu_block_ops"):
     import cdsegnet_amd.engine as engine
     import cdsegnet_amd.train_graph as tg
     from cdsegnet_amd import configs
     from cdsegnet_amd.param_init import fill_state_dict
     from cdsegnet_amd.registry import build_model
-    from tests import emu_block_ops
+    import importlib
+    emu_block_ops = importlib.import_module("tests." + emu_name)  # (the default: the emulated native Block and what it falls back to)
     from tests.helpers import load_fixture
     monkeypatch.setattr(engine, "ops", emu_block_ops)
     monkeypatch.setattr(tg, "ops", emu_block_ops)
@@ -309,3 +310,50 @@ def test_prepare_runs_once_per_weight_version_on_the_emulation(monkeypatch):
     opt.step()                             # an in-place weight change between forward and backward raises
     with pytest.raises(RuntimeError, match="modified by an inplace operation"):
         loss.backward()
+
+
+@pytest.mark.parametrize("mode,emu_name", [("autograd", "emu_rows_ops"), ("native", "emu_block_ops")])
+def test_deterministic_step_runs_on_the_emulated_ops_and_the_keyword_travels(monkeypatch, mode, emu_name):
+    """`train_deterministic = True` on the emulated layer (autograd Blocks on tests/emu_rows_ops.py, whose `segment_sum` the
+    deterministic gather backward needs; native Blocks on tests/emu_block_ops.py): every gradient reduction of the step (`linear_wgrad`, `conv_wgrad`,
+    `layernorm_bwd`) receives `deterministic=True`, none of them receives the keyword in the default mode (ops.det_kw: the
+    default call is what it was).  The keyword itself changes nothing here (a fixed-order torch sum is deterministic already),
+    but the mode also takes the gather backward through `segment_sum`, another summation order: loss and gradients of the
+    two modes agree by the metric and bound of the whole-step comparison above (1e-5 of the loss, 1e-3 per tensor)."""
+    from tests import emu_ops
+    model, inp, draws, emu = _mini(monkeypatch, emu_name)
+    model.train_block = mode
+    state = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    seen = []
+
+    def spy(name):
+        fn = getattr(emu_ops, name)
+
+        def wrapped(*a, **k):
+            seen.append((name, k.get("deterministic", "absent")))
+            return fn(*a, **k)
+        monkeypatch.setattr(emu_ops, name, wrapped)
+
+    for name in ("linear_wgrad", "conv_wgrad", "layernorm_bwd"):
+        spy(name)
+
+    def run(det):
+        model.load_state_dict(state)
+        model.zero_grad(set_to_none=True)
+        model.train_deterministic = det
+        seen.clear()
+        out = model(inp, draws={**draws, "masks": {k: list(v) for k, v in draws["masks"].items()}})
+        out["loss"].backward()
+        return float(out["loss"].detach()), {k: p.grad.detach().clone() for k, p in model.named_parameters() if p.grad is not None}, list(seen)
+
+    l0, g0, s0 = run(False)
+    l1, g1, s1 = run(True)
+    assert {n for n, _ in s0} == {n for n, _ in s1} == {"linear_wgrad", "conv_wgrad", "layernorm_bwd"}
+    assert len(s0) == len(s1) and all(d == "absent" for _, d in s0) and all(d is True for _, d in s1)
+    assert set(g0) == set(g1) and len(g1) == 508 and abs(l0 - l1) <= 1e-5 * abs(l0)
+    top = max(float(g.abs().max()) for g in g0.values())
+    per = {k: float((g0[k] - g1[k]).abs().max()) / (float(g0[k].abs().max()) + 1e-3 * top) for k in g0}
+    worst = max(per, key=per.get)
+    print(f"[measure] emulated {mode} step, deterministic vs default: loss {l0:.8f} / {l1:.8f}, worst gradient difference "
+          f"{per[worst]:.3e} ({worst})")
+    assert per[worst] < 1e-3
