@@ -207,6 +207,7 @@ SIGNATURES = {
                            c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "cdseg_iou_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p]),
     "cdseg_gemm": (c_int, [POINTER(GemmArgs), c_void_p]),
+    "cdseg_gemm_ws_bytes": (c_size_t, [c_long, c_int, c_int, c_int]),
     "cdseg_mlp_fused": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                 c_long, c_int, c_int, c_void_p]),
     "cdseg_attn_tail_fused": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,

@@ -32,6 +32,7 @@
 #include "common.h"
 #include "prof.h"
 #include "route.h"
+#include "workspace.h"
 
 // row-count window in which a C = 128 sparse conv takes the 8-wave 256 x 128 tile (MIN 0 = never).  Measured
 // (tools/bench_conv.py 2 <scenes>, profiles/r05_conv128.txt): 14 k rows (one scene) 42.2 -> 37.2 us, but 114 k rows (8 scenes)
@@ -1561,6 +1562,12 @@ int launch(const GemmP& p, size_t ws_bytes, hipStream_t s) {
 }
 
 }  // namespace
+
+// The workspace launch_bn's plan above expects for one GEMM (the rule and its constants: workspace.h)
+extern "C" size_t cdseg_gemm_ws_bytes(long M, int N, int gathered, int fused_ln) {
+  if (M <= 0 || N <= 0) return 0;
+  return gemm_ws_rule(M, N, N, gathered != 0, fused_ln != 0);
+}
 
 extern "C" int cdseg_gemm(const cdseg_gemm_args* a, void* stream) {
   if (!a || !a->A || !a->W || !a->out) return CDSEG_ERR_ARG;

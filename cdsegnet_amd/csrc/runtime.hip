@@ -3,31 +3,18 @@
 // attention, proj, fc1, fc2 + their second-pass kernels): issues all launches of the block
 // from C++ so the Python binding pays one call instead of ~10 (the per-launch host cost of the
 // binding, ~10 us, was the step's critical path once the kernels were fast).
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
 #include "common.h"
 #include "deep.h"
+#include "workspace.h"
 
 namespace {
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-struct Carver {
-  char* base;
-  size_t off, cap;
-  void* take(size_t bytes) {
-    off = align_up(off, 256);
-    void* p = base ? base + off : nullptr;
-    off += bytes;
-    return p;
-  }
-};
-
 constexpr int FUSE_LN_MAX_C = 512;  // widest row one GEMM block finishes (LayerNorm fused into the epilogue)
-constexpr size_t SPLITK_WS_CAP = (size_t)64 << 20;
 
-inline size_t esz(int dtype) { return dtype == CDSEG_BF16 ? 2 : 4; }
 // storage type of a descriptor's activations / weights: CDSEG_F32X3 is fp32 in memory (split-half arithmetic, gemm.hip)
 inline int storage_dtype(int dtype) { return dtype == CDSEG_F32X3 ? CDSEG_F32 : dtype; }
 
@@ -37,7 +24,7 @@ struct Layout {
 };
 
 Layout carve(const cdseg_block_desc* d, long n, void* scratch) {
-  Carver c{(char*)scratch, 0, 0};
+  Carver c{(char*)scratch, 0};
   const size_t e = esz(d->dtype);
   const size_t C = d->channels;
   Layout L;
@@ -47,17 +34,10 @@ Layout carve(const cdseg_block_desc* d, long n, void* scratch) {
   L.o = c.take(n * C * e);
   L.u = c.take(n * (size_t)d->hidden * e);
   L.y2 = d->channels > FUSE_LN_MAX_C ? c.take(n * C * 4) : nullptr;
-  // partial tiles: needed by any GEMM of the block whose output has few tiles (the narrowest is N = C) for split-K,
-  // and by the LayerNorm-fused GEMMs whose rows span several column tiles (C > 128)
-  const long tiles = ((n + 63) / 64) * (((long)C + 127) / 128);
-  L.ws_bytes = tiles < 256 ? (size_t)32 * n * (size_t)(3 * C > (size_t)d->hidden ? 3 * C : d->hidden) * 4
-                           : (C > 128 ? (size_t)n * C * 4 : 0);
-  // the deep sparse convs (C >= 256: 128 x 256 tiles, one block per CU) split K while their grid is below 256 blocks
-  if (C >= 256 && ((n + 127) / 128) * (((long)C + 255) / 256) < 256) {
-    const size_t want = (size_t)8 * n * C * 4;
-    if (want > L.ws_bytes) L.ws_bytes = want;
-  }
-  if (L.ws_bytes > SPLITK_WS_CAP) L.ws_bytes = SPLITK_WS_CAP;
+  // one GEMM workspace for the whole Block (workspace.h): the plain and LayerNorm-fused products are gated by the narrowest
+  // (N = C) and sized for the widest (qkv or fc1); the sparse conv (N = C, gathered) may want its deep-conv planes on top
+  const long wide = std::max<long>(3 * C, d->hidden);
+  L.ws_bytes = std::min(GEMM_WS_CAP, std::max(gemm_ws_rule(n, C, wide, false, true), gemm_ws_rule(n, C, C, true, false)));
   L.ws = L.ws_bytes ? c.take(L.ws_bytes) : nullptr;
   // deep stages: the residual rows between the fused head and the fused tail live here (head reads x, writes xs; tail reads
   // xs, writes x), which lets the few-row launches split a tile over several workgroups (deep.hip, cdseg_*_rr2)

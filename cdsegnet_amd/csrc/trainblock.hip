@@ -13,16 +13,14 @@
 #include <cstring>
 
 #include "common.h"
+#include "workspace.h"
 
 namespace {
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-inline size_t esz(int dtype) { return dtype == CDSEG_BF16 ? 2 : 4; }
 
 constexpr int ROW_BLOCK = 256;
 constexpr long ROW_MAX_BLOCKS = 4096;
-constexpr size_t SPLITK_WS_CAP = (size_t)64 << 20;
 
 inline unsigned row_grid(long items) {
   long b = (items + ROW_BLOCK - 1) / ROW_BLOCK;
@@ -410,18 +408,7 @@ __global__ void derive_kernel(DeriveP p) {
   }
 }
 
-// ---------------------------------------------------------------- layouts (host, functions of the shape only)
-struct Carver {
-  char* base;
-  size_t off;
-  void* take(size_t bytes) {
-    off = align_up(off, 256);
-    void* p = base ? base + off : nullptr;
-    off += bytes;
-    return p;
-  }
-};
-
+// ---------------------------------------------------------------- layouts (host, functions of the shape only; workspace.h)
 // the six matrices: (out, in) with in = 27 * C for the conv
 enum { M_CONV = 0, M_CPE, M_QKV, M_PROJ, M_FC1, M_FC2, M_COUNT };
 const int MAT_PARAM[M_COUNT] = {CDSEG_TB_CONV_W, CDSEG_TB_CPE_W, CDSEG_TB_QKV_W, CDSEG_TB_PROJ_W, CDSEG_TB_FC1_W, CDSEG_TB_FC2_W};
@@ -485,13 +472,6 @@ Tape carve_tape(const cdseg_train_block_desc* d, long n, void* base) {
   return T;
 }
 
-inline size_t gemm_ws_bytes(long m, long N, bool conv) {  // the rule of ops.gemm
-  size_t b = 0;
-  if (((m + 63) >> 6) * ((N + 127) >> 7) < 256) b = (size_t)32 * m * N * 4;
-  else if (conv && N >= 256 && ((m + 127) >> 7) * ((N + 255) >> 8) < 256) b = (size_t)8 * m * N * 4;
-  return b > SPLITK_WS_CAP ? SPLITK_WS_CAP : b;
-}
-
 struct Scratch {
   void *ws, *f0, *f1, *h0, *aux;
   size_t ws_bytes, aux_bytes, total;
@@ -505,7 +485,7 @@ Scratch carve_scratch(const cdseg_train_block_desc* d, long n, long slots, void*
   S.ws_bytes = 0;
   const long widths[3] = {C, 3 * C, H};
   for (long w : widths) {
-    const size_t b = gemm_ws_bytes(n, w, w == C);
+    const size_t b = gemm_ws_rule(n, w, w, w == C, false);  // (N = C: the sparse conv, gathered; no GEMM here fuses a LayerNorm)
     if (b > S.ws_bytes) S.ws_bytes = b;
   }
   S.ws = S.ws_bytes ? c.take(S.ws_bytes) : nullptr;
@@ -614,7 +594,7 @@ int gemm(const cdseg_train_block_desc* d, const Scratch& S, long n, const void* 
   a.out_dtype = out_dtype;
   a.nbr = nbr; a.nbr_kmajor = nbr ? 1 : 0;
   a.ln_eps = 1e-5f;
-  const size_t want = gemm_ws_bytes(n, N, nbr != nullptr);
+  const size_t want = gemm_ws_rule(n, N, N, nbr != nullptr, false);
   if (want && S.ws) { a.ws = S.ws; a.ws_bytes = S.ws_bytes; }
   return cdseg_gemm(&a, stream);
 }

@@ -39,6 +39,7 @@ def is_lp(dtype):
 
 
 _WS = {}
+_GEMM_WS_BYTES = {}  # (m, N, gathered, fused LayerNorm) -> cdseg_gemm_ws_bytes
 
 
 class _LazyLib:
@@ -688,15 +689,15 @@ def gemm(A, W, out, *, bias=None, scale=None, shift=None, act=ACT_NONE, res=None
     else:
         a.ln_post_g = a.ln_post_b = a.ln_out = None
     a.ln_eps = float(ln_eps)
-    if ((m + 63) >> 6) * ((a.N + 127) >> 7) < 256:  # split-K partials: only when the output has few tiles
-        ws = workspace(min(32 * m * a.N * 4, 64 << 20), out.device)
-        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel()
-    elif nbr is not None and a.N >= 256 and ((m + 127) >> 7) * ((a.N + 255) >> 8) < 256:
-        # deep sparse convs run 128 x 256 tiles, one block per CU: split-K while that grid is below one round of the chip
-        ws = workspace(min(8 * m * a.N * 4, 64 << 20), out.device)
-        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel()
-    elif a.N > 128 and (ln_pre is not None or ln_post is not None):  # rows over several column tiles
-        ws = workspace(m * a.N * 4, out.device)
+    # cdseg_gemm_ws_bytes (the rule lives beside the launch plan it feeds, csrc/workspace.h), one lookup per repeated shape
+    wkey = (m, a.N, nbr is not None, ln_pre is not None or ln_post is not None)
+    want = _GEMM_WS_BYTES.get(wkey)
+    if want is None:
+        if len(_GEMM_WS_BYTES) > 4096:
+            _GEMM_WS_BYTES.clear()
+        want = _GEMM_WS_BYTES[wkey] = int(_lib.load().cdseg_gemm_ws_bytes(*wkey))
+    if want:
+        ws = workspace(want, out.device)
         a.ws, a.ws_bytes = ws.data_ptr(), ws.numel()
     else:
         a.ws, a.ws_bytes = None, 0

@@ -202,8 +202,11 @@ typedef struct cdseg_gemm_args {
   int a_dtype, compute_dtype, out_dtype, out2_dtype;
   int act;
   int out2_pre_add;
-  void* ws;        /* optional split-K workspace (fp32 partial tiles) or NULL: used when M is small */
-  size_t ws_bytes; /*   and K long (deep stages); results are deterministic either way */
+  void* ws;        /* fp32 partial tiles, 16-byte aligned, sized by cdseg_gemm_ws_bytes (0: pass NULL).  The workspace chooses */
+  size_t ws_bytes; /*   the plan: without one there is no split-K (few-tile, long-K launches of the deep stages run unsplit),
+                    *   and a fused LayerNorm over several column tiles (N > 128), which needs M * N * 4 bytes, is
+                    *   CDSEG_ERR_WORKSPACE; a smaller ws_bytes is legal for split-K and lowers the slice count to the
+                    *   (M, N) planes that fit.  Results are deterministic for a given ws_bytes. */
   /* fused row LayerNorm (N <= 128; ref: nn.LayerNorm eps 1e-5 at ptv3.py:365,367,381):
    *   v = act(acc + bias);  if ln_pre:  v = LN(v) * ln_pre_g + ln_pre_b      (CPE, ptv3.py:401-404)
    *   v += res + colbias (+ add_src);  out = v;  if ln_post: ln_out = LN(v) * ln_post_g + ln_post_b */
@@ -218,6 +221,10 @@ typedef struct cdseg_gemm_args {
   int nbr_kmajor;         /* neighbour table is offset-major (kvol, M): coalesced index loads, cheaper to build */
 } cdseg_gemm_args;
 int cdseg_gemm(const cdseg_gemm_args* args_host, void* stream);
+/* The workspace cdseg_gemm's launch plan expects for M x N (gathered: nbr != NULL; fused_ln: ln_pre_g or ln_post_g set): the
+ * split-K planes of a launch with few output tiles, or the one plane of a fused LayerNorm with N > 128; 0 = pass NULL.  A
+ * function of the shape only (host code, no device needed). */
+size_t cdseg_gemm_ws_bytes(long M, int N, int gathered, int fused_ln);
 
 /* ------------------------------------------------------------------ LayerNorm
  * out = [res +] LayerNorm(x) * gamma + beta [+ colbias]; optional second copy out2.

@@ -11,6 +11,10 @@ bytes.  Every test here
 A workspace the kernel only partly initialises also shows here: the exact view starts as 0xA5 bytes, not as whatever an earlier
 launch left behind.
 
+cdseg_gemm's workspace is sized by cdseg_gemm_ws_bytes like the others, but it also runs with less (fewer split-K slices) and
+the size chooses the launch plan: its tests cover the query's three branches through the wrapper (with the recorded route)
+and explicit smaller workspaces through the C entry point.
+
 ops.workspace is replaced for the inference wrappers, ops._scratch (the one place the training wrappers, the packed images and
 the plan arenas allocate from) for the rest.  The test id names the entry point(s).
 """
@@ -197,7 +201,8 @@ def _gemm_case(M, N, K, dtype, seed):
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("M,N,K", [(300, 512, 512), (65, 2048, 512), (100, 128, 4096)])
 def test_cdseg_gemm_split_k_through_the_wrapper_at_the_requested_bytes(ops, dtype, M, N, K):
-    """ops.gemm asks for min(32 M N 4, 64 MiB): the split-K partial planes (splits, M, N) fp32 stay inside exactly that."""
+    """ops.gemm asks for cdseg_gemm_ws_bytes(M, N, 0, 0) = min(32 M N 4, 64 MiB): the split-K partial planes (splits, M, N)
+    fp32 stay inside exactly that."""
     A, W, b = _gemm_case(M, N, K, dtype, M + N + K)
     Ad, Wd, bd = dev(A, dtype), dev(W, dtype), dev(b)
 
@@ -206,9 +211,68 @@ def test_cdseg_gemm_split_k_through_the_wrapper_at_the_requested_bytes(ops, dtyp
         ops.gemm(Ad, Wd, out, bias=bd, cache=False)
         return out
 
-    _exact_vs_today(ops, run, sizes=[min(32 * M * N * 4, 64 << 20)])
+    size = _lib.load().cdseg_gemm_ws_bytes(M, N, 0, 0)
+    assert size == min(32 * M * N * 4, 64 << 20)
+    _exact_vs_today(ops, run, sizes=[size])
     err = (run().cpu().double() - (A.double() @ W.double().t() + b.double())).abs().max().item()
     assert err < (2e-5 * K ** 0.5 + 1e-5)  # the bound of test_gemm_split_k / test_gemm_plain
+
+
+@LPS
+def test_cdseg_gemm_deep_conv_through_the_wrapper_at_cdseg_gemm_ws_bytes(ops, lp):
+    """The second branch of the size rule: a gathered 16-bit GEMM whose 64 x 128 tiles fill the chip (256 of them) while its
+    256 x 256 tiles do not (32).  M = 8192, N = K = 256, 27 offsets on a synthetic kernel map: the wrapper asks for the
+    query's 8 M N 4 bytes (= 64 MiB), the launch splits K 256 / 32 = 8 ways and its 8 planes fill exactly that."""
+    M, C, bf = 8192, 256, LP()
+    g = torch.Generator().manual_seed(M + C)
+    nbr = torch.where(torch.rand(27, M, generator=g) > 0.5, torch.randint(0, M, (27, M), generator=g), torch.full((27, M), -1)).int()
+    xd = dev(torch.randn(M, C, generator=g), bf)
+    wd = dev(torch.randn(C, 27 * C, generator=g) / (13 * C) ** 0.5, bf)
+    bd, nd = dev(torch.randn(C, generator=g)), dev(nbr)
+    splits = []
+
+    def run():
+        out = torch.full((M, C), float("nan"), dtype=torch.float32, device="cuda")
+        with ops.record_routes() as rr:
+            ops.gemm(xd, wd, out, bias=bd, nbr=nd, nbr_kmajor=True, kvol=27, cache=False)
+        splits.append([r.splits for r in rr.routes])
+        return out
+
+    size = _lib.load().cdseg_gemm_ws_bytes(M, C, 1, 0)
+    assert size == 8 * M * C * 4 and _lib.load().cdseg_gemm_ws_bytes(M, C, 0, 0) == 0
+    ex = _exact_vs_today(ops, run, sizes=[size])
+    assert [b.nbytes for b in ex.served] == [size]
+    assert splits == [[8], [8]], splits  # today's allocation and the exact view: the same plan
+
+
+def test_cdseg_gemm_fused_layernorm_through_the_wrapper_at_cdseg_gemm_ws_bytes(ops):
+    """The third branch: fp32, ln_post over N = 256 (two column tiles), M = 16384 - 512 tiles of 64 x 128, so no split-K: the
+    wrapper asks for the query's one plane M N 4 and the row finish runs inside exactly that."""
+    M, N, K = 16384, 256, 256
+    A, W, b = _gemm_case(M, N, K, torch.float32, M + N + K)
+    g = torch.Generator().manual_seed(7)
+    Ad, Wd, bd, res = dev(A), dev(W), dev(b), dev(torch.randn(M, N, generator=g))
+    g2, b2 = dev(1 + 0.1 * torch.randn(N, generator=g)), dev(0.1 * torch.randn(N, generator=g))
+    routes = []
+
+    def run():
+        out = torch.full((M, N), float("nan"), dtype=torch.float32, device="cuda")
+        h = torch.full((M, N), float("nan"), dtype=torch.float32, device="cuda")
+        with ops.record_routes() as rr:
+            ops.gemm(Ad, Wd, out, bias=bd, res=res, ln_post=(g2, b2), ln_out=h, cache=False)
+        routes.append([(r.splits, r.fix) for r in rr.routes])
+        return out, h
+
+    size = _lib.load().cdseg_gemm_ws_bytes(M, N, 0, 1)
+    assert size == M * N * 4 and _lib.load().cdseg_gemm_ws_bytes(M, N, 0, 0) == 0
+    ex = _exact_vs_today(ops, run, sizes=[size])
+    assert [b.nbytes for b in ex.served] == [size]
+    assert routes == [[(1, 2)], [(1, 2)]], routes  # unsplit, rows finished from the workspace, on both allocations
+    out, h = run()
+    x_ref = res.cpu().double() + A.double() @ W.double().t() + b.double()
+    assert (out.cpu().double() - x_ref).abs().max().item() < 2e-4 + 2e-5 * K ** 0.5  # test_gemm_fused_layernorm_epilogue's bound
+    h_ref = torch.nn.functional.layer_norm(x_ref.float(), (N,), g2.cpu(), b2.cpu())
+    assert (h.cpu() - h_ref).abs().max().item() < 2e-4 * (1 + h_ref.abs().max().item())
 
 
 def _gemm_raw(ops, A, W, out, ws, ws_bytes, bias=None, ln=None, res=None, ln_out=None):
