@@ -31,6 +31,7 @@ from ._lib import CdsegError, DuplicateVoxelsError
 from .models import fusion_gate
 
 CURVES = ("z", "z-trans", "hilbert", "hilbert-trans")
+POOL_LONG_MIN_ROWS = 960_000  # fine rows from which a long-run pooling takes the one-launch kernel (run_pooling)
 
 
 def _pooling_depth(stride):
@@ -561,6 +562,12 @@ class Engine:
                 w[pre + ".cat_a.w"] = (wc[:, :c] * f).to(device=device, dtype=T).contiguous()
                 w[pre + ".cat_b.w"] = wc[:, c:].to(device=device, dtype=T).contiguous()
                 w[pre + ".cat.b"] = f32(mod.proj_cat[0].bias)
+            else:
+                sw, pw = w[pre + ".skip.w"], w[pre + ".proj.w"]
+                if hasattr(ops, "unpool_fused_ok") and ops.unpool_fused_ok(sw.shape[1], pw.shape[1], pw.shape[0], T, device):
+                    # one-launch unpooling of the wide stages (csrc/pool.hip): both weights as LDS images
+                    w[pre + ".skip.wimg"] = ops.unpool_fused_pack(sw)
+                    w[pre + ".proj.wimg"] = ops.unpool_fused_pack(pw)
 
         bb = self.model.backbone
         stem(bb._n_embedding, "n_emb")
@@ -1399,10 +1406,13 @@ class Engine:
         cout = w[pre + ".proj.w"].shape[0]
         x = self._buf(coarse.n, cout, torch.float32)
         xc = x if self.T == torch.float32 else self._buf(coarse.n, cout, self.T)
-        if (pre + ".proj.wimg") in w and st.xc.stride(0) == st.xc.shape[1] and fine.n <= 5 * coarse.n:
+        if (pre + ".proj.wimg") in w and st.xc.stride(0) == st.xc.shape[1] and (
+                fine.n <= 5 * coarse.n or fine.n >= POOL_LONG_MIN_ROWS):
             # wide 16-bit stages: projection + maximum + BatchNorm + GELU in one launch, the projected rows stay on the CU
-            # (one octree step, ~2.2 children per pooled row: 118 -> 67 us on the first pooling of a collated forward; the
-            # c-branch's two-step pooling, ~8.4 children, folds too many rows per lane and stays on the two launches)
+            # (one octree step, ~2.2 children per pooled row: 118 -> 67 us on the first pooling of a collated forward).  The
+            # c-branch's two-step pooling, ~8.4 children, takes the library's long-run fold (csrc/pool.hip) at the sizes it was
+            # measured at, inputs from HBM: 2.88 M rows 172 us against 277 for the two launches, 960 k rows 66 against 88
+            # (profiles/level_fused_kernel_stats.txt).  Smaller forwards were not measured and keep their two launches
             ops.pool_fused(st.xc, w[pre + ".proj.wimg"], w[pre + ".proj.b"], seg, coarse.n, w[pre + ".bn.scale"],
                            w[pre + ".bn.shift"], ops.ACT_GELU, x, xc)
         else:
@@ -1440,13 +1450,20 @@ class Engine:
         w = self.w
         parent = st.parent
         fine, coarse = parent.level, st.level
-        cluster, _ = plan.link(fine.cum, coarse.cum)
+        cluster, seg = plan.link(fine.cum, coarse.cum)  # (one plan item: _touch_plan finishes both for shared plans)
         cout = w[pre + ".proj.w"].shape[0]
         f = mod.skip_scale
         s = mod.skip_filter
         x = self._buf(fine.n, cout, torch.float32)
         xc = self._buf(fine.n, cout, self.T)
-        if mod.skip_connection_mode == "add":
+        if (mod.skip_connection_mode == "add" and f == 1.0 and s is None and (pre + ".skip.wimg") in w and st.xc.is_cuda
+                and parent.xc.stride(0) == parent.xc.shape[1] and st.xc.stride(0) == st.xc.shape[1]):
+            # wide 16-bit stages: child projection, skip projection and the add in one launch - the projected coarse rows stay
+            # on the CU, a wave walks the fine rows of its 16 coarse rows (the runs the pooling walked)
+            ops.unpool_fused(parent.xc, w[pre + ".skip.wimg"], w[pre + ".skip.b"], w[pre + ".skip_bn.scale"],
+                             w[pre + ".skip_bn.shift"], st.xc, w[pre + ".proj.wimg"], w[pre + ".proj.b"],
+                             w[pre + ".proj_bn.scale"], w[pre + ".proj_bn.shift"], seg, coarse.n, ops.ACT_GELU, x, xc)
+        elif mod.skip_connection_mode == "add":
             child = self._buf(coarse.n, cout, torch.float32)
             ops.gemm(st.xc, w[pre + ".proj.w"], child, bias=w[pre + ".proj.b"], scale=w[pre + ".proj_bn.scale"],
                      shift=w[pre + ".proj_bn.shift"], act=ops.ACT_GELU)

@@ -1007,12 +1007,64 @@ def pool_fused_pack(w):
 
 
 def pool_fused(x, wimg, bias, seg_start, m, scale, shift, act, out, out2=None):
-    """out (m, cout) fp32 = act(scale * max over each run of round16(x W^T + bias) + shift), out2 its 16-bit copy."""
+    """out (m, cout) fp32 = act(scale * max over each run of round16(x W^T + bias) + shift), out2 its 16-bit copy.
+    The runs cover the rows of x (seg_start[m] = x.shape[0]): the library picks its fold from x.shape[0] / m."""
     _need_gpu(x, out)
     cin, cout = x.shape[1], out.shape[1]
-    check(_lib.load().cdseg_pool_fused(_ptr(x), x.stride(0), _ptr(wimg), _ptr(bias), _ptr(seg_start), int(m), _ptr(scale),
-                                       _ptr(shift), int(act), _ptr(out), out.stride(0), _ptr(out2),
-                                       out2.stride(0) if out2 is not None else 0, cin, cout, _stream()), "pool_fused")
+    check(_lib.load().cdseg_pool_fused_n(_ptr(x), x.stride(0), x.shape[0], _ptr(wimg), _ptr(bias), _ptr(seg_start), int(m),
+                                         _ptr(scale), _ptr(shift), int(act), _ptr(out), out.stride(0), _ptr(out2),
+                                         out2.stride(0) if out2 is not None else 0, cin, cout, _stream()), "pool_fused")
+    return out
+
+
+POOL_FOLD_AUTO, POOL_FOLD_WALK, POOL_FOLD_SCAN = 0, 1, 2  # include/cdseg.h cdseg_pool_fused_fold
+
+
+class pool_fused_fold:
+    """`with ops.pool_fused_fold(ops.POOL_FOLD_SCAN): ...` - test hook: every pool_fused launch of the process inside the block
+    folds its runs the given way instead of choosing by run length (the results are the same bits either way)."""
+
+    def __init__(self, fold):
+        self.fold, self.lib = int(fold), _lib.load()
+
+    def __enter__(self):
+        self.prev = self.lib.cdseg_pool_fused_fold(self.fold)
+        if self.prev < 0:
+            check(self.prev, "pool_fused_fold")
+        return self
+
+    def __exit__(self, *exc):
+        self.lib.cdseg_pool_fused_fold(self.prev)
+        return False
+
+
+def unpool_fused_ok(k_skip, k_child, c, dtype, device):
+    """The one-launch unpooling (csrc/pool.hip) covers the wide 16-bit decoder stages on the GPU: skip 32 / child 64 and
+    skip 64 / child 128 input channels, 64 output channels."""
+    return (is_lp(dtype) and torch.device(device).type == "cuda"
+            and (int(k_skip), int(k_child), int(c)) in ((32, 64, 64), (64, 128, 64)))
+
+
+def unpool_fused_pack(w):
+    """(64, cin) 16-bit projection weight -> its MFMA-fragment image (built once per weight)."""
+    _need_gpu(w)
+    cout, cin = w.shape
+    lib = _lib.load()
+    img = _scratch(lib.cdseg_unpool_fused_img_bytes(cin, cout), w.device)
+    check(lib.cdseg_unpool_fused_pack(_ptr(w), cin, cout, _ptr(img), _stream()), "unpool_fused_pack")
+    return img
+
+
+def unpool_fused(skip_x, wimg_skip, bias_skip, scale_skip, shift_skip, coarse_x, wimg_child, bias_child, scale_child, shift_child,
+                 seg_start, m, act, out, out2):
+    """out (n, c) fp32 = s + act(scale_child * (coarse_x W_child^T + bias_child) + shift_child)[the run that holds the row],
+    s = act(scale_skip * (skip_x W_skip^T + bias_skip) + shift_skip); out2 (n, c) 16-bit = s.  Runs = seg_start (m + 1)."""
+    _need_gpu(skip_x, coarse_x, out, out2)
+    check(_lib.load().cdseg_unpool_fused(_ptr(skip_x), skip_x.stride(0), _ptr(wimg_skip), _ptr(bias_skip), _ptr(scale_skip),
+                                         _ptr(shift_skip), _ptr(coarse_x), coarse_x.stride(0), _ptr(wimg_child), _ptr(bias_child),
+                                         _ptr(scale_child), _ptr(shift_child), _ptr(seg_start), int(m), int(act), _ptr(out),
+                                         out.stride(0), _ptr(out2), out2.stride(0), skip_x.shape[1], coarse_x.shape[1],
+                                         out.shape[1], _stream()), "unpool_fused")
     return out
 
 

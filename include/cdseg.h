@@ -319,12 +319,40 @@ int cdseg_segment_max(const void* y, int y_dtype, int ldy, const int32_t* seg_st
  * :548-551 norm + act):   out[j] = act(scale * max_{i in run j} round16(W x_i + bias) + shift),   out2 = 16-bit copy.
  * Bit-identical to cdseg_gemm (16-bit output) followed by cdseg_segment_max; the projected rows never reach HBM.
  * (cin, cout) = (32, 64) or (64, 128), else CDSEG_ERR_UNSUPPORTED (callers use the two-launch form).  wimg: fragment image
- * of W (cout, cin) built once by cdseg_pool_fused_pack (cdseg_pool_fused_img_bytes bytes).  act: NONE or GELU. */
+ * of W (cout, cin) built once by cdseg_pool_fused_pack (cdseg_pool_fused_img_bytes bytes).  act: NONE or GELU.
+ * Every run holds at least one row, as for cdseg_segment_max.
+ * The maximum of a run is folded in one of two ways that give the same bits: short runs (one octree step) through a strip
+ * the lanes of a pooled row walk, long runs (two steps, ~8 children) by a segmented maximum across the 16 child lanes of a
+ * step.  cdseg_pool_fused_n takes the rows of x, n_fine = seg_start[m], which only the device holds otherwise, and chooses
+ * from the mean run length n_fine / m; cdseg_pool_fused, without it, walks.
+ * TEST HOOK, not part of the product interface: cdseg_pool_fused_fold forces the fold of every later launch of the process
+ * (0 = as above, 1 = walk, 2 = segmented maximum) and returns the previous setting; CDSEG_ERR_ARG otherwise. */
+int cdseg_pool_fused_fold(int fold);
+int cdseg_pool_fused_n(const void* x, int ldx, long n_fine, const void* wimg, const float* bias, const int32_t* seg_start, long m,
+                       const float* scale, const float* shift, int act, float* out, int ldo, void* out2, int ldo2,
+                       int cin, int cout, void* stream);
 size_t cdseg_pool_fused_img_bytes(int cin, int cout);
 int cdseg_pool_fused_pack(const void* w, int cin, int cout, void* wimg, void* stream);
 int cdseg_pool_fused(const void* x, int ldx, const void* wimg, const float* bias, const int32_t* seg_start, long m,
                      const float* scale, const float* shift, int act, float* out, int ldo, void* out2, int ldo2,
                      int cin, int cout, void* stream);
+/* SerializedUnpooling of the wide decoder stages, mode "add", in one launch (16-bit trunk; ref: ptv3.py:597-630):
+ *   s = act(scale_skip * (W_skip skip_x[i] + bias_skip) + shift_skip),   out2[i] = round16(s)   (the pre-add skip),
+ *   out[i] = s + act(scale_child * (W_child coarse_x[j] + bias_child) + shift_child)   for the rows i of run j,
+ * runs = seg_start (m + 1 entries, every run holds at least one row; the rows of skip_x / out / out2 are seg_start[m]).
+ * Bit-identical to cdseg_gemm of coarse_x into an fp32 buffer followed by cdseg_gemm of skip_x with add_src / add_idx (the
+ * cluster of seg_start) / out2_pre_add; the projected coarse rows never reach HBM.  (k_skip, k_child, c) = (32, 64, 64) or
+ * (64, 128, 64), else CDSEG_ERR_UNSUPPORTED (callers use the two launches).  wimg_*: fragment images of the (c, k) weights
+ * built once by cdseg_unpool_fused_pack (cdseg_unpool_fused_img_bytes bytes; cin 32 / 64 / 128, cout 64).  act: NONE or GELU.
+ * ld_skip / ld_coarse % 8 == 0, ldo / ldo2 % 4 == 0; skip_x, coarse_x, the images, out and the parameter vectors 16-byte
+ * aligned, out2 8-byte aligned (CDSEG_ERR_ARG otherwise, nothing is launched).  No workspace. */
+size_t cdseg_unpool_fused_img_bytes(int cin, int cout);
+int cdseg_unpool_fused_pack(const void* w, int cin, int cout, void* wimg, void* stream);
+int cdseg_unpool_fused(const void* skip_x, int ld_skip, const void* wimg_skip, const float* bias_skip,
+                       const float* scale_skip, const float* shift_skip, const void* coarse_x, int ld_coarse,
+                       const void* wimg_child, const float* bias_child, const float* scale_child,
+                       const float* shift_child, const int32_t* seg_start, long m, int act, float* out, int ldo,
+                       void* out2, int ldo2, int k_skip, int k_child, int c, void* stream);
 /* segment mean of coord (ref: ptv3.py:513-515) */
 int cdseg_segment_mean(const float* x, int ldx, const int32_t* seg_start, long m, int c, float* out, int ldo,
                        void* stream);
