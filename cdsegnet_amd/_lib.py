@@ -246,6 +246,14 @@ SIGNATURES = {
     "cdseg_attention_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_int, c_int, c_long, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                     c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "cdseg_attention_drop": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_int, c_int, c_int, c_float, c_void_p, c_int, c_int, ctypes.c_double, c_uint64, c_uint64,
+                                     c_void_p]),
+    "cdseg_attention_drop_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_int, c_int, c_long, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                         c_int, c_int, c_int, c_int, c_void_p, c_size_t, ctypes.c_double, c_uint64, c_uint64,
+                                         c_void_p]),
+    "cdseg_dropout": (c_int, [c_void_p, c_int, c_void_p, c_int, c_long, c_int, ctypes.c_double, c_uint64, c_uint64, c_void_p]),
     "cdseg_layernorm_bwd": (c_int, [c_void_p, c_int, c_void_p, c_float, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
                                     c_void_p, c_long, c_int, c_void_p]),
     "cdseg_gelu_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p]),

@@ -71,7 +71,14 @@
   Z(ATTN_B16, "attn_bf16_kernel<narrow>")                             \
   Z(ATTN_B16_WIDE, "attn_bf16_kernel<16>")                            \
   Z(ATTN_X3, "attn_x3_kernel")                                        \
-  Z(ATTN_F32, "attn_f32_kernel")
+  Z(ATTN_F32, "attn_f32_kernel")                                      \
+  Z(ATTN_DROP_F32, "attn_drop_f32_kernel")                            \
+  Z(ATTN_DROP_B16, "attn_drop16_kernel")                              \
+  Z(ATTN_BWD_Q_DROP, "attn_bwd_q_mfma_kernel<DropP>")                 \
+  Z(ATTN_BWD_KV_DROP, "attn_bwd_kv_mfma_kernel<DropP>")               \
+  Z(ATTN_BWD16_Q_DROP, "attn_bwd16_q_kernel<DropP>")                  \
+  Z(ATTN_BWD16_KV_DROP, "attn_bwd16_kv_kernel<DropP>")                \
+  Z(DROPOUT_F32, "dropout_kernel")
 
 enum {
   CDSEG_RT_b16 = 0, CDSEG_RT_f32 = 1, CDSEG_RT_x3 = 2,

@@ -12,14 +12,14 @@
 // attn_bf16_kernel, what the reference's flash-attention path computes in a training step.
 #include <mutex>
 
+#include "attn_train.h"
 #include "common.h"
+#include "route.h"
 #include "wgrad_partition.h"
 
 namespace {
 
-constexpr int HD = 16;       // head dim
-constexpr int BW_WAVES = 16;  // waves per block of the attention backward kernels (1 block per CU: the LDS holds K + V or Q + dO)
-constexpr int BW_MAXL = 1024;
+using namespace cdseg_attn_train;  // HD, BW_WAVES, BW_MAXL, the LDS images, the 16-bit fragment helpers, the dropout mask
 
 struct AttnBwdP {
   const float* q; const float* k; const float* v; const float* dout;
@@ -44,13 +44,20 @@ struct AttnBwdP {
 //             column, then dV^T += dO^T P and dK^T += Q'^T dS the same way.
 // Q is prescaled by scale * log2(e) so that P = exp2(s' - m'); 20 + 16 MFMAs per 16 x 16 (query, key) tile.
 // LDS rows are 16 floats; the four 16-byte chunks of a row are XOR-swizzled with (row >> 1) & 3 (conflict-free float4
-// operand reads, like attn_f32_kernel's K image).
-__device__ __forceinline__ int bw_off(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 1) & 3)) << 4); }
-__device__ __forceinline__ float bw_elem(const char* base, int row, int d) {
-  return *reinterpret_cast<const float*>(base + bw_off(row, d >> 2) + (d & 3) * 4);
-}
+// operand reads, like attn_f32_kernel's K image): bw_off / bw_elem of attn_train.h.
+//
+// DROP (cdseg_attention_drop_bwd): the forward was O = ((M / keep) o P) V with the mask M of include/cdseg.h.  Each kernel
+// regenerates the mask factors f = M / keep of its tile from (seed, offset, patch, head, query, key) and uses
+//   dP = (dO V^T) o f,   D = sum_j P dP,   dS = P (dP - D),   dV = (f o P)^T dO;
+// the statistics (m, l) are those of the unmasked softmax.  The mask is a second kernel argument: kernel<DropP> takes it,
+// kernel<> is the kernel as it was (same arguments, same code).
+__device__ __forceinline__ DropP drop_arg() { return DropP{}; }
+__device__ __forceinline__ DropP drop_arg(const DropP& d) { return d; }
 
-__global__ __launch_bounds__(BW_WAVES * 64) void attn_bwd_q_mfma_kernel(AttnBwdP p) {
+template <typename... MASK>
+__global__ __launch_bounds__(BW_WAVES * 64) void attn_bwd_q_mfma_kernel(AttnBwdP p, MASK... drop) {
+  constexpr bool DROP = sizeof...(MASK) != 0;
+  [[maybe_unused]] const DropP d = drop_arg(drop...);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Ks = smem;
   char* Vs = smem + BW_MAXL * 64;
@@ -108,6 +115,12 @@ __global__ __launch_bounds__(BW_WAVES * 64) void attn_bwd_q_mfma_kernel(AttnBwdP
 #pragma unroll
       for (int r = 0; r < 4; ++r)
         if (kt * 16 + 4 * g + r >= L) sc[r] = -INFINITY;
+      if constexpr (DROP) {  // dP o f: keys 4 (4 kt + g) + r of query qslot
+        float f[4];
+        drop_keys4(d, patch, head, qslot, 4 * kt + g, f);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dp[r] *= f[r];
+      }
     };
     // ---- sweep 1: online (m, l, sum e dP) over the lane's keys, then across the four lane groups of the query
     float m = -INFINITY, l = 0.f, dn = 0.f;
@@ -164,7 +177,10 @@ __global__ __launch_bounds__(BW_WAVES * 64) void attn_bwd_q_mfma_kernel(AttnBwdP
   }
 }
 
-__global__ __launch_bounds__(BW_WAVES * 64) void attn_bwd_kv_mfma_kernel(AttnBwdP p) {
+template <typename... MASK>
+__global__ __launch_bounds__(BW_WAVES * 64) void attn_bwd_kv_mfma_kernel(AttnBwdP p, MASK... drop) {
+  constexpr bool DROP = sizeof...(MASK) != 0;
+  [[maybe_unused]] const DropP d = drop_arg(drop...);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Qs = smem;                                                     // Q' = Q * scale * log2(e)
   char* Gs = smem + BW_MAXL * 64;                                      // dO
@@ -239,7 +255,16 @@ __global__ __launch_bounds__(BW_WAVES * 64) void attn_bwd_kv_mfma_kernel(AttnBwd
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         pr[r] = exp2f(sc[r] - ms[r]) * is[r];
-        ds[r] = pr[r] * (dp[r] - Ds[r]);
+        if constexpr (!DROP) ds[r] = pr[r] * (dp[r] - Ds[r]);
+      }
+      if constexpr (DROP) {  // queries 4 (4 qt + g) + r of key kslot: dS from the masked dP, then f o P for dV
+        float f[4];
+        drop_queries4(d, patch, head, 4 * qt + g, kslot, f);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          ds[r] = pr[r] * (dp[r] * f[r] - Ds[r]);
+          pr[r] *= f[r];
+        }
       }
 #pragma unroll
       for (int t = 0; t < 4; ++t) {  // k-slot g of MFMA t <-> query 4 g + t: A = dO / Q' [query][head dim kl], B = register t
@@ -287,8 +312,6 @@ constexpr int BW_KV_LDS = 2 * BW_MAXL * 64 + 3 * BW_MAXL * 4;
 // 0 + a + b = 0 + b + a in fp32: the result does not depend on the order the atomics arrive in
 // (tests/test_gpu_deterministic.py pins this on launches whose rows sit in at most two slots; a plan that put a row into
 // three slots would need a per-row reduce).
-constexpr int B16_WAVES = 8;
-constexpr int B16_IMG = BW_MAXL * 32;  // one 16-bit operand of a patch-head
 constexpr int B16_Q_LDS = 2 * B16_IMG;
 constexpr int B16_KV_LDS = 2 * B16_IMG + 2 * BW_MAXL * 4;
 
@@ -302,38 +325,10 @@ struct AttnBwd16P {
   float scale;
 };
 
-typedef __attribute__((ext_vector_type(4))) short b16_s16x4_t;
-typedef __attribute__((address_space(3))) b16_s16x4_t b16_lds_s16x4_t;
-
-// byte offset of (row, 4-dim chunk c4) in a row-major 16-bit image
-__device__ __forceinline__ int b16_off(int row, int c4) { return row * 32 + ((((c4 >> 1) ^ (row >> 3)) & 1) << 4) + ((c4 & 1) << 3); }
-
-// A operand = rows 0 .. 15 of X^T for the 16 rows (k-slots) of X the lane's half wave covers: two transposing reads
-__device__ __forceinline__ bf16x8_t b16_tr_pair(unsigned a0, unsigned a1) {
-  const b16_s16x4_t v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<b16_lds_s16x4_t*>(a0));
-  const b16_s16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<b16_lds_s16x4_t*>(a1));
-  return __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
-// q * c rounded once to the 16-bit type, as attn_bf16_kernel prepares its B operand (flags 0)
-__device__ __forceinline__ uint4 b16_prescale(uint4 r, float c) {
-  float lo, hi;
-  unpack_bf16x2(r.x, lo, hi); r.x = pack_bf16x2(lo * c, hi * c);
-  unpack_bf16x2(r.y, lo, hi); r.y = pack_bf16x2(lo * c, hi * c);
-  unpack_bf16x2(r.z, lo, hi); r.z = pack_bf16x2(lo * c, hi * c);
-  unpack_bf16x2(r.w, lo, hi); r.w = pack_bf16x2(lo * c, hi * c);
-  return r;
-}
-
-__device__ __forceinline__ bf16x8_t b16_frag(uint4 u) { return __builtin_bit_cast(bf16x8_t, u); }
-
-// registers 8 mf .. 8 mf + 7 of a 32 x 32 accumulator as the 16-bit B fragment of k-slots 8 h .. 8 h + 7 (no saturation)
-__device__ __forceinline__ bf16x8_t b16_pack8(const float* x) {
-  return b16_frag(make_uint4(pack_bf16x2_inrange(x[0], x[1]), pack_bf16x2_inrange(x[2], x[3]), pack_bf16x2_inrange(x[4], x[5]),
-                             pack_bf16x2_inrange(x[6], x[7])));
-}
-
-__global__ __launch_bounds__(B16_WAVES * 64, 4) void attn_bwd16_q_kernel(AttnBwd16P p) {
+template <typename... MASK>
+__global__ __launch_bounds__(B16_WAVES * 64, 4) void attn_bwd16_q_kernel(AttnBwd16P p, MASK... drop) {
+  constexpr bool DROP = sizeof...(MASK) != 0;
+  [[maybe_unused]] const DropP d = drop_arg(drop...);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Ks = smem;
   char* Vs = smem + B16_IMG;
@@ -363,6 +358,13 @@ __global__ __launch_bounds__(B16_WAVES * 64, 4) void attn_bwd16_q_kernel(AttnBwd
   const unsigned tr0 = lds_base + b16_off(4 * h + ((lane & 15) >> 2), lane & 3);
   const unsigned tr1 = lds_base + b16_off(4 * h + ((lane & 15) >> 2) + 8, lane & 3);
   const f32x16_t zero16 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  // (DROP) dP o f: registers 4 c .. 4 c + 3 are keys 32 kt + 8 c + 4 h + {0 .. 3} of the lane's query
+  auto drop_dp = [&](int kt, int query, f32x16_t& dp) {
+    float f[16];
+    drop_keys16(d, patch, head, query, 8 * kt + h, f);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dp[r] *= f[r];
+  };
   for (int qt = blockIdx.z * B16_WAVES + wave; qt < nt; qt += B16_WAVES * gridDim.z) {
     const int qslot = qt * 32 + ql;
     const bool valid = qslot < L;
@@ -379,7 +381,8 @@ __global__ __launch_bounds__(B16_WAVES * 64, 4) void attn_bwd16_q_kernel(AttnBwd
     float m = -INFINITY, l = 0.f, dn = 0.f;
     for (int kt = 0; kt < nt; ++kt) {
       f32x16_t sc = mfma_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(Ks + kt * 1024 + row_off), qf, zero16);
-      const f32x16_t dp = mfma_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(Vs + kt * 1024 + row_off), gf, zero16);
+      f32x16_t dp = mfma_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(Vs + kt * 1024 + row_off), gf, zero16);
+      if constexpr (DROP) drop_dp(kt, qslot, dp);
       if (kt == nt - 1) {
 #pragma unroll
         for (int r = 0; r < 16; ++r)
@@ -421,7 +424,8 @@ __global__ __launch_bounds__(B16_WAVES * 64, 4) void attn_bwd16_q_kernel(AttnBwd
     f32x16_t dq = zero16;
     for (int kt = 0; kt < nt; ++kt) {
       const f32x16_t sc = mfma_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(Ks + kt * 1024 + row_off), qf, negm);
-      const f32x16_t dp = mfma_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(Vs + kt * 1024 + row_off), gf, zero16);
+      f32x16_t dp = mfma_32x32x16_bf16(*reinterpret_cast<const bf16x8_t*>(Vs + kt * 1024 + row_off), gf, zero16);
+      if constexpr (DROP) drop_dp(kt, qslot, dp);
       float ds[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) ds[r] = __builtin_amdgcn_exp2f(sc[r]) * (dp[r] - D);
@@ -444,7 +448,10 @@ __global__ __launch_bounds__(B16_WAVES * 64, 4) void attn_bwd16_q_kernel(AttnBwd
   }
 }
 
-__global__ __launch_bounds__(B16_WAVES * 64, 4) void attn_bwd16_kv_kernel(AttnBwd16P p) {
+template <typename... MASK>
+__global__ __launch_bounds__(B16_WAVES * 64, 4) void attn_bwd16_kv_kernel(AttnBwd16P p, MASK... drop) {
+  constexpr bool DROP = sizeof...(MASK) != 0;
+  [[maybe_unused]] const DropP d = drop_arg(drop...);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* Qs = smem;                                                   // Q' = round16(Q * scale * log2 e)
   char* Gs = smem + B16_IMG;                                         // dO
@@ -508,7 +515,16 @@ __global__ __launch_bounds__(B16_WAVES * 64, 4) void attn_bwd16_kv_kernel(AttnBw
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         pr[r] = __builtin_amdgcn_exp2f(sc[r]);
-        ds[r] = pr[r] * (dp[r] - Dr[r]);
+        if constexpr (!DROP) ds[r] = pr[r] * (dp[r] - Dr[r]);
+      }
+      if constexpr (DROP) {  // registers 4 c .. 4 c + 3 are queries 32 qt + 8 c + 4 h + {0 .. 3} of the lane's key
+        float f[16];
+        drop_queries16(d, patch, head, 8 * qt + h, kslot, f);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          ds[r] = pr[r] * (dp[r] * f[r] - Dr[r]);
+          pr[r] *= f[r];
+        }
       }
 #pragma unroll
       for (int mf = 0; mf < 2; ++mf) {
@@ -984,11 +1000,12 @@ extern "C" size_t cdseg_attention_bwd_ws_bytes(long num_slots, int num_heads) {
   return (size_t)num_slots * num_heads * 3 * sizeof(float);
 }
 
-extern "C" int cdseg_attention_bwd(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
-                                   const int32_t* q_gidx, const int32_t* kv_gidx, const int32_t* widx,
-                                   const int32_t* patch_start, int num_patches, int num_heads, long num_slots, int max_len,
-                                   float scale, const void* dout, int lddo, void* dq, void* dk, void* dv, int lddq, int lddk,
-                                   int lddv, int dtype, void* ws, size_t ws_bytes, void* stream) {
+// drop: NULL = cdseg_attention_bwd; else the mask of cdseg_attention_drop_bwd (the kernel<DropP> instantiations)
+static int attention_bwd_launch(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const int32_t* q_gidx,
+                                const int32_t* kv_gidx, const int32_t* widx, const int32_t* patch_start, int num_patches,
+                                int num_heads, long num_slots, int max_len, float scale, const void* dout, int lddo, void* dq,
+                                void* dk, void* dv, int lddq, int lddk, int lddv, int dtype, void* ws, size_t ws_bytes, void* stream,
+                                const DropP* drop) {
   if (num_patches <= 0 || num_heads <= 0) return CDSEG_OK;
   if (dtype != CDSEG_F32 && dtype != CDSEG_BF16) return CDSEG_ERR_UNSUPPORTED;
   // the patch-head lives in LDS (like the forward): a longer patch would write past the staged K / V / statistics
@@ -1012,8 +1029,8 @@ extern "C" int cdseg_attention_bwd(const void* q, const void* k, const void* v, 
     static std::once_flag attr16_once;
     static bool attr16_ok = false;
     std::call_once(attr16_once, [] {
-      attr16_ok = hipFuncSetAttribute((const void*)attn_bwd16_q_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, B16_Q_LDS) == hipSuccess &&
-                  hipFuncSetAttribute((const void*)attn_bwd16_kv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, B16_KV_LDS) == hipSuccess;
+      attr16_ok = hipFuncSetAttribute((const void*)attn_bwd16_q_kernel<>, hipFuncAttributeMaxDynamicSharedMemorySize, B16_Q_LDS) == hipSuccess &&
+                  hipFuncSetAttribute((const void*)attn_bwd16_kv_kernel<>, hipFuncAttributeMaxDynamicSharedMemorySize, B16_KV_LDS) == hipSuccess;
     });
     if (!attr16_ok) return CDSEG_ERR_LAUNCH;
     // A patch-head is cut into `split` slices of its query (q kernel) / key (kv kernel) tiles, each a block that stages the
@@ -1022,8 +1039,23 @@ extern "C" int cdseg_attention_bwd(const void* q, const void* k, const void* v, 
     int split = 1;
     while (split < 4 && (long)num_patches * num_heads * split * 2 <= 512) split *= 2;
     const dim3 grid16((unsigned)num_patches, (unsigned)num_heads, (unsigned)split);
-    hipLaunchKernelGGL(attn_bwd16_q_kernel, grid16, dim3(B16_WAVES * 64), B16_Q_LDS, s, p);
-    hipLaunchKernelGGL(attn_bwd16_kv_kernel, grid16, dim3(B16_WAVES * 64), B16_KV_LDS, s, p);
+    if (drop) {
+      static std::once_flag drop16_once;
+      static bool drop16_ok = false;
+      std::call_once(drop16_once, [] {
+        drop16_ok = hipFuncSetAttribute((const void*)attn_bwd16_q_kernel<DropP>, hipFuncAttributeMaxDynamicSharedMemorySize, B16_Q_LDS) == hipSuccess &&
+                    hipFuncSetAttribute((const void*)attn_bwd16_kv_kernel<DropP>, hipFuncAttributeMaxDynamicSharedMemorySize, B16_KV_LDS) == hipSuccess;
+      });
+      if (!drop16_ok) return CDSEG_ERR_LAUNCH;
+      cdseg_route_rec(CDSEG_RK_ATTN_BWD16_Q_DROP, 32, 32, split, 0, 0, CDSEG_BF16 << CDSEG_ROUTE_F_CT_SHIFT, B16_WAVES);
+      hipLaunchKernelGGL(attn_bwd16_q_kernel<DropP>, grid16, dim3(B16_WAVES * 64), B16_Q_LDS, s, p, *drop);
+      cdseg_route_rec(CDSEG_RK_ATTN_BWD16_KV_DROP, 32, 32, split, 0, 0, CDSEG_BF16 << CDSEG_ROUTE_F_CT_SHIFT, B16_WAVES);
+      hipLaunchKernelGGL(attn_bwd16_kv_kernel<DropP>, grid16, dim3(B16_WAVES * 64), B16_KV_LDS, s, p, *drop);
+      CDSEG_CHECK_LAUNCH();
+      return CDSEG_OK;
+    }
+    hipLaunchKernelGGL(attn_bwd16_q_kernel<>, grid16, dim3(B16_WAVES * 64), B16_Q_LDS, s, p);
+    hipLaunchKernelGGL(attn_bwd16_kv_kernel<>, grid16, dim3(B16_WAVES * 64), B16_KV_LDS, s, p);
     CDSEG_CHECK_LAUNCH();
     return CDSEG_OK;
   }
@@ -1036,14 +1068,52 @@ extern "C" int cdseg_attention_bwd(const void* q, const void* k, const void* v, 
   static std::once_flag attr_once;  // (one device per process: one process per GPU)
   static bool attr_ok = false;
   std::call_once(attr_once, [] {
-    attr_ok = hipFuncSetAttribute((const void*)attn_bwd_q_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BW_Q_LDS) == hipSuccess &&
-              hipFuncSetAttribute((const void*)attn_bwd_kv_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BW_KV_LDS) == hipSuccess;
+    attr_ok = hipFuncSetAttribute((const void*)attn_bwd_q_mfma_kernel<>, hipFuncAttributeMaxDynamicSharedMemorySize, BW_Q_LDS) == hipSuccess &&
+              hipFuncSetAttribute((const void*)attn_bwd_kv_mfma_kernel<>, hipFuncAttributeMaxDynamicSharedMemorySize, BW_KV_LDS) == hipSuccess;
   });
   if (!attr_ok) return CDSEG_ERR_LAUNCH;
-  hipLaunchKernelGGL(attn_bwd_q_mfma_kernel, grid, dim3(BW_WAVES * 64), BW_Q_LDS, s, p);
-  hipLaunchKernelGGL(attn_bwd_kv_mfma_kernel, grid, dim3(BW_WAVES * 64), BW_KV_LDS, s, p);
+  if (drop) {
+    static std::once_flag drop_once;
+    static bool drop_ok = false;
+    std::call_once(drop_once, [] {
+      drop_ok = hipFuncSetAttribute((const void*)attn_bwd_q_mfma_kernel<DropP>, hipFuncAttributeMaxDynamicSharedMemorySize, BW_Q_LDS) == hipSuccess &&
+                hipFuncSetAttribute((const void*)attn_bwd_kv_mfma_kernel<DropP>, hipFuncAttributeMaxDynamicSharedMemorySize, BW_KV_LDS) == hipSuccess;
+    });
+    if (!drop_ok) return CDSEG_ERR_LAUNCH;
+    cdseg_route_rec(CDSEG_RK_ATTN_BWD_Q_DROP, 16, 16, 1, 0, 0, CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, BW_WAVES);
+    hipLaunchKernelGGL(attn_bwd_q_mfma_kernel<DropP>, grid, dim3(BW_WAVES * 64), BW_Q_LDS, s, p, *drop);
+    cdseg_route_rec(CDSEG_RK_ATTN_BWD_KV_DROP, 16, 16, 1, 0, 0, CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, BW_WAVES);
+    hipLaunchKernelGGL(attn_bwd_kv_mfma_kernel<DropP>, grid, dim3(BW_WAVES * 64), BW_KV_LDS, s, p, *drop);
+    CDSEG_CHECK_LAUNCH();
+    return CDSEG_OK;
+  }
+  hipLaunchKernelGGL(attn_bwd_q_mfma_kernel<>, grid, dim3(BW_WAVES * 64), BW_Q_LDS, s, p);
+  hipLaunchKernelGGL(attn_bwd_kv_mfma_kernel<>, grid, dim3(BW_WAVES * 64), BW_KV_LDS, s, p);
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
+}
+
+extern "C" int cdseg_attention_bwd(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
+                                   const int32_t* q_gidx, const int32_t* kv_gidx, const int32_t* widx,
+                                   const int32_t* patch_start, int num_patches, int num_heads, long num_slots, int max_len,
+                                   float scale, const void* dout, int lddo, void* dq, void* dk, void* dv, int lddq, int lddk,
+                                   int lddv, int dtype, void* ws, size_t ws_bytes, void* stream) {
+  return attention_bwd_launch(q, k, v, ldq, ldk, ldv, q_gidx, kv_gidx, widx, patch_start, num_patches, num_heads, num_slots, max_len,
+                              scale, dout, lddo, dq, dk, dv, lddq, lddk, lddv, dtype, ws, ws_bytes, stream, nullptr);
+}
+
+// The dropout backward (include/cdseg.h): a threshold of 256 drops nothing and is cdseg_attention_bwd's launch.
+extern "C" int cdseg_attention_drop_bwd(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
+                                        const int32_t* q_gidx, const int32_t* kv_gidx, const int32_t* widx,
+                                        const int32_t* patch_start, int num_patches, int num_heads, long num_slots, int max_len,
+                                        float scale, const void* dout, int lddo, void* dq, void* dk, void* dv, int lddq, int lddk,
+                                        int lddv, int dtype, void* ws, size_t ws_bytes, double rate, uint64_t seed, uint64_t offset,
+                                        void* stream) {
+  DropP d;
+  if (!cdseg_drop_threshold(rate, seed, offset, &d)) return CDSEG_ERR_ARG;
+  if (max_len > CDSEG_MAX_PATCH || num_heads > 65535) return CDSEG_ERR_ARG;
+  return attention_bwd_launch(q, k, v, ldq, ldk, ldv, q_gidx, kv_gidx, widx, patch_start, num_patches, num_heads, num_slots, max_len,
+                              scale, dout, lddo, dq, dk, dv, lddq, lddk, lddv, dtype, ws, ws_bytes, stream, d.thr >= 256 ? nullptr : &d);
 }
 
 // The fp32 entry points check what they are given before any launch, like the 16-bit and the deterministic forms: the

@@ -84,10 +84,20 @@ def _reject(**flags):
                 f"MI355X hot path (supported: {allowed!r})")
 
 
+def _rate(name, value):
+    """A dropout rate: a real number in [0, 1), kept as a plain float (no parameter, no buffer)."""
+    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not 0.0 <= float(value) < 1.0:
+        raise ValueError(f"{name}={value!r}: a dropout rate is a real number in [0, 1)")
+    return float(value)
+
+
 class SerializedAttention(nn.Module):
     def __init__(self, channels, num_heads, patch_size, qkv_bias=True, qk_scale=None, order_index=0,
-                 enable_flash=True):
+                 enable_flash=True, attn_drop=0.0, proj_drop=0.0):
         super().__init__()
+        # train mode only (train_graph.py): attn_drop on the attention probabilities (ptv3.py:282-288), proj_drop behind proj
+        # (:293-294); the masks are the library's (include/cdseg.h "dropout")
+        self.attn_drop, self.proj_drop = _rate("attn_drop", attn_drop), _rate("proj_drop", proj_drop)
         assert channels % num_heads == 0
         if channels // num_heads != 16:
             raise NotImplementedError("the HIP attention kernels are specialised for head dim 16 (C/H == 16)")
@@ -105,10 +115,13 @@ class Block(nn.Module):
     """ref: ptv3.py:326-428."""
 
     def __init__(self, channels, num_heads, patch_size=48, mlp_ratio=4.0, qkv_bias=True, qk_scale=None,
-                 order_index=0, cpe_indice_key=None, enable_flash=True, T_dim=-1, pre_norm=True, drop_path=0.0):
+                 order_index=0, cpe_indice_key=None, enable_flash=True, T_dim=-1, pre_norm=True, drop_path=0.0,
+                 attn_drop=0.0, proj_drop=0.0):
         super().__init__()
         _reject(pre_norm=(pre_norm, True))
         self.channels, self.T_dim = channels, T_dim
+        # proj_drop is also the rate of the two MLP drops, behind the activation and behind fc2 (ptv3.py:316-322, :381)
+        self.attn_drop, self.proj_drop = _rate("attn_drop", attn_drop), _rate("proj_drop", proj_drop)
         self.drop_prob = float(drop_path)  # stochastic depth of the training forward (timm DropPath, ptv3.py:392-394): rows
         self.cpe = PointSequential(
             SubMConv3d(channels, channels, 3, bias=True, indice_key=cpe_indice_key),
@@ -116,7 +129,8 @@ class Block(nn.Module):
             nn.LayerNorm(channels),
         )
         self.norm1 = PointSequential(nn.LayerNorm(channels))
-        self.attn = SerializedAttention(channels, num_heads, patch_size, qkv_bias, qk_scale, order_index, enable_flash)
+        self.attn = SerializedAttention(channels, num_heads, patch_size, qkv_bias, qk_scale, order_index, enable_flash,
+                                        attn_drop=self.attn_drop, proj_drop=self.proj_drop)
         self.norm2 = PointSequential(nn.LayerNorm(channels))
         self.mlp = PointSequential(MLP(channels, int(channels * mlp_ratio), channels))
         self.drop_path = PointSequential(nn.Identity())
@@ -209,9 +223,10 @@ class SerializedCrossAttention(nn.Module):
     """ref: ptv3.py:859-1055."""
 
     def __init__(self, q_channels, kv_channels, num_heads, q_patch_size, kv_patch_size, qkv_bias=True, qk_scale=None,
-                 order_index=0, enable_flash=True):
+                 order_index=0, enable_flash=True, attn_drop=0.0, proj_drop=0.0):
         super().__init__()
         assert q_channels % num_heads == 0 and kv_channels % num_heads == 0
+        self.attn_drop, self.proj_drop = _rate("attn_drop", attn_drop), _rate("proj_drop", proj_drop)  # (ptv3.py:1038-1053)
         if q_channels // num_heads != 16:
             raise NotImplementedError("the HIP attention kernels are specialised for head dim 16 (C/H == 16)")
         self.q_channels, self.kv_channels, self.num_heads = q_channels, kv_channels, num_heads
@@ -248,9 +263,10 @@ class CrossBlock(nn.Module):
 
     def __init__(self, q_channels, kv_channels, num_heads, q_patch_size, kv_patch_size, mlp_ratio=4.0, qkv_bias=True,
                  qk_scale=None, order_index=0, q_cpe_indice_key=None, kv_cpe_indice_key=None, enable_flash=True,
-                 tm_feat=1.0, drop_path=0.0):
+                 tm_feat=1.0, drop_path=0.0, attn_drop=0.0, proj_drop=0.0):
         super().__init__()
         self.drop_prob = float(drop_path)
+        self.attn_drop, self.proj_drop = _rate("attn_drop", attn_drop), _rate("proj_drop", proj_drop)
         # the fusion gate (ptv3.py:1091-1103): a number f, or one of FUSION_MODES with a learned `feat_scale` - registered
         # FIRST, like the reference's, so that the state_dict keys keep its order
         if isinstance(tm_feat, str):
@@ -271,7 +287,8 @@ class CrossBlock(nn.Module):
         self.q_norm1 = PointSequential(nn.LayerNorm(q_channels))
         self.kv_norm1 = PointSequential(nn.LayerNorm(kv_channels))
         self.attn = SerializedCrossAttention(q_channels, kv_channels, num_heads, q_patch_size, kv_patch_size, qkv_bias,
-                                             qk_scale, order_index, enable_flash)
+                                             qk_scale, order_index, enable_flash, attn_drop=self.attn_drop,
+                                             proj_drop=self.proj_drop)
         self.q_norm2 = PointSequential(nn.LayerNorm(q_channels))
         self.mlp = PointSequential(MLP(q_channels, int(q_channels * mlp_ratio), q_channels))
         self.drop_path = PointSequential(nn.Identity())
@@ -284,6 +301,7 @@ class TransferModule(nn.Module):
     def __init__(self, tm_bidirectional=False, kv_num_heads=None, kv_drop_path=0.0, **kw):
         super().__init__()
         self.tm_bidirectional = bool(tm_bidirectional)
+        self.attn_drop, self.proj_drop = _rate("attn_drop", kw.get("attn_drop", 0.0)), _rate("proj_drop", kw.get("proj_drop", 0.0))
         if self.tm_bidirectional:
             swapped = dict(kw, q_channels=kw["kv_channels"], kv_channels=kw["q_channels"], num_heads=kv_num_heads,
                            q_patch_size=kw["kv_patch_size"], kv_patch_size=kw["q_patch_size"],
@@ -331,7 +349,9 @@ class PointTransformerV3(nn.Module):
         assert self.n_num_stages == len(n_dec_depths) + 1 == len(n_dec_channels) + 1 == len(n_dec_num_head) + 1
 
         no = len(self.order)
-        blk = dict(mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, qk_scale=qk_scale, enable_flash=enable_flash)
+        self.attn_drop, self.proj_drop = _rate("attn_drop", attn_drop), _rate("proj_drop", proj_drop)
+        blk = dict(mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, qk_scale=qk_scale, enable_flash=enable_flash,
+                   attn_drop=self.attn_drop, proj_drop=self.proj_drop)
 
         def rates(depths):  # stochastic-depth schedule over the blocks of one coder (ptv3.py:1459-1466)
             return [float(x) for x in torch.linspace(0, drop_path, sum(depths))]
@@ -406,6 +426,7 @@ class PointTransformerV3(nn.Module):
                 q_patch_size=n_enc_patch_size[-1], kv_patch_size=c_enc_patch_size[-1], mlp_ratio=mlp_ratio,
                 qkv_bias=qkv_bias, qk_scale=qk_scale, order_index=0, q_cpe_indice_key="stage2",
                 kv_cpe_indice_key="stage2", enable_flash=enable_flash, tm_feat=tm_feat,
+                attn_drop=self.attn_drop, proj_drop=self.proj_drop,
                 drop_path=c_enc_dp[2] if len(c_enc_dp) > 2 else 0.0,  # (ptv3.py:1735-1736)
                 tm_bidirectional=tm_bidirectional, kv_num_heads=c_enc_num_head[-1],
                 kv_drop_path=c_enc_dp[2] if len(c_enc_dp) > 2 else 0.0)

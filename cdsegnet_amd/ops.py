@@ -6,6 +6,7 @@ the hand-written HIP kernels of libcdseg_hip.so.  No fallbacks: tensors must liv
 """
 import collections
 import ctypes
+import math
 import os
 import threading
 
@@ -1397,6 +1398,77 @@ def attention_bwd(q, k, v, q_gidx, kv_gidx, widx, patch_start, patch_start_host,
                                   _ptr(kv_gidx), _ptr(widx), _ptr(patch_start), num_patches, int(num_heads), ps[-1], max(1, max_len),
                                   float(scale), _ptr(dout), dout.stride(0), _ptr(dq), _ptr(dk), _ptr(dv), dq.stride(0),
                                   dk.stride(0), dv.stride(0), code, _ptr(ws), ws.numel(), _stream()), "attention_bwd")
+
+
+# ---- dropout (include/cdseg.h "dropout"; csrc/attention_drop.hip, the mask variants of csrc/train.hip)
+_U64 = 2 ** 64 - 1
+
+
+def _drop_rate(what, rate):
+    rate = float(rate)
+    if not 0.0 <= rate < 1.0:
+        raise _lib.CdsegError(f"{what}: rate must lie in [0, 1), got {rate!r}")
+    return rate
+
+
+def dropout_keep(rate):
+    """The effective keep probability T / 256 of a dropout rate: T = floor(256 (1 - rate) + 1/2), at least 1 (8-bit
+    granularity; kept values are divided by it)."""
+    rate = _drop_rate("dropout_keep", rate)
+    return max(1, int(math.floor(256.0 * (1.0 - rate) + 0.5))) / 256.0
+
+
+def attention_drop(q, k, v, q_gidx, kv_gidx, widx, patch_start, num_heads, max_len, scale, out, rate, seed, offset):
+    """`attention` with dropout on the probabilities: out = ((M / keep) o softmax(scale q k^T)) v, M the library's mask of
+    the site (seed, offset) at `rate`.  fp32, or the active build's 16-bit type (q not prescaled, v of the same type)."""
+    _need_gpu(q, out)
+    rate = _drop_rate("attention_drop", rate)
+    if not (q.dtype == k.dtype == v.dtype == out.dtype):
+        raise _lib.CdsegError("attention_drop: q, k, v, out must share a dtype")
+    code = dt(q)
+    check(_lib.load().cdseg_attention_drop(_ptr(q), _ptr(k), _ptr(v), q.stride(0), k.stride(0), v.stride(0), _ptr(q_gidx),
+                                           _ptr(kv_gidx), _ptr(widx), _ptr(patch_start), patch_start.numel() - 1, int(num_heads),
+                                           int(max_len), float(scale), _ptr(out), out.stride(0), code, rate, int(seed) & _U64,
+                                           int(offset) & _U64, _stream()), "attention_drop")
+    return out
+
+
+def attention_drop_bwd(q, k, v, q_gidx, kv_gidx, widx, patch_start, patch_start_host, num_heads, scale, dout, dq, dk, dv, rate,
+                       seed, offset):
+    """Gradients of `attention_drop` at the same (rate, seed, offset); everything else as `attention_bwd`."""
+    _need_gpu(q, dout)
+    rate = _drop_rate("attention_drop_bwd", rate)
+    if not (q.dtype == k.dtype == v.dtype == dout.dtype):
+        raise _lib.CdsegError("attention_drop_bwd: q, k, v, dout must share a dtype")
+    if not (dq.dtype == dk.dtype == dv.dtype == torch.float32):
+        raise _lib.CdsegError("attention_drop_bwd: dq, dk, dv are fp32 (accumulated into)")
+    code = dt(q)
+    ps = [int(x) for x in patch_start_host]
+    num_patches = len(ps) - 1
+    max_len = max((ps[i + 1] - ps[i] for i in range(num_patches)), default=0)
+    lib = _lib.load()
+    ws = _scratch(max(1, lib.cdseg_attention_bwd_ws_bytes(ps[-1], int(num_heads))), q.device)
+    check(lib.cdseg_attention_drop_bwd(_ptr(q), _ptr(k), _ptr(v), q.stride(0), k.stride(0), v.stride(0), _ptr(q_gidx),
+                                       _ptr(kv_gidx), _ptr(widx), _ptr(patch_start), num_patches, int(num_heads), ps[-1],
+                                       max(1, max_len), float(scale), _ptr(dout), dout.stride(0), _ptr(dq), _ptr(dk), _ptr(dv),
+                                       dq.stride(0), dk.stride(0), dv.stride(0), code, _ptr(ws), ws.numel(), rate,
+                                       int(seed) & _U64, int(offset) & _U64, _stream()), "attention_drop_bwd")
+
+
+def dropout(x, rate, seed, offset, out=None):
+    """out = x o M / keep on a 2-D fp32 tensor (any row stride; out may be x), M the library's element mask of the site
+    (seed, offset).  Its own backward: dropout(dy, rate, seed, offset)."""
+    _need_gpu(x)
+    rate = _drop_rate("dropout", rate)
+    if out is None:
+        out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    if x.dim() != 2 or out.shape != x.shape or x.dtype != torch.float32 or out.dtype != torch.float32:
+        raise _lib.CdsegError("dropout: x and out are fp32 (m, c) tensors of one shape")
+    if x.shape[1] > 1 and (x.stride(1) != 1 or out.stride(1) != 1):
+        raise _lib.CdsegError("dropout: rows must be contiguous")
+    check(_lib.load().cdseg_dropout(_ptr(x), x.stride(0), _ptr(out), out.stride(0), x.shape[0], x.shape[1], rate,
+                                    int(seed) & _U64, int(offset) & _U64, _stream()), "dropout")
+    return out
 
 
 def layernorm_bwd(x, gamma, dy, dx, accumulate=False, eps=1e-5, dgamma=None, dbeta=None, deterministic=False):

@@ -70,6 +70,13 @@ mode such modules normalise with this rank's rows only, and say so once.  Eval m
 512, momentum = None and modules without affine parameters take the torch path in either mode; a CPU tensor in the fused mode
 raises like every other op of the library.  These sites are fp32 in every train_precision.
 
+Dropout (`attn_drop`, `proj_drop` of the backbone; train mode, rate > 0 only - otherwise no node is added): `_AttentionDrop` /
+`_AttentionDrop16` in the attention core's place, `_Dropout` behind `proj`, behind the MLP's GELU and behind `fc2`.  A site is (seed,
+offset) of the library's mask stream (include/cdseg.h "dropout"): seed = torch.initial_seed(), offset = the next value of a counter on
+the TrainGraph that restarts when a forward finds another seed than the forward before; `draws["dropout"] = (seed, first offset)` pins a
+forward; `TrainGraph.dropout_sites` lists the sites of the last one.  Under `train_block = "native"` a Block with a rate runs as its
+autograd chain (one warning per process).
+
 Native Blocks (`model.train_block = "native"`, default "autograd"; read at every forward): every Block of both branches is ONE
 autograd node, `_NativeBlock`, whose forward and backward are one library call each (csrc/trainblock.hip: ops.train_block_forward /
 _backward): the same products through the same entry points, the torch glue between them (residual adds, stochastic-depth
@@ -422,12 +429,82 @@ class _Attention16(torch.autograd.Function):
         return da, (None if packed else db), None, None, None, None, None, None, None, None, None, None
 
 
-def attention_core(variant, q_src, kv_src, cq, q_gidx, kv_gidx, widx, patch_start, psh, heads, max_len, scale):
+class _AttentionDrop(torch.autograd.Function):
+    """_Attention with dropout on the probabilities (ref: ptv3.py:282-288 `dropout_p=self.attn_drop`): drop = (rate, seed,
+    offset), the site's mask of include/cdseg.h; the backward regenerates it from the same triple."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, q_gidx, kv_gidx, widx, patch_start, patch_start_host, heads, max_len, scale, drop):
+        o = _f32(q.shape, q)
+        ops.attention_drop(q, k, v, q_gidx, kv_gidx, widx, patch_start, heads, max_len, scale, o, *drop)
+        ctx.save_for_backward(q, k, v, q_gidx, kv_gidx, widx, patch_start)
+        ctx.meta = (list(patch_start_host), heads, scale, tuple(drop))
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, k, v, q_gidx, kv_gidx, widx, patch_start = ctx.saved_tensors
+        psh, heads, scale, drop = ctx.meta
+        dq, dk, dv = torch.zeros_like(q), torch.zeros_like(k), torch.zeros_like(v)
+        ops.attention_drop_bwd(q, k, v, q_gidx, kv_gidx, widx, patch_start, psh, heads, scale, _c(do), dq, dk, dv, *drop)
+        return dq, dk, dv, None, None, None, None, None, None, None, None, None
+
+
+class _AttentionDrop16(torch.autograd.Function):
+    """_Attention16 with dropout on the probabilities: the same casts (dout WITHOUT saturation), the 16-bit dropout kernels."""
+
+    @staticmethod
+    def forward(ctx, src, src2, cq, q_gidx, kv_gidx, widx, patch_start, patch_start_host, heads, max_len, scale, variant, drop):
+        t16 = ops.LP_DTYPES[variant]
+        with _lib.use(variant):
+            a = ops.cast(_c(src), t16)
+            b = a if src2 is None else ops.cast(_c(src2), t16)
+            q, k, v = (a[:, :cq], a[:, cq:2 * cq], a[:, 2 * cq:]) if src2 is None else (a, b[:, :cq], b[:, cq:])
+            o = torch.empty((src.shape[0], cq), dtype=t16, device=src.device)
+            ops.attention_drop(q, k, v, q_gidx, kv_gidx, widx, patch_start, heads, max_len, scale, o, *drop)
+        ctx.save_for_backward(a, b, q_gidx, kv_gidx, widx, patch_start)
+        ctx.meta = (list(patch_start_host), heads, scale, variant, cq, src2 is None, tuple(drop))
+        return o.float()
+
+    @staticmethod
+    def backward(ctx, do):
+        a, b, q_gidx, kv_gidx, widx, patch_start = ctx.saved_tensors
+        psh, heads, scale, variant, cq, packed, drop = ctx.meta
+        q, k, v = (a[:, :cq], a[:, cq:2 * cq], a[:, 2 * cq:]) if packed else (a, b[:, :cq], b[:, cq:])
+        da = torch.zeros(a.shape, dtype=torch.float32, device=a.device)
+        db = da if packed else torch.zeros(b.shape, dtype=torch.float32, device=a.device)
+        dq, dk, dv = (da[:, :cq], da[:, cq:2 * cq], da[:, 2 * cq:]) if packed else (da, db[:, :cq], db[:, cq:])
+        with _lib.use(variant):
+            ops.attention_drop_bwd(q, k, v, q_gidx, kv_gidx, widx, patch_start, psh, heads, scale, _c(do).to(a.dtype), dq, dk, dv,
+                                   *drop)
+        return da, (None if packed else db), None, None, None, None, None, None, None, None, None, None, None
+
+
+class _Dropout(torch.autograd.Function):
+    """Element dropout of an fp32 (rows, C) tensor (ref: proj_drop ptv3.py:293-294, MLP.drop :316-322): y = x o M / keep with
+    the site's mask; the backward is the same call on dy."""
+
+    @staticmethod
+    def forward(ctx, x, rate, seed, offset):
+        ctx.meta = (rate, seed, offset)
+        return ops.dropout(_c(x), rate, seed, offset)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.dropout(_c(dy), *ctx.meta), None, None, None
+
+
+def attention_core(variant, q_src, kv_src, cq, q_gidx, kv_gidx, widx, patch_start, psh, heads, max_len, scale, drop=None):
     """The attention core of a Block (kv_src None: q_src is the packed (N, 3 cq) qkv) or of the cross attention (q_src (N, cq),
-    kv_src (M, 2 cq)); variant None = exact fp32, "f16" / "bf16" = 16-bit core on that build of the library."""
+    kv_src (M, 2 cq)); variant None = exact fp32, "f16" / "bf16" = 16-bit core on that build of the library.
+    drop: None, or (rate, seed, offset) of the site's attention dropout."""
     if variant is None:
         q, k, v = (q_src[:, :cq], q_src[:, cq:2 * cq], q_src[:, 2 * cq:]) if kv_src is None else (q_src, kv_src[:, :cq], kv_src[:, cq:])
+        if drop is not None:
+            return _AttentionDrop.apply(q, k, v, q_gidx, kv_gidx, widx, patch_start, psh, heads, max_len, scale, drop)
         return _Attention.apply(q, k, v, q_gidx, kv_gidx, widx, patch_start, psh, heads, max_len, scale)
+    if drop is not None:
+        return _AttentionDrop16.apply(q_src, kv_src, cq, q_gidx, kv_gidx, widx, patch_start, psh, heads, max_len, scale, variant, drop)
     return _Attention16.apply(q_src, kv_src, cq, q_gidx, kv_gidx, widx, patch_start, psh, heads, max_len, scale, variant)
 
 
@@ -716,6 +793,7 @@ class _SegmentMaxArg(torch.autograd.Function):
 
 
 _warned_local_sync_bn = False
+_warned_native_dropout = False
 
 
 def _bn_gelu(x, bn, norm="torch"):
@@ -788,6 +866,12 @@ class TrainGraph:
         self.train_mix3d = "fold"      # from model.train_mix3d at every forward
         self.last_shared = None        # (N points, V voxels) of the last forward
         self._native = {}  # id(Block) -> [Block, static key, weight versions, ops.TrainBlock] (train_block "native")
+        # dropout sites (attn_drop / proj_drop): a site is (seed, offset) of the library's mask stream.  seed = torch.initial_seed();
+        # every site of a forward takes the next offset of a counter that restarts when a forward finds another seed than the
+        # forward before it (the rule of Engine.reserve_rng); draws["dropout"] = (seed, first offset) pins a forward.
+        self._drop_seed, self._drop_offset = None, 0
+        self._site = None          # [seed, next offset] of the running forward
+        self.dropout_sites = []    # (site name, seed, offset) of the last forward, in call order
 
     # ---------------------------------------------------------------------------------------- pieces
     def _mask(self, st, name, rate, masks):
@@ -832,8 +916,42 @@ class TrainGraph:
     def _ln(self, x, mod):
         return layernorm(x, mod, self.det)
 
-    def _mlp(self, h, mlp):
-        return self._lin(F.gelu(self._lin(h, mlp.fc1)), mlp.fc2)
+    def _begin_sites(self, draws):
+        self.dropout_sites = []
+        pinned = draws.get("dropout") if draws else None
+        if pinned is not None:
+            self._site = [int(pinned[0]), int(pinned[1]), True]
+            return
+        seed = torch.initial_seed()
+        if seed != self._drop_seed:
+            self._drop_seed, self._drop_offset = seed, 0
+        self._site = [seed, self._drop_offset, False]
+
+    def _next_site(self, name):
+        """(seed, offset) of dropout site `name`: the next offset of the forward."""
+        seed, offset, pinned = self._site
+        self._site[1] = offset + 1
+        if not pinned:
+            self._drop_offset = offset + 1
+        self.dropout_sites.append((name, seed, offset))
+        return seed, offset
+
+    def _attn_site(self, att, name):
+        """None, or (rate, seed, offset) of the attention dropout of `att` in this forward (train mode, rate > 0)."""
+        if att.attn_drop <= 0.0 or not self.model.training:
+            return None
+        return (att.attn_drop,) + self._next_site(name + ".attn.attn_drop")
+
+    def _drop(self, x, rate, name):
+        """Element dropout site `name`; the identity in eval mode or at rate 0 (no node)."""
+        if rate <= 0.0 or not self.model.training:
+            return x
+        return _Dropout.apply(x, rate, *self._next_site(name))
+
+    def _mlp(self, h, mlp, rate=0.0, name=""):
+        """fc1 - GELU - drop - fc2 - drop (ptv3.py:316-322; rate: the block's proj_drop)."""
+        h = self._drop(F.gelu(self._lin(h, mlp.fc1)), rate, name + ".mlp.0.drop.0")
+        return self._drop(self._lin(h, mlp.fc2), rate, name + ".mlp.0.drop.1")
 
     def _native_desc(self, mod):
         """The Block's descriptor for the native executor, with its derived weights current: rebuilt when the mode, a
@@ -883,7 +1001,13 @@ class TrainGraph:
     def _block(self, st, mod, name, t_scene, masks):
         """ref: ptv3.py:399-428."""
         if self.train_block == "native":
-            return self._block_native(st, mod, name, t_scene, masks)
+            if not self.model.training or (mod.attn_drop <= 0.0 and mod.proj_drop <= 0.0):
+                return self._block_native(st, mod, name, t_scene, masks)
+            global _warned_native_dropout  # (dropout is not part of the native executor: this Block runs as its autograd chain)
+            if not _warned_native_dropout:
+                _warned_native_dropout = True
+                warnings.warn("train_block = 'native': a Block with attn_drop / proj_drop > 0 runs as its autograd chain (dropout "
+                              "is not part of the native Block executor; cdsegnet_amd/train_graph.py)")
         lv = st.level
         x = st.x
         xconv, st.conv = (x if st.conv is None else st.conv), None
@@ -896,11 +1020,12 @@ class TrainGraph:
         gidx, widx = lv.slots(st.curves[att.order_index], att.patch_size, att.enable_flash)
         patch_start, max_len = lv.pad(att.patch_size, att.enable_flash)[4:6]
         psh = lv.pad_host(att.patch_size, att.enable_flash)[3].tolist()
-        o = attention_core(self.attn_variant, qkv, None, c, gidx, gidx, widx, patch_start, psh, att.num_heads, max_len, att.scale)
-        a = self._lin(o, att.proj)
+        o = attention_core(self.attn_variant, qkv, None, c, gidx, gidx, widx, patch_start, psh, att.num_heads, max_len, att.scale,
+                           self._attn_site(att, name))
+        a = self._drop(self._lin(o, att.proj), att.proj_drop, name + ".attn.proj_drop")
         m = self._mask(st, name + ".drop_path.0", mod.drop_prob, masks)
         x = x + (a if m is None else a * m)
-        h = self._mlp(self._ln(x, mod.norm2[0]), mod.mlp[0])
+        h = self._mlp(self._ln(x, mod.norm2[0]), mod.mlp[0], mod.proj_drop, name)
         m = self._mask(st, name + ".drop_path.0", mod.drop_prob, masks)
         st.x = x + (h if m is None else h * m)
         return st
@@ -974,15 +1099,17 @@ class TrainGraph:
         kv_gidx, _ = klv.slots(kvst.curves[att.order_index], K, att.enable_flash)
         patch_start, max_len = lv.pad(K, att.enable_flash)[4:6]
         psh = lv.pad_host(K, att.enable_flash)[3].tolist()
-        o = attention_core(self.attn_variant, q, kv, cq, q_gidx, kv_gidx, widx, patch_start, psh, att.num_heads, max_len, att.scale)
-        a = self._lin(o, att.proj)
+        o = attention_core(self.attn_variant, q, kv, cq, q_gidx, kv_gidx, widx, patch_start, psh, att.num_heads, max_len, att.scale,
+                           self._attn_site(att, name))
+        a = self._drop(self._lin(o, att.proj), att.proj_drop, name + ".attn.proj_drop")
+        block = name
         name = name + ".drop_path.0"
         m = self._mask(qst, name, cb.drop_prob, masks)
         if isinstance(cb.tm_feat, str):  # a learned gate: one node over the two kernels of csrc/fusion.hip
             x = _FuseGate.apply(xq, a, m, cb.feat_scale, cb.tm_feat)
         else:
             x = xq + cb.tm_feat * (a if m is None else a * m)
-        h = self._mlp(self._ln(x, cb.q_norm2[0]), cb.mlp[0])
+        h = self._mlp(self._ln(x, cb.q_norm2[0]), cb.mlp[0], cb.proj_drop, block)
         m = self._mask(qst, name, cb.drop_prob, masks)
         qst.x = x + (h if m is None else h * m)
 
@@ -1027,6 +1154,7 @@ class TrainGraph:
         self.train_loss = resolve_train_loss(self.model)
         self.train_norm = resolve_train_norm(self.model)
         self.train_block = resolve_train_block(self.model)
+        self._begin_sites(draws)
         if feat_is_cuda(input_dict):
             with torch.autocast(device_type="cuda", enabled=False):
                 return self._forward(input_dict, draws)

@@ -799,6 +799,58 @@ int cdseg_linear_wgrad16(const void* x, int ldx, const int32_t* xidx, const void
 int cdseg_conv_wgrad16(const void* x, int ldx, const int32_t* nbr_kmajor, int kvol, const void* dy, int lddy, long m, int cin,
                        int cout, float* dw, float* db, void* stream);
 
+/* ------------------------------------------------------------------ dropout (training only: attn_drop, proj_drop)
+ * ref: ptv3.py:282-288, :1038-1047 (flash-attention's dropout_p = attn_drop), :293-294, :1052-1053 (proj_drop),
+ *      :316-322 (MLP.drop).  The masks are this library's own; they are not torch's nor flash-attention's.
+ *
+ * The mask.  A dropout site is a pair (seed, offset).  Its random bytes are words of the cdseg_rand_int stream of that
+ * pair: W(t) = the four 32-bit words cdseg_rand_int(out, 4, seed, offset, NULL, 0) would write at out[4 t .. 4 t + 3], i.e.
+ * Philox4x32-10 under key (seed low, seed high) at counter (t low, t high, offset low, offset high).  Byte b of a word is
+ * (word >> 8 b) & 255.
+ *   threshold  T = floor(256 * (1 - rate) + 1/2), computed in double, and at least 1.  An element is KEPT iff its byte < T
+ *              and kept values are multiplied by 256 / T (rounded to fp32): the effective keep probability is T / 256, the
+ *              8-bit granularity of flash-attention.  A rate below 1/512 has T = 256: nothing is dropped and the factor is 1
+ *              (the attention entry points then run cdseg_attention / cdseg_attention_bwd themselves).  A rate above
+ *              1 - 1/512 keeps T = 1.  A rate outside [0, 1) (or NaN) is CDSEG_ERR_ARG.
+ *   attention  element (patch p, head h, query slot i, key slot j), slots counted from the start of the patch (i, j < 1024,
+ *              h < 65536):  t = (j >> 2) | (i >> 2) << 8 | h << 16 | p << 32,  word i & 3,  byte j & 3.
+ *              One call is a 4 x 4 block of the (query, key) plane.  A lane of every kernel holds, per tile, either four
+ *              consecutive keys of one query (one word) or four consecutive queries of one key (the same byte of the four
+ *              words), so one call feeds four accumulator elements in the forward and in all four backward kernels; more
+ *              per call would serve one orientation and starve the other.  (The 16-bit kernels' lanes hold four such
+ *              blocks per tile and share them with the three other lanes of their quad: one call per lane for 16 elements.)
+ *   element    element (row r, column c) of the (m, c) tensor as passed (r < 2^32):
+ *              t = (c >> 4) | r << 32,  word (c >> 2) & 3,  byte c & 3  - 16 consecutive columns of a row per call.
+ * The decision depends on (seed, offset, p, h, i, j) - or (seed, offset, r, c) - and on nothing else: not on the tile order,
+ * the wave count or the kernel variant, not on the dtype or the build, not on forward or backward.
+ *
+ * cdseg_attention_drop: cdseg_attention with O = ((M / keep) o softmax(scale Q K^T)) V, M the mask above and keep = T / 256;
+ *   dtype CDSEG_F32, or CDSEG_BF16 (the build's 16-bit type, flags 0: q' = q * fp32(scale log2 e) rounded once).  The softmax
+ *   denominator runs over all keys, dropped or not.  A padding-duplicate slot (widx -1) is a key like any other with mask
+ *   elements of its own.  16-bit form: fp32 statistics with the exact row maximum; (M / keep) o P is rounded to the 16-bit
+ *   type once, as the MFMA operand; fp32 accumulator; the output is rounded as cdseg_attention's.
+ * cdseg_attention_drop_bwd: cdseg_attention_bwd for that forward (same workspace, cdseg_attention_bwd_ws_bytes):
+ *   dV = ((M/keep) o P)^T dO,  dP = (dO V^T) o (M/keep),  D = sum_j P dP,  dS = P (dP - D),  dQ = scale dS K,  dK = scale dS^T Q.
+ *   Rounding and accumulation as cdseg_attention_bwd: fp32 statistics, dout never clamped, (M/keep) o P and dS are the 16-bit
+ *   MFMA operands and dS is converted without saturation (half build).
+ *   Both: CDSEG_ERR_ARG for a bad rate, max_len > 1024, num_heads > 65535, a NULL operand, a pointer or a row (ld * element
+ *   size; gradient rows: lddq, lddk, lddv multiples of 4) that is not 16-byte aligned; CDSEG_ERR_WORKSPACE as cdseg_attention_bwd.
+ * cdseg_dropout: y = x o M / keep on an (m, c) fp32 tensor with row strides ldx, ldy >= c (elements); y may be x.  16-byte
+ *   accesses when x, y are 16-byte aligned and ldx, ldy are multiples of 4, scalar ones otherwise (and on a ragged last group).
+ *   It is its own backward: dx = cdseg_dropout(dy) with the same (seed, offset).  CDSEG_ERR_ARG: a bad rate, a NULL or not
+ *   4-byte aligned pointer, ld < c, m >= 2^32. */
+int cdseg_attention_drop(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const int32_t* q_gidx,
+                         const int32_t* kv_gidx, const int32_t* widx, const int32_t* patch_start, int num_patches, int num_heads,
+                         int max_len, float scale, void* out, int ldo, int dtype, double rate, uint64_t seed, uint64_t offset,
+                         void* stream);
+int cdseg_attention_drop_bwd(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const int32_t* q_gidx,
+                             const int32_t* kv_gidx, const int32_t* widx, const int32_t* patch_start, int num_patches,
+                             int num_heads, long num_slots, int max_len, float scale, const void* dout, int lddo, void* dq,
+                             void* dk, void* dv, int lddq, int lddk, int lddv, int dtype, void* ws, size_t ws_bytes, double rate,
+                             uint64_t seed, uint64_t offset, void* stream);
+int cdseg_dropout(const float* x, int ldx, float* y, int ldy, long m, int c, double rate, uint64_t seed, uint64_t offset,
+                  void* stream);
+
 /* ------------------------------------------------------------------ deterministic training (fixed-order gradient reductions)
  * Opt-in forms of the reductions above whose fp32 summation order is FIXED, so that two runs of a training step give the
  * same bits.  The default entry points are unchanged.  Contract of the order:

@@ -4,7 +4,7 @@ with a 16-bit attention core, or under AMP (16-bit attention core, Linears and s
 a first number for the training row of SURVEY 8(f4).
 usage: python tools/bench_train_step.py [scenes=1] [points=120000] [steps=4] [dataset=scannet|scannet200|nuscenes]
        [train_precision=fp32|fp16-attn|bf16-attn|fp16-amp|bf16-amp] [det] [fused] [fusednorm] [fusedopt] [shadow] [nativeblock]
-       [mix3d|mix3d-rows]
+       [mix3d|mix3d-rows] [attn_drop=R] [proj_drop=R]
 A trailing `det` sets train_deterministic = True (fixed-order gradient reductions: bit-reproducible steps), a trailing `fused`
 sets train_loss = "fused" (cross entropy + Lovasz on the HIP loss kernels instead of the torch criteria), a trailing `fusednorm` sets train_norm =
 "fused" (train-mode BatchNorm + GELU and the pooling maximum on the kernels of csrc/norm.hip), a trailing `fusedopt`
@@ -12,7 +12,8 @@ takes cdsegnet_amd.optim.FusedAdamW in torch.optim.AdamW's place, and `shadow` (
 keep the 16-bit weight copies the forward multiplies with.  A trailing `nativeblock` sets train_block = "native" (every Block one
 autograd node on the executor of csrc/trainblock.hip).  A trailing `mix3d` merges the scenes pairwise into one batch element each
 (Mix3D: the merged rooms share voxels) and trains them in the default train_mix3d = "fold"; `mix3d-rows` sets train_mix3d =
-"rows" on the same batch (every point a row of its own)."""
+"rows" on the same batch (every point a row of its own).  Trailing `attn_drop=R` / `proj_drop=R` set the backbone's dropout rates
+(default 0, as in every shipped config)."""
 import os, sys, time
 import numpy as np
 import torch
@@ -39,6 +40,8 @@ if shadow and not (fusedopt and train_precision.endswith("-amp")):
     sys.exit("`shadow` needs `fusedopt` and an AMP train_precision (the fp32 step multiplies with the fp32 weights)")
 dev = torch.device("cuda")
 cfg = configs.cdsegnet_config(dataset)
+drops = {k: float(a.split("=", 1)[1]) for a in sys.argv[6:] for k in ("attn_drop", "proj_drop") if a.startswith(k + "=")}
+cfg["backbone"].update(drops)
 cfg["criteria"] = [dict(type="MSELoss", loss_weight=1.0, ignore_index=-1, batch_sample_point=-1),
                    dict(type="CrossEntropyLoss", loss_weight=1.0, ignore_index=-1),
                    dict(type="LovaszLoss", mode="multiclass", loss_weight=1.0, ignore_index=-1)]
@@ -87,7 +90,7 @@ for it in range(steps + 1):
         times.append((t1 - t0, t2 - t1, t3 - t2))
 t = np.median(np.array(times), axis=0) * 1e3
 tot = np.array(times).sum(1) * 1e3  # run-to-run spread of the whole step
-print(f"training step, {dataset}, full width, {train_precision}{', deterministic' if deterministic else ''}{', fused loss' if fused else ''}{', fused norm' if fusednorm else ''}{', FusedAdamW' if fusedopt else ''}{' + 16-bit weight copies' if shadow else ''}{', native Blocks' if nativeblock else ''}, {scenes} scene(s), {n} points: forward {t[0]:.1f} ms, backward {t[1]:.1f} ms, "
+print(f"training step, {dataset}, full width, {train_precision}{', deterministic' if deterministic else ''}{', fused loss' if fused else ''}{', fused norm' if fusednorm else ''}{', FusedAdamW' if fusedopt else ''}{' + 16-bit weight copies' if shadow else ''}{', native Blocks' if nativeblock else ''}{''.join(f', {k} {v}' for k, v in drops.items())}, {scenes} scene(s), {n} points: forward {t[0]:.1f} ms, backward {t[1]:.1f} ms, "
       f"AdamW {t[2]:.1f} ms = {t.sum():.1f} ms/step (steps {tot.min():.1f} - {tot.max():.1f}) = {n / t.sum() * 1e3 / 1e6:.2f} M points/s; peak memory "
       f"{torch.cuda.max_memory_allocated() / 2**30:.1f} GiB; loss over the steps {[round(v, 4) for v in losses]}")
 if mix3d is not None:
