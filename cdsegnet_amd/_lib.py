@@ -67,6 +67,8 @@ class BlockIO(Structure):
         ("nbr", c_void_p), ("gidx", c_void_p), ("widx", c_void_p), ("patch_start", c_void_p),
         ("num_patches", c_int), ("max_len", c_int), ("scratch", c_void_p), ("scratch_bytes", c_size_t),
         ("sat_counter", c_void_p),
+        ("flags", c_int), ("logits", c_void_p), ("head_w", c_void_p), ("head_b", c_void_p), ("out_idx", c_void_p),
+        ("num_classes", c_int), ("ld_logits", c_int),
     ]
 
 
@@ -229,6 +231,9 @@ SIGNATURES = {
                                   c_void_p, c_float, c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_void_p]),
     "cdseg_attn_tail_rr": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
                                    c_void_p, c_int, c_void_p, c_int, c_long, c_int, c_void_p]),
+    "cdseg_attn_tail_rr_ex": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
+                                      c_void_p, c_int, c_void_p, c_int, c_long, c_int, c_int, c_void_p, c_int, c_void_p,
+                                      c_void_p, c_void_p, c_int, c_void_p]),
     "cdseg_cpe_head_rr2": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                    c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_long, c_int, c_int, c_void_p]),
     "cdseg_attn_tail_rr2": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,

@@ -25,6 +25,7 @@
 #include "common.h"
 #include "deep.h"
 #include "route.h"
+#include "tail_outputs.h"
 
 namespace {
 
@@ -208,9 +209,14 @@ struct TailRR {
   const bf16_t* o; const uint4* wimg; const float* bp; const float* ln_g; const float* ln_b; const float* b1;
   const float* b2; float* x; bf16_t* xc;
   long n; int ldo, ldx, ldxc; float eps;
+  int store_x;  // 0: the caller reads x no more (CDSEG_BLOCK_X_DEAD) - the rows are read as the residual and left as they are
+  // LOGITS instantiation: neither x nor xc is stored; logits[out_idx ? out_idx[row] : row] = head_w x + head_b, all fp32
+  float* logits; const float* head_w; const float* head_b; const int32_t* out_idx; int classes, ld_logits;
 };
 
-template <int C>
+// LOGITS: the head's weights sit behind the tail's parameters in LDS (tail_outputs.h: tail_logits_lds_bytes)
+static_assert(tail_rr_lds_bytes(32) == RRCfg<32>::TAIL_W + RRCfg<32>::TAIL_P && tail_rr_lds_bytes(64) == RRCfg<64>::TAIL_W + RRCfg<64>::TAIL_P);
+template <int C, bool LOGITS>
 __global__ __launch_bounds__(RR_WAVES * 64, 4) void tail_rr_kernel(TailRR p) {
   using K = RRCfg<C>;
   constexpr int KS = K::KS, CT = K::CT, Q = K::Q, HU = 4 * C / 32;  // hidden k steps of 32
@@ -226,6 +232,11 @@ __global__ __launch_bounds__(RR_WAVES * 64, 4) void tail_rr_kernel(TailRR p) {
       pr[c] = p.bp[c]; pr[C + c] = p.ln_g[c]; pr[2 * C + c] = p.ln_b[c]; pr[3 * C + c] = p.b2[c];
     }
     for (int c = tid; c < 4 * C; c += RR_WAVES * 64) pr[4 * C + c] = p.b1[c];
+    if constexpr (LOGITS) {
+      float* hw = pr + 8 * C;
+      for (int u = tid; u < p.classes * C; u += RR_WAVES * 64) hw[(u / C) * (C + 4) + (u % C)] = p.head_w[u];
+      for (int k = tid; k < p.classes; k += RR_WAVES * 64) hw[p.classes * (C + 4) + k] = p.head_b ? p.head_b[k] : 0.f;
+    }
   }
   __syncthreads();
   const uint4* Wp = reinterpret_cast<const uint4*>(smem);                    // CT x KS
@@ -310,12 +321,41 @@ __global__ __launch_bounds__(RR_WAVES * 64, 4) void tail_rr_kernel(TailRR p) {
         for (int t = 0; t < CT; ++t)
           acc2[t] = mfma_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, w2[t]), Hf, acc2[t]);
       }
-      if (ok) {
+      if constexpr (LOGITS) {
+        // logits^T = W_head x^T in exact fp32 (v_mfma_f32_16x16x4_f32): the final row is already the B operand - register
+        // acc2[t][r] holds channel q * Q + 4 t + r of the lane's point, k slot q -; the A operand is lane (i, q)'s weight of
+        // class 16 ot + i for that channel.  The result lands as 4 consecutive classes (16 ot + 4 q ..) of the lane's point
 #pragma unroll
         for (int t = 0; t < CT; ++t) {
           const f32x4_t b2 = *reinterpret_cast<const f32x4_t*>(pr + 3 * C + q * Q + 4 * t);
           acc2[t] = acc2[t] + (b2 + x1[t]);
-          *reinterpret_cast<f32x4_t*>(p.x + row * p.ldx + q * Q + 4 * t) = acc2[t];
+        }
+        const float* hw = pr + 8 * C;
+        const float* hb = hw + p.classes * (C + 4);
+        const long orow = ok ? (p.out_idx ? (long)p.out_idx[row] : row) : -1;
+#pragma unroll 1
+        for (int ot = 0; 16 * ot < p.classes; ++ot) {
+          const int ka = min(16 * ot + j, p.classes - 1);        // (classes past the last one: a copy of it, stored nowhere)
+          const int kd = min(16 * ot + 4 * q, p.classes - 4);    // classes % 4 == 0: a lane's 4 classes exist or none does
+          f32x4_t lg = *reinterpret_cast<const f32x4_t*>(hb + kd);
+#pragma unroll
+          for (int t = 0; t < CT; ++t) {
+            const f32x4_t a = *reinterpret_cast<const f32x4_t*>(hw + ka * (C + 4) + q * Q + 4 * t);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) lg = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], acc2[t][r], lg, 0, 0, 0);
+          }
+          if (orow >= 0 && 16 * ot + 4 * q < p.classes)
+            *reinterpret_cast<f32x4_t*>(p.logits + orow * p.ld_logits + 16 * ot + 4 * q) = lg;
+        }
+      } else if (ok) {
+#pragma unroll
+        for (int t = 0; t < CT; ++t) {
+          const f32x4_t b2 = *reinterpret_cast<const f32x4_t*>(pr + 3 * C + q * Q + 4 * t);
+          acc2[t] = acc2[t] + (b2 + x1[t]);
+        }
+        if (p.store_x) {
+#pragma unroll
+          for (int t = 0; t < CT; ++t) *reinterpret_cast<f32x4_t*>(p.x + row * p.ldx + q * Q + 4 * t) = acc2[t];
         }
         if (p.xc) {
 #pragma unroll
@@ -406,38 +446,71 @@ extern "C" int cdseg_cpe_head_rr(const void* y, int ldy, const void* head_img, c
   return CDSEG_OK;
 }
 
-extern "C" int cdseg_attn_tail_rr(const void* o, int ldo, const void* tail_img, const float* bp, const float* ln_g,
-                                  const float* ln_b, float eps, const float* b1, const float* b2, float* x, int ldx,
-                                  void* xc, int ldxc, long n, int channels, void* stream) {
+extern "C" int cdseg_attn_tail_rr_ex(const void* o, int ldo, const void* tail_img, const float* bp, const float* ln_g,
+                                     const float* ln_b, float eps, const float* b1, const float* b2, float* x, int ldx,
+                                     void* xc, int ldxc, long n, int channels, int flags, float* logits, int ld_logits,
+                                     const float* head_w, const float* head_b, const int32_t* out_idx, int num_classes,
+                                     void* stream) {
+  if (flags & ~CDSEG_BLOCK_X_DEAD) return CDSEG_ERR_ARG;
+  const bool want_logits = logits || head_w || head_b || out_idx || num_classes || ld_logits;
+  if (want_logits) {  // refused before any launch, n = 0 included: the caller falls back on the head's GEMM
+    if (channels != 32 && channels != 64) return CDSEG_ERR_UNSUPPORTED;
+    const int rc = tail_logits_status(channels, num_classes, ld_logits, logits, head_w, out_idx);
+    if (rc != CDSEG_OK) return rc;
+  }
   if (n <= 0) return CDSEG_OK;
   if (!o || !tail_img || !bp || !ln_g || !ln_b || !b1 || !b2 || !x) return CDSEG_ERR_ARG;
   if (channels != 32 && channels != 64 && !deep_supported(channels)) return CDSEG_ERR_UNSUPPORTED;
   if ((ldo & 7) || (ldx & 3) || (xc && (ldxc & 7)) || (((uintptr_t)o | (uintptr_t)x | (uintptr_t)xc | (uintptr_t)tail_img) & 15))
     return CDSEG_ERR_ARG;
-  if (deep_supported(channels))
+  if (deep_supported(channels))  // (the deep tails write x whatever the flag says: "unspecified" allows it)
     return deep_tail(o, ldo, tail_img, bp, ln_g, ln_b, eps, b1, b2, x, ldx, x, ldx, xc, ldxc, n, channels, nullptr, 0,
                      (hipStream_t)stream);
   TailRR p;
   p.o = (const bf16_t*)o; p.wimg = (const uint4*)tail_img; p.bp = bp; p.ln_g = ln_g; p.ln_b = ln_b; p.b1 = b1; p.b2 = b2;
   p.x = x; p.xc = (bf16_t*)xc; p.n = n; p.ldo = ldo; p.ldx = ldx; p.ldxc = ldxc; p.eps = eps;
+  p.store_x = (flags & CDSEG_BLOCK_X_DEAD) ? 0 : 1;
+  p.logits = logits; p.head_w = head_w; p.head_b = head_b; p.out_idx = out_idx; p.classes = num_classes; p.ld_logits = ld_logits;
+  // what the launch leaves unwritten, in the route record's aux word (CDSEG_TAIL_AUX_*)
+  const int aux = want_logits ? (CDSEG_TAIL_AUX_LOGITS | CDSEG_TAIL_AUX_X_SKIPPED)
+                              : (p.store_x ? 0 : CDSEG_TAIL_AUX_X_SKIPPED);
   hipStream_t s = (hipStream_t)stream;
-  if (channels == 32) {
+  if (want_logits) {  // (tail_logits_status: C = 64)
+    const int lds = tail_rr_lds_bytes(64) + tail_logits_lds_bytes(64, num_classes);
+    static std::atomic<bool> attr_done{false};  // (a concurrent first call sets the attribute twice: harmless)
+    if (!attr_done) {
+      if (hipFuncSetAttribute((const void*)tail_rr_kernel<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              TAIL_RR_LDS_TWO_PER_CU) != hipSuccess)
+        return CDSEG_ERR_LAUNCH;
+      attr_done = true;
+    }
+    cdseg_route_rec(CDSEG_RK_TAIL_RR_64, 0, 0, 1, 0, 0, 0, aux);
+    hipLaunchKernelGGL((tail_rr_kernel<64, true>), dim3(rr_grid(n, lds)), dim3(RR_WAVES * 64), lds, s, p);
+  } else if (channels == 32) {
     constexpr int lds = RRCfg<32>::TAIL_W + RRCfg<32>::TAIL_P;
-    cdseg_route_rec(CDSEG_RK_TAIL_RR_32, 0, 0, 1, 0, 0, 0, 0);
-    hipLaunchKernelGGL(tail_rr_kernel<32>, dim3(rr_grid(n, lds)), dim3(RR_WAVES * 64), lds, s, p);
+    cdseg_route_rec(CDSEG_RK_TAIL_RR_32, 0, 0, 1, 0, 0, 0, aux);
+    hipLaunchKernelGGL((tail_rr_kernel<32, false>), dim3(rr_grid(n, lds)), dim3(RR_WAVES * 64), lds, s, p);
   } else {
     constexpr int lds = RRCfg<64>::TAIL_W + RRCfg<64>::TAIL_P;
     static std::atomic<bool> attr_done{false};  // (a concurrent first call sets the attribute twice: harmless)
     if (!attr_done) {
-      if (hipFuncSetAttribute((const void*)tail_rr_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+      if (hipFuncSetAttribute((const void*)tail_rr_kernel<64, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) !=
+          hipSuccess)
         return CDSEG_ERR_LAUNCH;
       attr_done = true;
     }
-    cdseg_route_rec(CDSEG_RK_TAIL_RR_64, 0, 0, 1, 0, 0, 0, 0);
-    hipLaunchKernelGGL(tail_rr_kernel<64>, dim3(rr_grid(n, lds)), dim3(RR_WAVES * 64), lds, s, p);
+    cdseg_route_rec(CDSEG_RK_TAIL_RR_64, 0, 0, 1, 0, 0, 0, aux);
+    hipLaunchKernelGGL((tail_rr_kernel<64, false>), dim3(rr_grid(n, lds)), dim3(RR_WAVES * 64), lds, s, p);
   }
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
+}
+
+extern "C" int cdseg_attn_tail_rr(const void* o, int ldo, const void* tail_img, const float* bp, const float* ln_g,
+                                  const float* ln_b, float eps, const float* b1, const float* b2, float* x, int ldx,
+                                  void* xc, int ldxc, long n, int channels, void* stream) {
+  return cdseg_attn_tail_rr_ex(o, ldo, tail_img, bp, ln_g, ln_b, eps, b1, b2, x, ldx, xc, ldxc, n, channels, 0, nullptr, 0,
+                               nullptr, nullptr, nullptr, 0, stream);
 }
 
 // Deep stages (C = 128 / 256 / 512) with the residual rows read from one buffer and written to another (round 6).  With

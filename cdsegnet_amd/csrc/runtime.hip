@@ -9,6 +9,7 @@
 
 #include "common.h"
 #include "deep.h"
+#include "tail_outputs.h"
 #include "workspace.h"
 
 namespace {
@@ -96,6 +97,17 @@ static int block_forward_impl(const cdseg_block_desc* d, const cdseg_block_io* i
   if (!io->scratch || io->scratch_bytes < L.total) return CDSEG_ERR_WORKSPACE;
   const bool fuse = C <= FUSE_LN_MAX_C;
   int rc;
+  static const bool fused_tail = cdseg_knob("CDSEG_FUSED_TAIL", 1) != 0 && cdseg_knob("CDSEG_FUSED_MLP", 1) != 0;
+  // the register-resident tail of the wide stages (blockrr.hip) is the one launch that honours the caller's word on which
+  // outputs are read: X_DEAD is a permission, the logit fields are a request - refused here, before the Block's first
+  // launch, when this call ends on another tail or the head does not fit (the saturation diagnostic reads xc_out)
+  const bool tail_rr = fused_tail && T == CDSEG_BF16 && (C == 32 || C == 64) && d->hidden == 4 * C && d->tail_img;
+  const bool want_logits = io->logits || io->head_w || io->head_b || io->out_idx || io->num_classes || io->ld_logits;
+  if (io->flags & ~CDSEG_BLOCK_X_DEAD) return CDSEG_ERR_ARG;
+  if (want_logits) {
+    if (!tail_rr || io->sat_counter) return CDSEG_ERR_UNSUPPORTED;
+    if ((rc = tail_logits_status(C, io->num_classes, io->ld_logits, io->logits, io->head_w, io->out_idx)) != CDSEG_OK) return rc;
+  }
   // what the qkv producer of this Block has already done for the attention kernel (cdseg_attention_ex): the engine folds
   // scale * log2(e) into the q rows of the weights (desc), the fused heads write v as bfloat16
   // (the fp32 attention kernel honours Q_PRESCALED too - ADVICE r5: dropping the flag here applied the softmax scale twice
@@ -210,7 +222,6 @@ static int block_forward_impl(const cdseg_block_desc* d, const cdseg_block_io* i
                                  d->dtype, attn_flags, stream)) != CDSEG_OK)
       return rc;
   }
-  static const bool fused_tail = cdseg_knob("CDSEG_FUSED_TAIL", 1) != 0 && cdseg_knob("CDSEG_FUSED_MLP", 1) != 0;
   if (pingpong) {
     void* xc = (const void*)io->xc_out != (const void*)io->x ? io->xc_out : nullptr;
     return cdseg_attn_tail_rr2(L.o, C, d->tail_img, (const float*)d->proj_b, (const float*)d->norm2_g, (const float*)d->norm2_b,
@@ -225,10 +236,12 @@ static int block_forward_impl(const cdseg_block_desc* d, const cdseg_block_io* i
   if (fused_tail && T == CDSEG_BF16 && (C == 32 || C == 64) && d->hidden == 4 * C) {
     // big stages: proj + residual + LN2 + MLP in one launch; h and the hidden activation never leave the CU
     void* xc = (const void*)io->xc_out != (const void*)io->x ? io->xc_out : nullptr;
-    if (d->tail_img)  // weights resident in LDS, activations in registers (blockrr.hip)
-      return cdseg_attn_tail_rr(L.o, C, d->tail_img, (const float*)d->proj_b, (const float*)d->norm2_g,
-                                (const float*)d->norm2_b, d->ln_eps, (const float*)d->fc1_b, (const float*)d->fc2_b,
-                                (float*)io->x, C, xc, C, n, C, stream);
+    if (d->tail_img)  // weights resident in LDS, activations in registers (blockrr.hip); without a 16-bit copy x is all
+                      // there is of the Block's output: the permission to leave it unwritten does not apply
+      return cdseg_attn_tail_rr_ex(L.o, C, d->tail_img, (const float*)d->proj_b, (const float*)d->norm2_g,
+                                   (const float*)d->norm2_b, d->ln_eps, (const float*)d->fc1_b, (const float*)d->fc2_b,
+                                   (float*)io->x, C, xc, C, n, C, xc ? (io->flags & CDSEG_BLOCK_X_DEAD) : 0, io->logits,
+                                   io->ld_logits, io->head_w, io->head_b, io->out_idx, io->num_classes, stream);
     return cdseg_attn_tail_fused(L.o, C, d->proj_w, (const float*)d->proj_b, (const float*)d->norm2_g,
                                  (const float*)d->norm2_b, d->ln_eps, d->fc1_w, (const float*)d->fc1_b, d->fc2_w,
                                  (const float*)d->fc2_b, (float*)io->x, C, xc, C, n, C, T, stream);

@@ -32,6 +32,37 @@ from .models import fusion_gate
 
 CURVES = ("z", "z-trans", "hilbert", "hilbert-trans")
 POOL_LONG_MIN_ROWS = 960_000  # fine rows from which a long-run pooling takes the one-launch kernel (run_pooling)
+# level-0 rows from which the last decoder Block's tail writes the logits itself (backbone): the row count from which the
+# persistent Block head takes over.  Below it the Block stores its fp32 rows and the head's GEMM reads them back, as ever.
+# Measured at one 120 k-point scene (tools/single_scene_profile.py, parent and this form alternating three times): 3.57, 3.55,
+# 3.57 ms against 3.52, 3.56, 3.54 - level with the parent, so the gate stays where it started; at 2.88 M rows the last
+# Block + head take 576 us against 580 + 310 (profiles/tail_outputs_kernel_stats.txt).  Nothing smaller was measured
+LOGITS_IN_TAIL_MIN_ROWS = 65_536
+LOGITS_IN_TAIL_MAX_CLASSES = {64: 20}  # per channel count: what csrc/tail_outputs.h fits into the tail's LDS
+
+
+def block_outputs_read(part, stage, num_stages, last_block, precision, branch="n", has_head=True, diagnostic=False,
+                       native=True):
+    """Which of a Block's two outputs - the fp32 residual stream x and its 16-bit copy xc - a later kernel reads: (x, xc).
+    part "enc" / "dec", stage index and count of that branch's encoder (the decoder has one stage fewer), last_block: the
+    Block ends its stage.  What follows a stage's last Block:
+      encoder, not the bottleneck   run_pooling, and later the decoder's run_unpooling: both read xc alone
+      bottleneck                    the cross block, the multi-step hoist, the trace: both streams
+      decoder stage > 0             run_unpooling of the next stage: xc alone
+      last n-decoder stage          the seg head: x with precision "*+head" (fp32 head, `_fit(exact=True)`), xc without;
+                                    both without a head (the rows themselves are the result)
+      last c-decoder stage          the c-head of the multi-step path: left as it is, both
+    Everything is read inside a stage (the next Block), in an fp32 engine (one buffer), on the binding path and while the
+    saturation diagnostic counts the stores."""
+    if not last_block or diagnostic or not native or precision in ("fp32", "fp32x3"):
+        return True, True
+    if part == "enc":
+        return (True, True) if stage == num_stages - 1 else (False, True)
+    if stage > 0:
+        return False, True
+    if branch != "n" or not has_head:
+        return True, True
+    return (True, False) if precision.endswith("+head") else (False, True)
 
 
 def _pooling_depth(stride):
@@ -407,6 +438,10 @@ class Engine:
         self.rng_offset = 0
         self._rng_seed = None  # torch.initial_seed() the device-RNG cursor belongs to
         self.use_native_blocks = True  # one library call per Block instead of ~8 binding calls
+        # a stage's last Block writes only the outputs that a later kernel reads (block_outputs_read), and the model's last
+        # one the logits of an fp32 head (backbone).  False: every Block writes x and xc as if read (tests, tools A/B)
+        self.dead_outputs = True
+        self.logits_in_tail = True
         self.fold_attn_scale = True  # 16-bit engines: softmax scale * log2(e) folded into Wq / bq at prepare (tools A/B: False)
         # diagnostic of the IEEE-half trunk: count the 16-bit activations that reach memory at +-65504, the clamp value of the
         # half build's conversions (a checkpoint whose activations leave half's range is then noticed, not silently clamped).
@@ -1284,8 +1319,12 @@ class Engine:
             st.xc = self._buf(n, c, self.T)
             ops.gemm(u, w[pre_fc + "2.w"], st.x, bias=w[pre_fc + "2.b"], res=st.x, out2=st.xc)
 
-    def run_block(self, st, mod, pre, tbias=None):
-        """ref: ptv3.py:399-428."""
+    def run_block(self, st, mod, pre, tbias=None, live=(True, True), head=None):
+        """ref: ptv3.py:399-428.
+        live: which of (x, xc) a later kernel reads (block_outputs_read; the default is what every direct caller gets) - a
+        dead x is left unwritten by the wide stages' tail and st.x is None afterwards, a dead xc is not allocated (st.xc is
+        st.x).  head: (logits, head_w, head_b, out_idx) - the model's last Block writes the seg head's logits instead of
+        either stream; returns True if it did (st.x and st.xc are None then), else the Block ran as `live` says."""
         w, lv = self.w, st.level
         n, c = st.x.shape
         if self.native_blocks:
@@ -1296,18 +1335,30 @@ class Engine:
             self.attn_bytes += 4.0 * n * c * st.xc.element_size()
             self._count_conv(n, c, st.xc.element_size())
             desc = self.block_desc[pre]
-            xc_out = st.x if self.T == torch.float32 else self._buf(n, c, self.T)
+            x_live, xc_live = live
+            if self.T == torch.float32 or self._sat is not None:
+                x_live, xc_live, head = True, True, None
             sb = self._scratch_bytes.get((pre, n))
             if sb is None:
                 if len(self._scratch_bytes) > 4096:
                     self._scratch_bytes.clear()
                 sb = self._scratch_bytes[(pre, n)] = ops.block_scratch_bytes(desc, n)
+            if head is not None and ops.block_forward(desc, n, st.x, st.xc, st.x, tbias, lv.nbr(3, True), gidx, widx,
+                                                      patch_start, patch_start.numel() - 1, max_len, self.scratch(sb),
+                                                      logits=head[0], head_w=head[1], head_b=head[2], out_idx=head[3]):
+                st.x = st.xc = None  # (neither was written: a reader fails loudly)
+                return True
+            # an unread 16-bit copy is not made: the executor takes xc_out = x as "no second buffer" (the fp32 engine's form)
+            xc_out = st.x if (self.T == torch.float32 or not xc_live) else self._buf(n, c, self.T)
+            flags = ops.BLOCK_X_DEAD if not x_live and xc_out is not st.x else 0
             ops.block_forward(desc, n, st.x, st.xc, xc_out, tbias, lv.nbr(3, True), gidx, widx, patch_start,
-                              patch_start.numel() - 1, max_len, self.scratch(sb), sat_counter=self._sat)
+                              patch_start.numel() - 1, max_len, self.scratch(sb), sat_counter=self._sat, flags=flags)
             if self._sat is not None:
                 self.saturation_checked += n * c * (5 if xc_out is not st.x else 4)
             st.xc = xc_out
-            return
+            if flags:
+                st.x = None  # (unspecified from here on: a reader fails loudly)
+            return False
         qkv = self._buf(n, 3 * c, self.T)
         aflags = ops.ATTN_Q_PRESCALED if self.q_prescaled else 0  # what the qkv producer has done for the attention kernel
         # deep stages (C = 128 / 256 / 512: csrc/deep.hip), as the native executor runs them (csrc/runtime.hip): the residual rows
@@ -1980,29 +2031,45 @@ class Engine:
         n_curves = shuffled(next(pi))
         tb = self._t_bias(t) if cond else {}
 
+        # which outputs of a stage's last Block are written at all (block_outputs_read).  Only where this engine runs every
+        # stage in its own precision: a tool that moves single stages to the fp32 twin (self.hi) reads whatever it likes
+        own_hi = frozenset(("n_head", "c_head")) if self.precision.endswith("+head") else frozenset()
+        prune = self.dead_outputs and self.hi == own_hi and self._sat is None
+        has_head = "n_head.w" in w
+
+        def live(e, part, branch, s, names, name):
+            if not prune:
+                return True, True
+            return block_outputs_read(part, s, getattr(bb, f"{branch}_num_stages"), name == names[-1], self.precision,
+                                      branch=branch, has_head=has_head, diagnostic=self._sat is not None,
+                                      native=e.native_blocks)
+
         def enc_stage(st, branch, s, cum, perm):
             enc = getattr(getattr(bb, f"_{branch}_enc"), f"enc{s}")
             e = self._eng(f"{branch}_enc{s}")
             e._fit(st)
             if s > 0:
                 st = e.run_pooling(plan, st, f"{branch}_enc{s}.down", cum[s], perm)
-            for name, mod in enc._modules.items():
-                if name.startswith("block"):
-                    key = f"{branch}_enc{s}.{name}"
-                    e.run_block(st, mod, key, tb.get(key))
+            names = [name for name in enc._modules if name.startswith("block")]
+            for name in names:
+                key = f"{branch}_enc{s}.{name}"
+                e.run_block(st, enc._modules[name], key, tb.get(key), live=live(e, "enc", branch, s, names, name))
             return st
 
-        def dec_stage(st, branch, s):
+        def dec_stage(st, branch, s, head=None):
+            """head: run_block's, for the last Block of the last n-decoder stage; returns (State, logits written)."""
             dec = getattr(getattr(bb, f"_{branch}_dec"), f"dec{s}")
             e = self._eng(f"{branch}_dec{s}")
             e._fit(st)
             e._fit(st.parent)  # the skip feature saved by the encoder
             st = e.run_unpooling(plan, st, f"{branch}_dec{s}.up", dec.up)
-            for name, mod in dec._modules.items():
-                if name.startswith("block"):
-                    key = f"{branch}_dec{s}.{name}"
-                    e.run_block(st, mod, key, tb.get(key))
-            return st
+            names = [name for name in dec._modules if name.startswith("block")]
+            done = False
+            for name in names:
+                key = f"{branch}_dec{s}.{name}"
+                done = e.run_block(st, dec._modules[name], key, tb.get(key), live=live(e, "dec", branch, s, names, name),
+                                   head=head if name == names[-1] else None)
+            return st, bool(done)
 
         # ref: ptv3.py:1781-1794.  The reference interleaves the two encoders (c0 n0 c1 n1 n2 c2 n3 n4); that order
         # only fixes which randperm draw each stage consumes.  The encoders are independent until the cross block, so
@@ -2069,18 +2136,34 @@ class Engine:
         if cond and want_c:
             self._msi_count("c_decoders")
             for s in reversed(range(bb.c_num_stages - 1)):
-                cst = dec_stage(cst, "c", s)
+                cst, _ = dec_stage(cst, "c", s)
             e = self._eng("c_head")
             e._fit(cst, exact=True)
             c_out = torch.empty((n, w["c_head.w"].shape[0]), dtype=torch.float32, device=dev)
             ops.gemm(cst.xc, e.w["c_head.w"], c_out, bias=e.w["c_head.b"])
+        # An fp32 head ("*+head") behind a 16-bit trunk reads the last Block's fp32 rows: 4 C bytes per point written and read
+        # back for a C -> classes product.  From LOGITS_IN_TAIL_MIN_ROWS points that Block's tail forms the logits on the
+        # row it holds in registers instead (csrc/blockrr.hip), where the library has the kernel: C = 64, classes % 4 == 0
+        # and <= 20 (ScanNet200's 200 keep the GEMM).  Plain Python on purpose: no library call decides it
+        head, logits, done = None, None, False
+        if (prune and has_head and self.logits_in_tail and self.T != torch.float32 and "n_head" in self.hi
+                and self.native_blocks and bb.n_num_stages > 1 and n >= LOGITS_IN_TAIL_MIN_ROWS
+                and getattr(bb._n_dec.dec0.up, "skip_filter", None) is None):
+            e = self._eng("n_head")
+            classes, last_c = e.w["n_head.w"].shape
+            if classes % 4 == 0 and classes <= LOGITS_IN_TAIL_MAX_CLASSES.get(last_c, 0):
+                logits = torch.empty((n, classes), dtype=torch.float32, device=dev)
+                head = (logits, e.w["n_head.w"], e.w["n_head.b"], plan.perm0)
         for s in reversed(range(bb.n_num_stages - 1)):
-            nst = dec_stage(nst, "n", s)
+            nst, done = dec_stage(nst, "n", s, head if s == 0 else None)
         # head, scattered back to the caller's point order (ref: ptv3.py:1813)
-        if "n_head.w" in w:
+        if done:
+            pass
+        elif "n_head.w" in w:
             e = self._eng("n_head")
             e._fit(nst, exact=True)
-            logits = torch.empty((n, w["n_head.w"].shape[0]), dtype=torch.float32, device=dev)
+            if logits is None:
+                logits = torch.empty((n, w["n_head.w"].shape[0]), dtype=torch.float32, device=dev)
             ops.gemm(nst.xc, e.w["n_head.w"], logits, bias=e.w["n_head.b"], out_idx=plan.perm0)
         else:
             logits = torch.empty((n, nst.x.shape[1]), dtype=torch.float32, device=dev)

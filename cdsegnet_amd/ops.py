@@ -830,6 +830,23 @@ def attn_tail_rr(o, tail_img, bp, ln_g, ln_b, b1, b2, x, xc=None, eps=1e-5):
     return x
 
 
+def attn_tail_rr_ex(o, tail_img, bp, ln_g, ln_b, b1, b2, x, xc=None, eps=1e-5, flags=0, logits=None, head_w=None,
+                    head_b=None, out_idx=None, num_classes=None, ld_logits=None):
+    """`attn_tail_rr` with a say in what it writes (include/cdseg.h: cdseg_attn_tail_rr_ex).  flags: BLOCK_X_DEAD - x is read
+    and left as it is, xc alone is stored.  logits (rows, classes) fp32 with head_w (classes, C) / head_b fp32 and out_idx (n)
+    int32: neither x nor xc is written, the head's logits are (C = 64, classes % 4 == 0, classes <= 20).  num_classes /
+    ld_logits default to head_w's rows / the logits' row stride."""
+    if logits is not None:
+        num_classes = head_w.shape[0] if num_classes is None else num_classes
+        ld_logits = logits.stride(0) if ld_logits is None else ld_logits
+    check(_lib.load().cdseg_attn_tail_rr_ex(_ptr(o), o.stride(0), _ptr(tail_img), _ptr(bp), _ptr(ln_g), _ptr(ln_b), float(eps),
+                                            _ptr(b1), _ptr(b2), _ptr(x), x.stride(0), _ptr(xc),
+                                            xc.stride(0) if xc is not None else 0, o.shape[0], o.shape[1], int(flags),
+                                            _ptr(logits), int(ld_logits or 0), _ptr(head_w), _ptr(head_b), _ptr(out_idx),
+                                            int(num_classes or 0), _stream()), "attn_tail_rr_ex")
+    return x
+
+
 def _dp(t):
     return None if t is None else t.data_ptr()
 
@@ -871,9 +888,13 @@ def split16(x, lo_scale=2048.0):
 
 
 def block_forward(desc, n, x, xc_in, xc_out, tbias, nbr, gidx, widx, patch_start, num_patches, max_len, scratch,
-                  sat_counter=None):
+                  sat_counter=None, flags=0, logits=None, head_w=None, head_b=None, out_idx=None):
     """One PTv3 Block on the native executor (all launches issued by the library, one host call).  sat_counter: 1-element
-    int64 device tensor that collects the Block's clamped half values (diagnostic, see count_saturated)."""
+    int64 device tensor that collects the Block's clamped half values (diagnostic, see count_saturated).
+    flags: BLOCK_X_DEAD - the caller reads x no more, its contents are unspecified on return (the wide stages' tail then stores
+    xc_out alone).  logits (rows, classes) fp32 with head_w (classes, C) / head_b fp32 and out_idx (n) int32: the model's last
+    Block writes the head's logits instead of x and xc_out.  Returns False - nothing launched - when the library cannot
+    (CDSEG_ERR_UNSUPPORTED: the caller runs the Block without them, then the head), True otherwise."""
     if _TLS.block_io is None:
         io = _lib.BlockIO()
         _TLS.block_io = (io, ctypes.byref(io))
@@ -884,7 +905,22 @@ def block_forward(desc, n, x, xc_in, xc_out, tbias, nbr, gidx, widx, patch_start
     io.num_patches, io.max_len = int(num_patches), int(max_len)
     io.scratch, io.scratch_bytes = scratch.data_ptr(), scratch.numel()
     io.sat_counter = sat_counter.data_ptr() if sat_counter is not None else None
-    check(_lib.load().cdseg_block_forward(desc[1], ref, _stream()), "block_forward")
+    io.flags = int(flags)
+    if logits is None:
+        io.logits = io.head_w = io.head_b = io.out_idx = None
+        io.num_classes = io.ld_logits = 0
+    else:
+        if logits.dtype != torch.float32 or head_w.dtype != torch.float32 or not head_w.is_contiguous() or (
+                head_w.shape[1] != x.shape[1]) or (
+                head_b is not None and head_b.dtype != torch.float32) or (out_idx is not None and out_idx.dtype != torch.int32):
+            raise _lib.CdsegError("block_forward: logits / head_w / head_b are fp32 (head_w contiguous), out_idx int32")
+        io.logits, io.head_w, io.head_b, io.out_idx = logits.data_ptr(), head_w.data_ptr(), _dp(head_b), _dp(out_idx)
+        io.num_classes, io.ld_logits = int(head_w.shape[0]), int(logits.stride(0))
+    status = _lib.load().cdseg_block_forward(desc[1], ref, _stream())
+    if status == _UNSUPPORTED and logits is not None:
+        return False
+    check(status, "block_forward")
+    return True
 
 
 def stem5_ok(cout, dtype):
@@ -963,6 +999,9 @@ def layernorm(x, gamma, beta, out, *, eps=1e-5, res=None, colbias=None, out2=Non
 
 
 ATTN_Q_PRESCALED, ATTN_V_BF16 = 1, 2  # include/cdseg.h: producer-side preprocessing declared to cdseg_attention_ex
+BLOCK_X_DEAD = 1  # include/cdseg.h: cdseg_block_io.flags / cdseg_attn_tail_rr_ex - the caller reads x no more
+TAIL_AUX_X_SKIPPED, TAIL_AUX_LOGITS = 1, 2  # aux word of a tail_rr_kernel route record
+_UNSUPPORTED = -4
 
 
 def attention(q, k, v, q_gidx, kv_gidx, widx, patch_start, num_heads, max_len, scale, out, work=0.0, flags=0):

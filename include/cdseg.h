@@ -584,6 +584,25 @@ int cdseg_cpe_head_rr(const void* y, int ldy, const void* head_img, const float*
 int cdseg_attn_tail_rr(const void* o, int ldo, const void* tail_img, const float* bp, const float* ln_g, const float* ln_b,
                        float eps, const float* b1, const float* b2, float* x, int ldx, void* xc, int ldxc, long n,
                        int channels, void* stream);
+/* The tail with a say in what it writes (cdseg_attn_tail_rr is this call with flags 0 and no logit arguments).  The tail is
+ * bound by HBM traffic: 4 C bytes of x and 2 C of xc per row are a third each of what it moves.
+ *   flags & CDSEG_BLOCK_X_DEAD: the caller will not read x after this call; its contents are UNSPECIFIED on return.  The
+ *     C = 32 / 64 kernel then leaves the rows as it read them and stores xc alone, bit-identical to the unflagged call; the
+ *     deep-stage tails (C >= 128) write x as always.
+ *   logits != NULL (C = 64): neither x nor xc is written (xc may be NULL); the kernel forms the segmentation head on the
+ *     final fp32 row it holds in registers, logits[out_idx ? out_idx[row] : row][k] = sum_c head_w[k][c] x[c] + head_b[k]
+ *     (head_w (num_classes, C) fp32 row-major, head_b (num_classes) fp32 or NULL, out_idx (n) as in cdseg_gemm_args: a
+ *     negative entry writes the row nowhere), operands and accumulation in fp32.  It needs num_classes % 4 == 0, the head's
+ *     weights in what the tail's workgroup has left of 80 KB of LDS (num_classes <= 20 at C = 64), logits 16-byte aligned and
+ *     ld_logits % 4 == 0; anything else is CDSEG_ERR_UNSUPPORTED before any launch, nothing written.
+ * Route record (cdseg_route_read): the kernel id stays tail_rr_kernel<C>; aux says what the launch left unwritten. */
+#define CDSEG_BLOCK_X_DEAD 1
+#define CDSEG_TAIL_AUX_X_SKIPPED 1 /* aux bit 0: the fp32 rows of x were not stored */
+#define CDSEG_TAIL_AUX_LOGITS 2    /* aux bit 1: the launch wrote the logits and neither x (bit 0 is set too) nor xc */
+int cdseg_attn_tail_rr_ex(const void* o, int ldo, const void* tail_img, const float* bp, const float* ln_g, const float* ln_b,
+                          float eps, const float* b1, const float* b2, float* x, int ldx, void* xc, int ldxc, long n,
+                          int channels, int flags, float* logits, int ld_logits, const float* head_w, const float* head_b,
+                          const int32_t* out_idx, int num_classes, void* stream);
 /* Deep stages only (C = 128 / 256 / 512): the same two launches with the residual rows READ from one buffer (x / x_in) and
  * WRITTEN to another (x_out / x; they may alias, which gives the in-place forms above).  With distinct buffers, launches of
  * few rows (a single scene's deep stages: 32-row tiles on a fraction of the CUs) cut a tile's weight stream over several
@@ -655,6 +674,20 @@ typedef struct cdseg_block_io {
   size_t scratch_bytes;
   unsigned long long* sat_counter; /* NULL, or (diagnostic, IEEE-half build): += clamped values seen in this Block's 16-bit
                                       buffers that reach memory (cdseg_count_saturated); costs a few extra launches */
+  /* What the caller reads of the Block's outputs (trailing fields, all zero = everything, as before they existed; see
+   * cdseg_attn_tail_rr_ex).  flags & CDSEG_BLOCK_X_DEAD: x is not read after this call and is UNSPECIFIED on return; ignored
+   * when xc_out aliases x (there is no second copy), honoured by the C = 32 / 64 register-resident tail, ignored by every other
+   * path.  logits .. ld_logits: the Block is the model's last and its tail writes the segmentation logits INSTEAD of x and
+   * xc_out, which are then both unspecified (xc_out must still be a valid pointer; the saturation diagnostic skips it).  Only
+   * the register-resident tail can: CDSEG_ERR_UNSUPPORTED, before any launch of the Block, when this call would take another
+   * path or the head does not fit (cdseg_attn_tail_rr_ex) - the caller then runs the Block without them and the head itself. */
+  int flags;
+  float* logits;           /* (rows, ld_logits) fp32 or NULL */
+  const float* head_w;     /* (num_classes, C) fp32 row-major */
+  const float* head_b;     /* (num_classes) fp32 or NULL */
+  const int32_t* out_idx;  /* (n) or NULL: Block row -> logits row */
+  int num_classes;
+  int ld_logits;
 } cdseg_block_io;
 
 size_t cdseg_block_scratch_bytes(const cdseg_block_desc* desc, long n);
