@@ -2,6 +2,7 @@
 // segment max (+folded BN, +GELU), stem convolution (Cin 4..6, VALU), GEMV for the timestep
 // MLP, Philox normal draws, casts.  16-byte vector loads/stores per lane, one pass over HBM.
 #include "common.h"
+#include "route.h"
 
 namespace {
 
@@ -377,12 +378,13 @@ int cdseg_layernorm(const void* x, int x_dtype, int ldx, const float* gamma, con
   dim3 grid((unsigned)((waves + wpb - 1) / wpb)), block(64 * wpb);
   hipStream_t s = (hipStream_t)stream;
 #define LN_LAUNCH(MV)                                                                                             \
+  cdseg_route_rec(cdseg_route_template_id<CDSEG_RF_LN, MV>(), rpw, c, 1, 0, 0, x_dtype << CDSEG_ROUTE_F_CT_SHIFT, tpr); \
   hipLaunchKernelGGL(layernorm_kernel<MV>, grid, block, 0, s, x, x_dtype, ldx, gamma, beta, eps, res, ldres, colbias, \
                      out, out_dtype, ldo, out2, out2_dtype, ldo2, m, c, tpr)
-  if (maxv <= 1) LN_LAUNCH(1);
-  else if (maxv <= 2) LN_LAUNCH(2);
-  else if (maxv <= 4) LN_LAUNCH(4);
-  else LN_LAUNCH(8);
+  if (maxv <= 1) { LN_LAUNCH(1); }
+  else if (maxv <= 2) { LN_LAUNCH(2); }
+  else if (maxv <= 4) { LN_LAUNCH(4); }
+  else { LN_LAUNCH(8); }
 #undef LN_LAUNCH
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;

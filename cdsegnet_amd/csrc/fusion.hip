@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "route.h"
 
 namespace {
 
@@ -189,10 +190,12 @@ int cdseg_fuse_gate_fwd(const float* s, const float* a, const float* m, const fl
     const int R = FG_THREADS / (c >> 2);
     long blocks = (rows + (long)R * 4 - 1) / ((long)R * 4);  // about four rows a thread
     blocks = blocks < 1 ? 1 : (blocks > FG_MAX_GRID ? FG_MAX_GRID : blocks);
+    cdseg_route_rec(CDSEG_RK_FG_FWD, 0, c, 1, 0, 0, CDSEG_ROUTE_F_VEC_OK | (CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT), 0);
     hipLaunchKernelGGL(fg_fwd_kernel, dim3((unsigned)blocks), dim3(FG_THREADS), 0, (hipStream_t)stream, p);
   } else {
     long blocks = (rows * c + (long)FG_THREADS * 4 - 1) / ((long)FG_THREADS * 4);  // about four elements a thread
     blocks = blocks < 1 ? 1 : (blocks > FG_MAX_GRID ? FG_MAX_GRID : blocks);
+    cdseg_route_rec(CDSEG_RK_FG_FWD_SCALAR, 0, c, 1, 0, 0, CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, 0);
     hipLaunchKernelGGL(fg_fwd_scalar_kernel, dim3((unsigned)blocks), dim3(FG_THREADS), 0, (hipStream_t)stream, p);
   }
   CDSEG_CHECK_LAUNCH();
@@ -216,10 +219,13 @@ int cdseg_fuse_gate_bwd(const float* dy, const float* s, const float* a, const f
   int blocks;
   fg_partition(rows, p.rows_per_block, blocks);
   hipStream_t q = (hipStream_t)stream;
-  if ((c & 3) == 0 && fg_aligned(15, dy, s, a, alpha, gamma, ds, da))
+  if ((c & 3) == 0 && fg_aligned(15, dy, s, a, alpha, gamma, ds, da)) {
+    cdseg_route_rec(CDSEG_RK_FG_BWD, 0, c, blocks, 0, 0, CDSEG_ROUTE_F_VEC_OK | (CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT), 0);
     hipLaunchKernelGGL(fg_bwd_kernel, dim3((unsigned)blocks), dim3(FG_THREADS), 0, q, p);
-  else
+  } else {
+    cdseg_route_rec(CDSEG_RK_FG_BWD_SCALAR, 0, c, blocks, 0, 0, CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, 0);
     hipLaunchKernelGGL(fg_bwd_scalar_kernel, dim3((unsigned)blocks), dim3(FG_THREADS), 0, q, p);
+  }
   CDSEG_CHECK_LAUNCH();
   hipLaunchKernelGGL(fg_reduce_kernel, dim3((unsigned)cdiv(2 * c, 64)), dim3(64), 0, q, (const double*)ws, blocks, c, sums);
   CDSEG_CHECK_LAUNCH();

@@ -26,6 +26,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "common.h"
+#include "route.h"
 
 namespace {
 
@@ -423,6 +424,8 @@ int cdseg_seg_loss_fwd(const float* logits, int ldl, const int64_t* labels, long
   if (tmp_need > tmp_bytes) return CDSEG_ERR_WORKSPACE;
 
   launch_by_width(c, [&](auto G, auto E) {
+    cdseg_route_rec(cdseg_route_template_id<CDSEG_RF_LOSS, decltype(G)::value, decltype(E)::value, 0>(), ROWS_PER_BLOCK, c, 1, 0, 0,
+                    CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, np);
     hipLaunchKernelGGL((loss_rows_kernel<decltype(G)::value, decltype(E)::value>), dim3(row_blocks), dim3(256), 0, s, logits, ldl,
                        labels, n, c, ignore_index, tab, np, k0, ce_part);
   });
@@ -452,6 +455,8 @@ int cdseg_seg_loss_bwd(const float* logits, int ldl, const int64_t* labels, long
   const int row_blocks = (int)((n + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK);
   const double inv_valid = 1.0 / (double)n_valid;
   launch_by_width(c, [&](auto G, auto E) {
+    cdseg_route_rec(cdseg_route_template_id<CDSEG_RF_LOSS, decltype(G)::value, decltype(E)::value, 1>(), ROWS_PER_BLOCK, c, 1, 0, 0,
+                    CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, np);
     hipLaunchKernelGGL((loss_bwd_kernel<decltype(G)::value, decltype(E)::value>), dim3(row_blocks), dim3(256), 0,
                        (hipStream_t)stream, logits, ldl, labels, n, c, ignore_index, tab, np, coef, g_ce, g_lovasz, inv_valid,
                        dlogits, lddl);

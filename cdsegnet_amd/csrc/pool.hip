@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "route.h"
 
 namespace {
 
@@ -307,7 +308,7 @@ __global__ void pool_pack_kernel(const bf16_t* __restrict__ w, uint4* __restrict
 }
 
 template <int CIN, int COUT, bool SCAN>
-int launch_pool(const PoolP& p, hipStream_t s) {
+int launch_pool(const PoolP& p, int fold_asked, hipStream_t s) {
   using K = PoolCfg<CIN, COUT>;
   static std::atomic<bool> attr_done{false};  // (a concurrent first call sets the attribute twice: harmless)
   if (!attr_done) {
@@ -319,6 +320,9 @@ int launch_pool(const PoolP& p, hipStream_t s) {
   long blocks = (chunks + PL_WAVES - 1) / PL_WAVES;
   const int per_cu = K::LDS > 80 * 1024 ? 1 : (K::LDS > 52 * 1024 ? 2 : 3);
   if (blocks > 256 * per_cu) blocks = 256 * per_cu;
+  // fix: the fold taken; aux: the fold asked for (POOL_FOLD_AUTO = the rule decided)
+  cdseg_route_rec(cdseg_route_template_id<CDSEG_RF_POOL, CIN, COUT, SCAN ? 1 : 0>(), 16, COUT, 1, SCAN ? POOL_FOLD_SCAN : POOL_FOLD_WALK, 0,
+                  CDSEG_BF16 << CDSEG_ROUTE_F_CT_SHIFT, fold_asked);
   hipLaunchKernelGGL((pool_fused_kernel<CIN, COUT, SCAN>), dim3((unsigned)blocks), dim3(PL_WAVES * 64), K::LDS, s, p);
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
@@ -366,8 +370,8 @@ int pool_fused_impl(const void* x, int ldx, long n_fine, const void* wimg, const
   const int fold = g_pool_fold.load(std::memory_order_relaxed);
   const bool scan = fold ? fold == POOL_FOLD_SCAN : n_fine >= POOL_SCAN_RATIO * m;
   hipStream_t s = (hipStream_t)stream;
-  if (cin == 32) return scan ? launch_pool<32, 64, true>(p, s) : launch_pool<32, 64, false>(p, s);
-  return scan ? launch_pool<64, 128, true>(p, s) : launch_pool<64, 128, false>(p, s);
+  if (cin == 32) return scan ? launch_pool<32, 64, true>(p, fold, s) : launch_pool<32, 64, false>(p, fold, s);
+  return scan ? launch_pool<64, 128, true>(p, fold, s) : launch_pool<64, 128, false>(p, fold, s);
 }
 
 }  // namespace
@@ -573,6 +577,7 @@ int launch_unpool(const UnpoolP& p, hipStream_t s) {
   long blocks = (chunks + PL_WAVES - 1) / PL_WAVES;
   const int per_cu = K::LDS > 80 * 1024 ? 1 : (K::LDS > 52 * 1024 ? 2 : 3);
   if (blocks > 256 * per_cu) blocks = 256 * per_cu;
+  cdseg_route_rec(cdseg_route_template_id<CDSEG_RF_UNPOOL, KS, KP>(), 16, 64, 1, 0, 0, CDSEG_BF16 << CDSEG_ROUTE_F_CT_SHIFT, 0);
   hipLaunchKernelGGL((unpool_fused_kernel<KS, KP>), dim3((unsigned)blocks), dim3(PL_WAVES * 64), K::LDS, s, p);
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;

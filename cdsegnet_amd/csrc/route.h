@@ -2,7 +2,8 @@
 // chooser picked, per host thread.  Host code only.  Off by default: a recording site then costs one thread-local test.
 //
 // ONE table names every kernel a chooser can launch; a kernel id is an index into it.  The recording sites take their ids
-// from this table (the GEMM arms by a compile-time search on their template arguments, the others by enumerator), and
+// from this table (the GEMM arms and the other template arms by a compile-time search on their template arguments, the rest by
+// enumerator), and
 // cdseg_route_catalog prints it: the catalogue cannot list a kernel the code does not name, nor the reverse.
 #pragma once
 #include <stdint.h>
@@ -78,18 +79,76 @@
   Z(ATTN_BWD_KV_DROP, "attn_bwd_kv_mfma_kernel<DropP>")               \
   Z(ATTN_BWD16_Q_DROP, "attn_bwd16_q_kernel<DropP>")                  \
   Z(ATTN_BWD16_KV_DROP, "attn_bwd16_kv_kernel<DropP>")                \
-  Z(DROPOUT_F32, "dropout_kernel")
+  Z(DROPOUT_F32, "dropout_kernel")                                    \
+  Z(ATTN_BWD_Q, "attn_bwd_q_mfma_kernel<>")                           \
+  Z(ATTN_BWD_KV, "attn_bwd_kv_mfma_kernel<>")                         \
+  Z(ATTN_BWD16_Q, "attn_bwd16_q_kernel<>")                            \
+  Z(ATTN_BWD16_KV, "attn_bwd16_kv_kernel<>")                          \
+  Z(WGRAD, "wgrad_kernel")                                            \
+  Z(WGRAD_DET, "wgrad_det_kernel")                                    \
+  Z(LN_BWD, "layernorm_bwd_kernel")                                   \
+  Z(LN_BWD_DET, "layernorm_bwd_det_kernel")                           \
+  Z(GATHER_FIRST_B16, "gather_first_kernel<b16>")                     \
+  Z(GATHER_FIRST_F32, "gather_first_kernel<f32>")                     \
+  Z(SCATTER_FIRST_ACC, "scatter_first_kernel<acc>")                   \
+  Z(SCATTER_FIRST_SET, "scatter_first_kernel<set>")                   \
+  Z(SCALE_CAST_B16, "scale_cast_kernel<b16>")                         \
+  Z(SCALE_CAST_F32, "scale_cast_kernel<f32>")                         \
+  Z(GELU_FWD_B16, "gelu_fwd_kernel<b16>")                             \
+  Z(GELU_FWD_F32, "gelu_fwd_kernel<f32>")                             \
+  Z(GELU_BWD_CAST_B16, "gelu_bwd_cast_kernel<b16>")                   \
+  Z(GELU_BWD_CAST_F32, "gelu_bwd_cast_kernel<f32>")                   \
+  Z(SK_STATS_B16, "sk_stats_kernel<b16>")                             \
+  Z(SK_STATS_F32, "sk_stats_kernel<f32>")                             \
+  Z(SK_STATS_SCALAR_B16, "sk_stats_scalar_kernel<b16>")               \
+  Z(SK_STATS_SCALAR_F32, "sk_stats_scalar_kernel<f32>")               \
+  Z(SK_FOLD_B16, "sk_fold_kernel<b16>")                               \
+  Z(SK_FOLD_F32, "sk_fold_kernel<f32>")                               \
+  Z(SK_MERGE, "sk_merge_kernel")                                      \
+  Z(SK_MERGE_SCALAR, "sk_merge_scalar_kernel")                        \
+  Z(FG_FWD, "fg_fwd_kernel")                                          \
+  Z(FG_FWD_SCALAR, "fg_fwd_scalar_kernel")                            \
+  Z(FG_BWD, "fg_bwd_kernel")                                          \
+  Z(FG_BWD_SCALAR, "fg_bwd_scalar_kernel")
+// the choosers outside the GEMM whose arms are template arguments: family, up to three arguments, name.  Their recording sites
+// find the id by a compile-time search on (family, arguments), like the GEMM arms
+#define CDSEG_ROUTE_TEMPLATE_KERNELS(T)                                                                       \
+  T(LN, 1, 0, 0, "layernorm_kernel<1>") T(LN, 2, 0, 0, "layernorm_kernel<2>")                                 \
+  T(LN, 4, 0, 0, "layernorm_kernel<4>") T(LN, 8, 0, 0, "layernorm_kernel<8>")                                 \
+  T(ADD_LN, 1, 1, 0, "add_layernorm_kernel<1,b16>") T(ADD_LN, 1, 0, 0, "add_layernorm_kernel<1,f32>")         \
+  T(ADD_LN, 2, 1, 0, "add_layernorm_kernel<2,b16>") T(ADD_LN, 2, 0, 0, "add_layernorm_kernel<2,f32>")         \
+  T(ADD_LN, 4, 1, 0, "add_layernorm_kernel<4,b16>") T(ADD_LN, 4, 0, 0, "add_layernorm_kernel<4,f32>")         \
+  T(ADD_LN, 8, 1, 0, "add_layernorm_kernel<8,b16>") T(ADD_LN, 8, 0, 0, "add_layernorm_kernel<8,f32>")         \
+  T(WGRAD16, 1, 1, 0, "wgrad16_kernel<1,1>") T(WGRAD16, 1, 2, 0, "wgrad16_kernel<1,2>")                       \
+  T(WGRAD16, 1, 4, 0, "wgrad16_kernel<1,4>") T(WGRAD16, 2, 1, 0, "wgrad16_kernel<2,1>")                       \
+  T(WGRAD16, 2, 2, 0, "wgrad16_kernel<2,2>") T(WGRAD16, 2, 4, 0, "wgrad16_kernel<2,4>")                       \
+  T(WGRAD16, 4, 1, 0, "wgrad16_kernel<4,1>") T(WGRAD16, 4, 2, 0, "wgrad16_kernel<4,2>")                       \
+  T(WGRAD16, 1, 1, 1, "wgrad16_det_kernel<1,1>") T(WGRAD16, 1, 2, 1, "wgrad16_det_kernel<1,2>")               \
+  T(WGRAD16, 1, 4, 1, "wgrad16_det_kernel<1,4>") T(WGRAD16, 2, 1, 1, "wgrad16_det_kernel<2,1>")               \
+  T(WGRAD16, 2, 2, 1, "wgrad16_det_kernel<2,2>") T(WGRAD16, 2, 4, 1, "wgrad16_det_kernel<2,4>")               \
+  T(WGRAD16, 4, 1, 1, "wgrad16_det_kernel<4,1>") T(WGRAD16, 4, 2, 1, "wgrad16_det_kernel<4,2>")               \
+  T(POOL, 32, 64, 0, "pool_fused_kernel<32,64,walk>") T(POOL, 32, 64, 1, "pool_fused_kernel<32,64,scan>")     \
+  T(POOL, 64, 128, 0, "pool_fused_kernel<64,128,walk>") T(POOL, 64, 128, 1, "pool_fused_kernel<64,128,scan>") \
+  T(UNPOOL, 32, 64, 0, "unpool_fused_kernel<32,64>") T(UNPOOL, 64, 128, 0, "unpool_fused_kernel<64,128>")     \
+  T(LOSS, 16, 1, 0, "loss_rows_kernel<16,1>") T(LOSS, 16, 2, 0, "loss_rows_kernel<16,2>")                     \
+  T(LOSS, 64, 1, 0, "loss_rows_kernel<64,1>") T(LOSS, 64, 2, 0, "loss_rows_kernel<64,2>")                     \
+  T(LOSS, 64, 4, 0, "loss_rows_kernel<64,4>")                                                                 \
+  T(LOSS, 16, 1, 1, "loss_bwd_kernel<16,1>") T(LOSS, 16, 2, 1, "loss_bwd_kernel<16,2>")                       \
+  T(LOSS, 64, 1, 1, "loss_bwd_kernel<64,1>") T(LOSS, 64, 2, 1, "loss_bwd_kernel<64,2>")                       \
+  T(LOSS, 64, 4, 1, "loss_bwd_kernel<64,4>")
 
 enum {
   CDSEG_RT_b16 = 0, CDSEG_RT_f32 = 1, CDSEG_RT_x3 = 2,
   CDSEG_RT_kshort = 0, CDSEG_RT_klong = 1,
   CDSEG_RT_plain = 0, CDSEG_RT_gather = 1,
   CDSEG_RT_ring = 0, CDSEG_RT_sq = 1,
+  // families of CDSEG_ROUTE_TEMPLATE_KERNELS
+  CDSEG_RF_LN = 0, CDSEG_RF_ADD_LN = 1, CDSEG_RF_WGRAD16 = 2, CDSEG_RF_POOL = 3, CDSEG_RF_UNPOOL = 4, CDSEG_RF_LOSS = 5,
 };
 
 struct CdsegRouteEntry {
   const char* name;
-  int key;  // GEMM arms: their template arguments, packed (0 for the kernels addressed by enumerator)
+  int key;  // GEMM and template arms: their template arguments, packed (0 for the kernels addressed by enumerator)
 };
 
 constexpr int cdseg_route_gemm_key(int ct, int bn, int klong, int gather, int bm) {
@@ -97,6 +156,9 @@ constexpr int cdseg_route_gemm_key(int ct, int bn, int klong, int gather, int bm
 }
 constexpr int cdseg_route_dma_key(int bm, int gather, int bn, int stages, int sq) {
   return (2 << 28) | (stages << 24) | (sq << 23) | (gather << 22) | ((bn / 32) << 12) | (bm / 32);
+}
+constexpr int cdseg_route_template_key(int family, int a, int b, int c) {
+  return (3 << 28) | (family << 24) | (a << 12) | (b << 4) | c;  // a <= 64, b <= 128, c <= 1
 }
 
 inline constexpr CdsegRouteEntry kCdsegRouteTable[] = {
@@ -111,6 +173,9 @@ inline constexpr CdsegRouteEntry kCdsegRouteTable[] = {
 #define CDSEG_RZ(sym, name) {name, 0},
     CDSEG_ROUTE_OTHER_KERNELS(CDSEG_RZ)
 #undef CDSEG_RZ
+#define CDSEG_RT(fam, a, b, c, name) {name, cdseg_route_template_key(CDSEG_RF_##fam, a, b, c)},
+    CDSEG_ROUTE_TEMPLATE_KERNELS(CDSEG_RT)
+#undef CDSEG_RT
 };
 constexpr int kCdsegRouteCount = (int)(sizeof(kCdsegRouteTable) / sizeof(kCdsegRouteTable[0]));
 
@@ -131,6 +196,9 @@ enum {
 #define CDSEG_RZ(sym, name) CDSEG_RK_##sym,
   CDSEG_ROUTE_OTHER_KERNELS(CDSEG_RZ)
 #undef CDSEG_RZ
+#define CDSEG_RT(fam, a, b, c, name) CDSEG_RK_T_##fam##_##a##_##b##_##c,
+  CDSEG_ROUTE_TEMPLATE_KERNELS(CDSEG_RT)
+#undef CDSEG_RT
   CDSEG_RK_COUNT
 };
 static_assert(CDSEG_RK_COUNT == kCdsegRouteCount, "one table");
@@ -148,10 +216,20 @@ constexpr int cdseg_route_dma_id() {
   static_assert(id >= 0, "gemm_dma_kernel instantiation missing from CDSEG_ROUTE_DMA_KERNELS");
   return id;
 }
+// ids of the template arms outside the GEMM, the same way
+template <int FAMILY, int A, int B = 0, int C = 0>
+constexpr int cdseg_route_template_id() {
+  constexpr int id = cdseg_route_find(cdseg_route_template_key(FAMILY, A, B, C));
+  static_assert(id >= 0, "kernel instantiation missing from CDSEG_ROUTE_TEMPLATE_KERNELS");
+  return id;
+}
 
 extern thread_local bool tl_cdseg_route_on;
 void cdseg_route_push(int id, int bm, int bn, int splits, int fix, int xmode, int flags, int aux);
 void cdseg_route_or_flags(int flags);  // into the newest record of this thread
+
+// rows per split of a weight-gradient launch, for the xmode word of its record
+constexpr int cdseg_route_rows(long rows) { return rows > 0x7fffffffL ? 0x7fffffff : (int)rows; }
 
 // the recording site: immediately before the hipLaunchKernelGGL it describes
 static inline void cdseg_route_rec(int id, int bm, int bn, int splits, int fix, int xmode, int flags, int aux) {

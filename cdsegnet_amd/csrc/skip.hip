@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "route.h"
 
 namespace {
 
@@ -285,14 +286,20 @@ int cdseg_skip_stats(const void* x, int dtype, int ldx, long n, int c, const int
   sk_partition(n, p.rows_per_chunk, chunks);
   hipStream_t q = (hipStream_t)stream;
   const bool vec = (c & 3) == 0 && (ldx & 3) == 0 && sk_aligned(lp ? 7 : 15, x);
-  if (vec && lp)
+  const int rflags = (vec ? CDSEG_ROUTE_F_VEC_OK : 0) | (dtype << CDSEG_ROUTE_F_CT_SHIFT);
+  if (vec && lp) {
+    cdseg_route_rec(CDSEG_RK_SK_STATS_B16, 0, c, chunks, 0, 0, rflags, 0);
     hipLaunchKernelGGL(sk_stats_kernel<true>, dim3((unsigned)chunks), dim3(SK_THREADS), 0, q, p);
-  else if (vec)
+  } else if (vec) {
+    cdseg_route_rec(CDSEG_RK_SK_STATS_F32, 0, c, chunks, 0, 0, rflags, 0);
     hipLaunchKernelGGL(sk_stats_kernel<false>, dim3((unsigned)chunks), dim3(SK_THREADS), 0, q, p);
-  else if (lp)
+  } else if (lp) {
+    cdseg_route_rec(CDSEG_RK_SK_STATS_SCALAR_B16, 0, c, chunks, 0, 0, rflags, 0);
     hipLaunchKernelGGL(sk_stats_scalar_kernel<true>, dim3((unsigned)chunks), dim3(SK_THREADS), 0, q, p);
-  else
+  } else {
+    cdseg_route_rec(CDSEG_RK_SK_STATS_SCALAR_F32, 0, c, chunks, 0, 0, rflags, 0);
     hipLaunchKernelGGL(sk_stats_scalar_kernel<false>, dim3((unsigned)chunks), dim3(SK_THREADS), 0, q, p);
+  }
   CDSEG_CHECK_LAUNCH();
   hipLaunchKernelGGL(sk_reduce_kernel, dim3((unsigned)cdiv(3 * c, 16)), dim3(256), 0, q, (const double*)ws, chunks, 3 * c, stats);
   CDSEG_CHECK_LAUNCH();
@@ -304,10 +311,13 @@ int cdseg_skip_fold(const void* w, int dtype, int ldw, int cout, int cin, const 
   if (sk_width_status(cin) != CDSEG_OK || sk_width_status(cout) != CDSEG_OK) return CDSEG_ERR_UNSUPPORTED;
   const bool lp = dtype == CDSEG_BF16;
   if (!w || !stats || !u || ldw < cin || !sk_aligned(lp ? 1 : 3, w) || !sk_aligned(7, stats) || !sk_aligned(7, u)) return CDSEG_ERR_ARG;
-  if (lp)
+  if (lp) {
+    cdseg_route_rec(CDSEG_RK_SK_FOLD_B16, cout, cin, 1, 0, 0, CDSEG_BF16 << CDSEG_ROUTE_F_CT_SHIFT, 0);
     hipLaunchKernelGGL(sk_fold_kernel<true>, dim3((unsigned)cout), dim3(64), 0, (hipStream_t)stream, w, ldw, cin, cout, stats, u);
-  else
+  } else {
+    cdseg_route_rec(CDSEG_RK_SK_FOLD_F32, cout, cin, 1, 0, 0, CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, 0);
     hipLaunchKernelGGL(sk_fold_kernel<false>, dim3((unsigned)cout), dim3(64), 0, (hipStream_t)stream, w, ldw, cin, cout, stats, u);
+  }
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
 }
@@ -335,10 +345,12 @@ int cdseg_skip_merge(float* x, int ldx, long n, int c, const double* stats, int 
     const int R = SK_THREADS / (c >> 2);
     long blocks = (n + (long)R * 4 - 1) / ((long)R * 4);  // about four rows a thread
     blocks = blocks < 1 ? 1 : (blocks > SK_MAX_GRID ? SK_MAX_GRID : blocks);
+    cdseg_route_rec(CDSEG_RK_SK_MERGE, 0, c, 1, 0, 0, CDSEG_ROUTE_F_VEC_OK | (CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT), 0);
     hipLaunchKernelGGL(sk_merge_kernel, dim3((unsigned)blocks), dim3(SK_THREADS), 0, (hipStream_t)stream, p);
   } else {
     long blocks = (n * c + (long)SK_THREADS * 4 - 1) / ((long)SK_THREADS * 4);
     blocks = blocks < 1 ? 1 : (blocks > SK_MAX_GRID ? SK_MAX_GRID : blocks);
+    cdseg_route_rec(CDSEG_RK_SK_MERGE_SCALAR, 0, c, 1, 0, 0, CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, 0);
     hipLaunchKernelGGL(sk_merge_scalar_kernel, dim3((unsigned)blocks), dim3(SK_THREADS), 0, (hipStream_t)stream, p);
   }
   CDSEG_CHECK_LAUNCH();

@@ -1054,7 +1054,9 @@ static int attention_bwd_launch(const void* q, const void* k, const void* v, int
       CDSEG_CHECK_LAUNCH();
       return CDSEG_OK;
     }
+    cdseg_route_rec(CDSEG_RK_ATTN_BWD16_Q, 32, 32, split, 0, 0, CDSEG_BF16 << CDSEG_ROUTE_F_CT_SHIFT, B16_WAVES);
     hipLaunchKernelGGL(attn_bwd16_q_kernel<>, grid16, dim3(B16_WAVES * 64), B16_Q_LDS, s, p);
+    cdseg_route_rec(CDSEG_RK_ATTN_BWD16_KV, 32, 32, split, 0, 0, CDSEG_BF16 << CDSEG_ROUTE_F_CT_SHIFT, B16_WAVES);
     hipLaunchKernelGGL(attn_bwd16_kv_kernel<>, grid16, dim3(B16_WAVES * 64), B16_KV_LDS, s, p);
     CDSEG_CHECK_LAUNCH();
     return CDSEG_OK;
@@ -1087,7 +1089,9 @@ static int attention_bwd_launch(const void* q, const void* k, const void* v, int
     CDSEG_CHECK_LAUNCH();
     return CDSEG_OK;
   }
+  cdseg_route_rec(CDSEG_RK_ATTN_BWD_Q, 16, 16, 1, 0, 0, CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, BW_WAVES);
   hipLaunchKernelGGL(attn_bwd_q_mfma_kernel<>, grid, dim3(BW_WAVES * 64), BW_Q_LDS, s, p);
+  cdseg_route_rec(CDSEG_RK_ATTN_BWD_KV, 16, 16, 1, 0, 0, CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, BW_WAVES);
   hipLaunchKernelGGL(attn_bwd_kv_mfma_kernel<>, grid, dim3(BW_WAVES * 64), BW_KV_LDS, s, p);
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
@@ -1130,6 +1134,7 @@ extern "C" int cdseg_layernorm_bwd(const float* x, int ldx, const float* gamma, 
   if (m <= 0) return CDSEG_OK;
   if (c <= 0 || !x || !gamma || !dy || !dx) return CDSEG_ERR_ARG;
   if (!f32_aligned(x, gamma, dy, dx, dgamma, dbeta)) return CDSEG_ERR_ARG;
+  cdseg_route_rec(CDSEG_RK_LN_BWD, 4 * LNB_ROWS, c, 1, 0, 0, CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, 0);
   hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((unsigned)cdiv(m, 4 * LNB_ROWS)), dim3(256), 0, (hipStream_t)stream, x, ldx, gamma, eps, dy,
                      lddy, dx, lddx, accumulate, dgamma, dbeta, m, c);
   CDSEG_CHECK_LAUNCH();
@@ -1162,9 +1167,11 @@ static int launch_wgrad(WgradP p, int noff, hipStream_t stream, float* ws = null
   const dim3 grid((unsigned)cdiv(p.N, 64), (unsigned)cdiv(p.K, 64), (unsigned)(q.splits * noff));
   if (ws) {
     float* ws_db = ws + (size_t)noff * q.splits * p.N * p.K;
+    cdseg_route_rec(CDSEG_RK_WGRAD_DET, 64, 64, q.splits, 0, cdseg_route_rows(q.rows_per_split), CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, noff);
     hipLaunchKernelGGL(wgrad_det_kernel, grid, dim3(256), 0, stream, p, ws, ws_db);
     launch_wgrad_reduce(ws, ws_db, p.dw, p.db, p.N, p.K, p.lddw, q.splits, noff, p.dw_off_stride, stream);
   } else {
+    cdseg_route_rec(CDSEG_RK_WGRAD, 64, 64, q.splits, 0, cdseg_route_rows(q.rows_per_split), CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, noff);
     hipLaunchKernelGGL(wgrad_kernel, grid, dim3(256), 0, stream, p);
   }
   CDSEG_CHECK_LAUNCH();
@@ -1196,8 +1203,15 @@ extern "C" int cdseg_conv_wgrad(const float* x, int ldx, const int32_t* nbr_kmaj
 template <int TN, int TK>
 static void launch_wgrad16_tile(const Wgrad16P& p, int noff, hipStream_t stream, float* ws_dw, float* ws_db) {
   const dim3 grid((unsigned)cdiv(p.N, 32 * TN), (unsigned)cdiv(p.K, 32 * TK), (unsigned)(p.splits * noff));
-  if (ws_dw) hipLaunchKernelGGL((wgrad16_det_kernel<TN, TK>), grid, dim3(256), 0, stream, p, ws_dw, ws_db);
-  else hipLaunchKernelGGL((wgrad16_kernel<TN, TK>), grid, dim3(256), 0, stream, p);
+  if (ws_dw) {
+    cdseg_route_rec(cdseg_route_template_id<CDSEG_RF_WGRAD16, TN, TK, 1>(), 32 * TN, 32 * TK, p.splits, 0, cdseg_route_rows(p.rows_per_split),
+                    CDSEG_BF16 << CDSEG_ROUTE_F_CT_SHIFT, noff);
+    hipLaunchKernelGGL((wgrad16_det_kernel<TN, TK>), grid, dim3(256), 0, stream, p, ws_dw, ws_db);
+  } else {
+    cdseg_route_rec(cdseg_route_template_id<CDSEG_RF_WGRAD16, TN, TK, 0>(), 32 * TN, 32 * TK, p.splits, 0, cdseg_route_rows(p.rows_per_split),
+                    CDSEG_BF16 << CDSEG_ROUTE_F_CT_SHIFT, noff);
+    hipLaunchKernelGGL((wgrad16_kernel<TN, TK>), grid, dim3(256), 0, stream, p);
+  }
 }
 
 // Tile: the narrowest of 32 / 64 / 128 columns that covers N (K), so the narrow stages read dY and X once (C = 32: dW 96 x 32
@@ -1324,6 +1338,7 @@ extern "C" int cdseg_layernorm_bwd_det(const float* x, int ldx, const float* gam
   if (((uintptr_t)ws & 3) != 0) return CDSEG_ERR_ARG;
   if (!ws || ws_bytes < cdseg_layernorm_bwd_det_ws_bytes(m, c)) return CDSEG_ERR_WORKSPACE;
   const long nblocks = cdseg_wgrad::ln_blocks(m);
+  cdseg_route_rec(CDSEG_RK_LN_BWD_DET, 0, c, (int)nblocks, 0, 0, CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, 0);
   hipLaunchKernelGGL(layernorm_bwd_det_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, x, ldx, gamma, eps, dy, lddy,
                      dx, lddx, accumulate, m, c, (float*)ws);
   if (dgamma || dbeta)

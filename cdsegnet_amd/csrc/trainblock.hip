@@ -13,6 +13,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "route.h"
 #include "workspace.h"
 
 namespace {
@@ -671,8 +672,13 @@ extern "C" int cdseg_gather_first(const float* x, const int32_t* row_start, void
   if (!x || !row_start || !out || c <= 0 || (c & 3) || !al16(x) || !al16(out) || ((uintptr_t)row_start & 3)) return CDSEG_ERR_ARG;
   if (out_dtype != CDSEG_F32 && out_dtype != CDSEG_BF16) return CDSEG_ERR_ARG;
   const dim3 grid(row_grid(nv * (c >> 2))), block(ROW_BLOCK);
-  if (out_dtype == CDSEG_BF16) hipLaunchKernelGGL(gather_first_kernel<true>, grid, block, 0, (hipStream_t)stream, x, row_start, out, nv, c);
-  else hipLaunchKernelGGL(gather_first_kernel<false>, grid, block, 0, (hipStream_t)stream, x, row_start, out, nv, c);
+  if (out_dtype == CDSEG_BF16) {
+    cdseg_route_rec(CDSEG_RK_GATHER_FIRST_B16, 0, c, 1, 0, 0, CDSEG_BF16 << CDSEG_ROUTE_F_CT_SHIFT, 0);
+    hipLaunchKernelGGL(gather_first_kernel<true>, grid, block, 0, (hipStream_t)stream, x, row_start, out, nv, c);
+  } else {
+    cdseg_route_rec(CDSEG_RK_GATHER_FIRST_F32, 0, c, 1, 0, 0, CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, 0);
+    hipLaunchKernelGGL(gather_first_kernel<false>, grid, block, 0, (hipStream_t)stream, x, row_start, out, nv, c);
+  }
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
 }
@@ -706,8 +712,13 @@ extern "C" int cdseg_scatter_first(const float* g, const int32_t* row_vox, const
       (((uintptr_t)row_vox | (uintptr_t)row_start) & 3))
     return CDSEG_ERR_ARG;
   const dim3 grid(row_grid(n * (c >> 2))), block(ROW_BLOCK);
-  if (accumulate) hipLaunchKernelGGL(scatter_first_kernel<true>, grid, block, 0, (hipStream_t)stream, g, row_vox, row_start, dx, n, c);
-  else hipLaunchKernelGGL(scatter_first_kernel<false>, grid, block, 0, (hipStream_t)stream, g, row_vox, row_start, dx, n, c);
+  if (accumulate) {
+    cdseg_route_rec(CDSEG_RK_SCATTER_FIRST_ACC, 0, c, 1, 0, 0, CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, 0);
+    hipLaunchKernelGGL(scatter_first_kernel<true>, grid, block, 0, (hipStream_t)stream, g, row_vox, row_start, dx, n, c);
+  } else {
+    cdseg_route_rec(CDSEG_RK_SCATTER_FIRST_SET, 0, c, 1, 0, 0, CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, 0);
+    hipLaunchKernelGGL(scatter_first_kernel<false>, grid, block, 0, (hipStream_t)stream, g, row_vox, row_start, dx, n, c);
+  }
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
 }
@@ -717,8 +728,13 @@ extern "C" int cdseg_scale_cast(const float* dy, const float* mask, void* out, i
   if (!dy || !out || c <= 0 || (c & 3) || !al16(dy) || !al16(out)) return CDSEG_ERR_ARG;
   if (out_dtype != CDSEG_F32 && out_dtype != CDSEG_BF16) return CDSEG_ERR_ARG;
   const dim3 grid(row_grid(n * (c >> 2))), block(ROW_BLOCK);
-  if (out_dtype == CDSEG_BF16) hipLaunchKernelGGL(scale_cast_kernel<true>, grid, block, 0, (hipStream_t)stream, dy, mask, out, n, c);
-  else hipLaunchKernelGGL(scale_cast_kernel<false>, grid, block, 0, (hipStream_t)stream, dy, mask, out, n, c);
+  if (out_dtype == CDSEG_BF16) {
+    cdseg_route_rec(CDSEG_RK_SCALE_CAST_B16, 0, c, 1, 0, 0, CDSEG_BF16 << CDSEG_ROUTE_F_CT_SHIFT, 0);
+    hipLaunchKernelGGL(scale_cast_kernel<true>, grid, block, 0, (hipStream_t)stream, dy, mask, out, n, c);
+  } else {
+    cdseg_route_rec(CDSEG_RK_SCALE_CAST_F32, 0, c, 1, 0, 0, CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, 0);
+    hipLaunchKernelGGL(scale_cast_kernel<false>, grid, block, 0, (hipStream_t)stream, dy, mask, out, n, c);
+  }
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
 }
@@ -739,10 +755,13 @@ extern "C" int cdseg_add_layernorm(const float* x, const float* a, const float* 
   hipStream_t s = (hipStream_t)stream;
 #define ALN_LAUNCH(MV)                                                                                                        \
   do {                                                                                                                        \
-    if (out_dtype == CDSEG_BF16)                                                                                              \
+    if (out_dtype == CDSEG_BF16) {                                                                                            \
+      cdseg_route_rec(cdseg_route_template_id<CDSEG_RF_ADD_LN, MV, 1>(), rpw, c, 1, 0, 0, CDSEG_BF16 << CDSEG_ROUTE_F_CT_SHIFT, tpr); \
       hipLaunchKernelGGL((add_layernorm_kernel<MV, true>), grid, block, 0, s, x, a, mask, gamma, beta, eps, x1, h, n, c, tpr); \
-    else                                                                                                                      \
+    } else {                                                                                                                  \
+      cdseg_route_rec(cdseg_route_template_id<CDSEG_RF_ADD_LN, MV, 0>(), rpw, c, 1, 0, 0, CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, tpr); \
       hipLaunchKernelGGL((add_layernorm_kernel<MV, false>), grid, block, 0, s, x, a, mask, gamma, beta, eps, x1, h, n, c, tpr); \
+    }                                                                                                                         \
   } while (0)
   if (maxv <= 1) ALN_LAUNCH(1);
   else if (maxv <= 2) ALN_LAUNCH(2);
@@ -759,8 +778,13 @@ extern "C" int cdseg_gelu_fwd(const float* u, void* g, int out_dtype, long count
   if (out_dtype != CDSEG_F32 && out_dtype != CDSEG_BF16) return CDSEG_ERR_ARG;
   const long nchunks = count >> 2;
   const dim3 grid(row_grid(nchunks)), block(ROW_BLOCK);
-  if (out_dtype == CDSEG_BF16) hipLaunchKernelGGL(gelu_fwd_kernel<true>, grid, block, 0, (hipStream_t)stream, u, g, nchunks);
-  else hipLaunchKernelGGL(gelu_fwd_kernel<false>, grid, block, 0, (hipStream_t)stream, u, g, nchunks);
+  if (out_dtype == CDSEG_BF16) {
+    cdseg_route_rec(CDSEG_RK_GELU_FWD_B16, 0, 0, 1, 0, 0, CDSEG_BF16 << CDSEG_ROUTE_F_CT_SHIFT, 0);
+    hipLaunchKernelGGL(gelu_fwd_kernel<true>, grid, block, 0, (hipStream_t)stream, u, g, nchunks);
+  } else {
+    cdseg_route_rec(CDSEG_RK_GELU_FWD_F32, 0, 0, 1, 0, 0, CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, 0);
+    hipLaunchKernelGGL(gelu_fwd_kernel<false>, grid, block, 0, (hipStream_t)stream, u, g, nchunks);
+  }
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
 }
@@ -771,8 +795,13 @@ extern "C" int cdseg_gelu_bwd_cast(const float* u, const float* dg, void* du, in
   if (out_dtype != CDSEG_F32 && out_dtype != CDSEG_BF16) return CDSEG_ERR_ARG;
   const long nchunks = count >> 2;
   const dim3 grid(row_grid(nchunks)), block(ROW_BLOCK);
-  if (out_dtype == CDSEG_BF16) hipLaunchKernelGGL(gelu_bwd_cast_kernel<true>, grid, block, 0, (hipStream_t)stream, u, dg, du, nchunks);
-  else hipLaunchKernelGGL(gelu_bwd_cast_kernel<false>, grid, block, 0, (hipStream_t)stream, u, dg, du, nchunks);
+  if (out_dtype == CDSEG_BF16) {
+    cdseg_route_rec(CDSEG_RK_GELU_BWD_CAST_B16, 0, 0, 1, 0, 0, CDSEG_BF16 << CDSEG_ROUTE_F_CT_SHIFT, 0);
+    hipLaunchKernelGGL(gelu_bwd_cast_kernel<true>, grid, block, 0, (hipStream_t)stream, u, dg, du, nchunks);
+  } else {
+    cdseg_route_rec(CDSEG_RK_GELU_BWD_CAST_F32, 0, 0, 1, 0, 0, CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, 0);
+    hipLaunchKernelGGL(gelu_bwd_cast_kernel<false>, grid, block, 0, (hipStream_t)stream, u, dg, du, nchunks);
+  }
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
 }

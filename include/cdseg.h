@@ -275,6 +275,11 @@ long cdseg_attention_schedule(int num_patches, int num_heads, int max_len, int d
  *   tile mapping, 0 / 1 / 2); [6] flags; [7] aux: the deep-stage head / tail: workgroups per row tile (the head, when it
  *   reads the conv's split-K partial planes: | their count << 8); attention: waves per block; fused MLP / tail / head: rows
  *   per workgroup; sparse conv: waves per block.
+ *   The training, level and elementwise choosers: LayerNorm / add + LayerNorm: [1] rows per wave, [2] c, [7] lanes per row
+ *   (tpr), the compute-type bits = the dtype of x / of h; weight gradients: [1] x [2] the dW tile, [3] row splits, [5] rows per
+ *   split (not cdseg_gemm's xmode), [7] kernel offsets; attention backward: [3] slices of a patch-head, [7] waves per block;
+ *   cdseg_pool_fused: [4] the fold taken (1 walk / 2 scan), [7] the fold asked for (0 = the rule decided); the segmentation
+ *   loss: [2] c, [7] classes present; skip statistics: [3] row chunks; skip / fusion row kernels: F_VEC_OK = the 16-byte arm.
  * cdseg_route_enable: returns the previous state.  cdseg_route_clear: forget this thread's records.  cdseg_route_read: the
  * number of launches recorded since the last clear (may exceed both the ring and `capacity`); writes the newest
  * min(count, 64, capacity) records, oldest first (rec may be NULL with capacity 0).  cdseg_route_catalog: the names of every

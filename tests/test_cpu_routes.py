@@ -12,6 +12,26 @@ from cdsegnet_amd import _lib, ops
 
 RING = 64  # include/cdseg.h: "a ring of the newest 64 launches"
 
+_TILES16 = ("1,1>", "1,2>", "1,4>", "2,1>", "2,2>", "2,4>", "4,1>", "4,2>")  # csrc/wgrad_partition.h partition_16
+_WIDTHS = ("16,1>", "16,2>", "64,1>", "64,2>", "64,4>")                      # csrc/loss.hip launch_by_width
+_LP = ("b16>", "f32>")
+OTHER_FAMILIES = {
+    "layernorm_kernel<": ("1>", "2>", "4>", "8>"),
+    "add_layernorm_kernel<": tuple(f"{mv},{t}" for mv in (1, 2, 4, 8) for t in _LP),
+    "gather_first_kernel<": _LP, "scatter_first_kernel<": ("acc>", "set>"), "scale_cast_kernel<": _LP,
+    "gelu_fwd_kernel<": _LP, "gelu_bwd_cast_kernel<": _LP,
+    "wgrad_kernel": ("",), "wgrad_det_kernel": ("",), "wgrad16_kernel<": _TILES16, "wgrad16_det_kernel<": _TILES16,
+    "attn_bwd_q_mfma_kernel<": (">", "DropP>"), "attn_bwd_kv_mfma_kernel<": (">", "DropP>"),
+    "attn_bwd16_q_kernel<": (">", "DropP>"), "attn_bwd16_kv_kernel<": (">", "DropP>"),
+    "layernorm_bwd_kernel": ("",), "layernorm_bwd_det_kernel": ("",),
+    "pool_fused_kernel<": ("32,64,walk>", "32,64,scan>", "64,128,walk>", "64,128,scan>"),
+    "unpool_fused_kernel<": ("32,64>", "64,128>"),
+    "loss_rows_kernel<": _WIDTHS, "loss_bwd_kernel<": _WIDTHS,
+    "sk_stats_kernel<": _LP, "sk_stats_scalar_kernel<": _LP, "sk_fold_kernel<": _LP, "sk_merge_kernel": ("",),
+    "sk_merge_scalar_kernel": ("",),
+    "fg_fwd_kernel": ("",), "fg_fwd_scalar_kernel": ("",), "fg_bwd_kernel": ("",), "fg_bwd_scalar_kernel": ("",),
+}
+
 
 @pytest.fixture(scope="module", params=_lib.VARIANTS)
 def lib(request):
@@ -49,6 +69,9 @@ def test_catalogue_names_are_unique_and_the_same_in_both_builds(lib):
     for family in ("gemm_kernel<", "gemm_dma_kernel<", "mlp_fused_kernel<", "cpe_head_fused_kernel<", "cpe_head_stream_kernel<",
                    "deep_head_kernel<", "deep_tail_kernel<", "head_rr_kernel<", "tail_rr_kernel<", "conv_ll_kernel<", "attn_"):
         assert any(n.startswith(family) for n in names), family
+    # the choosers outside the GEMM and the Block: family -> the instantiations its launcher can pick, every one of them
+    for family, arms in OTHER_FAMILIES.items():
+        assert sorted(n for n in names if n.startswith(family)) == sorted(family + a for a in arms), family
     # a buffer that is too small is left alone; the size asked for is the size needed
     need = lib.cdseg_route_catalog(None, 0)
     assert need == len("\n".join(names)) + 1

@@ -153,9 +153,14 @@ def test_gradients_vs_fp64_within_twice_the_reference_rounding(ops, lp, name, le
     lpt = LP()
     rng = np.random.default_rng(sum(lens) + 31 * H + dup)
     launch, (q16, k16, v16, do16) = _case(lens, H, dup, cross, lpt, rng, sigma_k)
-    got = _kernel(lpt, q16, k16, v16, do16, launch, H, packed=packed)
+    with ops.record_routes() as rr:
+        got = _kernel(lpt, q16, k16, v16, do16, launch, H, packed=packed)
     worst = _compare(name, got, launch, q16, k16, v16, do16, H, lpt)
     report(f"attn bwd16 {name} worst ratio ({lp})", ratio=worst)
+    # the launch record: the plain pair, every patch-head cut in four (at most 24 patch-heads here: 24 * 4 * 2 <= 512)
+    assert len(lens) * H <= 24
+    assert rr.count == 2 and rr.kernels() == ["attn_bwd16_q_kernel<>", "attn_bwd16_kv_kernel<>"], rr.routes
+    assert all(r.splits == 4 and r.compute == ops.BF16 for r in rr.routes), rr.routes
 
 
 @LPS

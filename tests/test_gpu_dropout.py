@@ -678,14 +678,15 @@ def test_the_model_honours_attn_drop_and_proj_drop(ops, monkeypatch):
 
 @LPS
 def test_the_new_kernels_record_their_routes(ops, lp):
-    """The launch record names the dropout kernels (appended at the end of the catalogue: earlier ids keep their meaning), and
-    a rate whose threshold is 256 records the existing forward kernel."""
+    """The launch record names the dropout kernels (appended to the catalogue as it was then: earlier ids keep their meaning),
+    and a rate whose threshold is 256 records the existing forward kernel and the plain backward pair."""
     rng = np.random.default_rng(4)
     launch, (q, k, v, do) = _case([130, 64], 2, 0, False, LP(), rng, 1.0)
     names = O.route_catalog()
     new = ["attn_drop_f32_kernel", "attn_drop16_kernel", "attn_bwd_q_mfma_kernel<DropP>", "attn_bwd_kv_mfma_kernel<DropP>",
            "attn_bwd16_q_kernel<DropP>", "attn_bwd16_kv_kernel<DropP>", "dropout_kernel"]
-    assert names[-len(new):] == new and names[-len(new) - 1] == "attn_f32_kernel"
+    at = names.index(new[0])  # (in one block behind the forward attention kernels; later work appended behind them)
+    assert names[at:at + len(new)] == new and names[at - 1] == "attn_f32_kernel"
     with O.record_routes() as rr:
         _run(torch.float32, q, k, v, do, launch, 2, 0.5)
     assert rr.kernels() == [new[0], new[2], new[3]]
@@ -695,4 +696,4 @@ def test_the_new_kernels_record_their_routes(ops, lp):
     with O.record_routes() as rr:
         O.dropout(dev(rng.standard_normal((5, 7)), torch.float32), 0.5, 1, 2)
         _run(torch.float32, q, k, v, do, launch, 2, 0.0)
-    assert rr.kernels() == [new[6], "attn_f32_kernel"]
+    assert rr.kernels() == [new[6], "attn_f32_kernel", "attn_bwd_q_mfma_kernel<>", "attn_bwd_kv_mfma_kernel<>"]

@@ -54,14 +54,18 @@ def test_gate_kernels_vs_fp64(rows, c, masked):
     ma64 = d(a) if m is None else d(m2) * d(a)
     ma32 = a if m is None else m2 * a
     # forward
-    y = O.fuse_gate_fwd(s, a, alpha, gamma, m)
+    with O.record_routes() as rr:
+        y = O.fuse_gate_fwd(s, a, alpha, gamma, m)
+    assert rr.kernels() == ["fg_fwd_kernel"] and rr.routes[0].vec_ok, rr.routes  # (the 16-byte arm: these widths divide by 4)
     _within(f"fwd {rows}x{c}", y, alpha * s + gamma * ma32, d(alpha) * d(s) + d(gamma) * ma64)
     assert torch.equal(O.fuse_gate_fwd(s, None, alpha, gamma), O.fuse_gate_fwd(s, a, alpha, torch.zeros_like(gamma)))  # (a NULL: alpha s)
     # y aliasing s
     s2 = s.clone()
     assert O.fuse_gate_fwd(s2, a, alpha, gamma, m, out=s2) is s2 and GB.same_bits(s2, y)
     # backward
-    ds, da, sums = O.fuse_gate_bwd(dy, s, a, alpha, gamma, m)
+    with O.record_routes() as rr:
+        ds, da, sums = O.fuse_gate_bwd(dy, s, a, alpha, gamma, m)
+    assert rr.kernels() == ["fg_bwd_kernel"] and rr.routes[0].vec_ok, rr.routes
     dm64 = d(dy) if m is None else d(dy) * d(m2)
     dm32 = dy if m is None else dy * m2
     _within(f"bwd ds {rows}x{c}", ds, alpha * dy, d(alpha) * d(dy))
@@ -118,10 +122,12 @@ def test_gate_kernels_scalar_path(rows, c, shift):
     y, ds, da = (f.reshape(-1)[shift:shift + n_el].view(rows, c) for f in (y_flat, ds_flat, da_flat))
     sums, sb = GB.banded((1, 2 * c), torch.float64, rows=8, cols=0, fill=float("nan"), name="sums")
     ws, wb = GB.exact_workspace(lib.cdseg_fuse_gate_ws_bytes(rows, c))
-    O.check(lib.cdseg_fuse_gate_fwd(O._ptr(s), O._ptr(a), O._ptr(m), O._ptr(alpha), O._ptr(gamma), O._ptr(y), rows, c, O._stream()),
-            "fuse_gate_fwd")
-    O.check(lib.cdseg_fuse_gate_bwd(O._ptr(dy), O._ptr(s), O._ptr(a), O._ptr(m), O._ptr(alpha), O._ptr(gamma), O._ptr(ds), O._ptr(da),
-                                    O._ptr(sums), rows, c, O._ptr(ws), ws.numel(), O._stream()), "fuse_gate_bwd")
+    with O.record_routes() as rr:
+        O.check(lib.cdseg_fuse_gate_fwd(O._ptr(s), O._ptr(a), O._ptr(m), O._ptr(alpha), O._ptr(gamma), O._ptr(y), rows, c, O._stream()),
+                "fuse_gate_fwd")
+        O.check(lib.cdseg_fuse_gate_bwd(O._ptr(dy), O._ptr(s), O._ptr(a), O._ptr(m), O._ptr(alpha), O._ptr(gamma), O._ptr(ds),
+                                        O._ptr(da), O._ptr(sums), rows, c, O._ptr(ws), ws.numel(), O._stream()), "fuse_gate_bwd")
+    assert rr.kernels() == ["fg_fwd_scalar_kernel", "fg_bwd_scalar_kernel"] and not any(r.vec_ok for r in rr.routes), rr.routes
     for b in (yb, dsb, dab, sb, wb):
         b.check()
     for f in (y_flat, ds_flat, da_flat):  # the slack inside the inner row, in front of and behind the shifted view

@@ -24,6 +24,7 @@ pytestmark = pytest.mark.gpu
 
 SHAPES = [(32, 64), (64, 128)]
 PATTERNS = ["ones", "eights", "mixed", "step_end", "group_span"]
+POOL_ONLY_PATTERNS = ["eights_less_one"]  # every run 8 children but the last, which has 7: one child below the scan's ratio
 
 
 def make_runs(pattern, m, g):
@@ -32,6 +33,10 @@ def make_runs(pattern, m, g):
         return torch.ones(m, dtype=torch.int64)
     if pattern == "eights":
         return torch.full((m,), 8, dtype=torch.int64)
+    if pattern == "eights_less_one":
+        runs = torch.full((m,), 8, dtype=torch.int64)
+        runs[-1] = 7
+        return runs
     runs = torch.randint(1, 41, (m,), generator=g)
     if pattern == "mixed":
         runs[m // 2] = 37  # longer than 32: in three 16-child steps wherever it starts
@@ -53,7 +58,7 @@ def pool_case(lp, cin, cout, m, pattern, values):
     """One problem and the two launches' result on it (computed once per case, read-only afterwards)."""
     from cdsegnet_amd import ops as O
     bf = LP()
-    g = torch.Generator().manual_seed(1000 * cin + 10 * m + PATTERNS.index(pattern))
+    g = torch.Generator().manual_seed(1000 * cin + 10 * m + (PATTERNS + POOL_ONLY_PATTERNS).index(pattern))
     runs = make_runs(pattern, m, g)
     seg = torch.cat([torch.zeros(1, dtype=torch.int64), runs.cumsum(0)]).int()
     n = int(seg[-1])
@@ -84,7 +89,24 @@ def pool_case(lp, cin, cout, m, pattern, values):
 
 
 CASES = [(m, p, "normal") for p in PATTERNS for m in (1, 15, 16, 17, 33)] + \
-        [(m, "mixed", v) for v in ("negative", "huge") for m in (1, 33)]
+        [(m, "mixed", v) for v in ("negative", "huge") for m in (1, 33)] + [(m, "eights_less_one", "normal") for m in (1, 17)]
+POOL_SCAN_RATIO = 8  # csrc/pool.hip: left to itself the library scans from n_fine >= 8 m on
+
+
+def auto_fold(ops, n_fine, m):
+    return ops.POOL_FOLD_SCAN if n_fine >= POOL_SCAN_RATIO * m else ops.POOL_FOLD_WALK
+
+
+def test_the_patterns_reach_both_folds_under_auto_on_either_side_of_the_ratio(ops):
+    """What POOL_FOLD_AUTO picks is asserted from the launch record in the test below; this holds its case list to both
+    sides of the rule: "eights" sits ON the ratio (n = 8 m: the scan), "eights_less_one" one child below it (the walk)."""
+    g = torch.Generator().manual_seed(0)
+    auto = {(m, p): auto_fold(ops, int(make_runs(p, m, g).sum()), m) for m, p, v in CASES if p in ("ones", "eights", "eights_less_one")}
+    assert {f for (m, p), f in auto.items() if p == "eights"} == {ops.POOL_FOLD_SCAN}
+    assert {f for (m, p), f in auto.items() if p == "eights_less_one"} == {ops.POOL_FOLD_WALK}
+    assert {f for (m, p), f in auto.items() if p == "ones"} == {ops.POOL_FOLD_WALK}
+    assert all(int(make_runs("eights", m, g).sum()) == 8 * m and int(make_runs("eights_less_one", m, g).sum()) == 8 * m - 1
+               for m in (1, 17))
 
 
 @LPS
@@ -101,9 +123,14 @@ def test_pool_fused_both_folds_equal_gemm_then_segment_max(ops, lp, cin, cout, m
         out2, band2 = GB.banded((m, cout), bf, rows=64, fill=-7.0, name="out2")
         assert xi.stride(0) != cin and out.stride(0) != cout and out2.stride(0) != cout
         seg, seg_check = GB.guard_index(d["seg"], rows=64)
-        with ops.pool_fused_fold(fold):
+        with ops.pool_fused_fold(fold), ops.record_routes() as rr:
             ops.pool_fused(xi, d["img"], d["b"], seg, m, d["sc"], d["sh"], ops.ACT_GELU, out, out2)
         band.check(), band2.check(), seg_check()
+        # the launch record: the fold taken - under AUTO the scan from a mean run of POOL_SCAN_RATIO children on
+        took = auto_fold(ops, d["n"], m) if fold == ops.POOL_FOLD_AUTO else fold
+        name = f"pool_fused_kernel<{cin},{cout},{'scan' if took == ops.POOL_FOLD_SCAN else 'walk'}>"
+        assert rr.count == 1 and rr.kernels() == [name], (fold, rr.routes)
+        assert (rr.routes[0].fix, rr.routes[0].aux, rr.routes[0].bn) == (took, fold, cout), rr.routes
         bad, bad2 = int((GB.bits(out) != GB.bits(d["ref"])).sum()), int((GB.bits(out2) != GB.bits(d["ref2"])).sum())
         report(f"pool fused fold={fold} {cin}->{cout} m={m} {pattern} {values} {lp}", n=d["n"], fp32_mismatches=bad, lp_mismatches=bad2)
         assert bad == 0 and bad2 == 0, (fold, bad, bad2)
@@ -180,8 +207,10 @@ def test_unpool_fused_equals_the_two_gemm_launches(ops, lp, ks, kp, c, n, patter
     out2, band2 = GB.banded((n, c), bf, rows=64, fill=-7.0, name="xc")
     assert xs.stride(0) != ks and xp.stride(0) != kp and out.stride(0) != c and out2.stride(0) != c
     seg, seg_check = GB.guard_index(d["seg"], rows=64)
-    ops.unpool_fused(xs, d["img_s"], *d["ps"], xp, d["img_p"], *d["pp"], seg, m, ops.ACT_GELU, out, out2)
+    with ops.record_routes() as rr:
+        ops.unpool_fused(xs, d["img_s"], *d["ps"], xp, d["img_p"], *d["pp"], seg, m, ops.ACT_GELU, out, out2)
     band.check(), band2.check(), seg_check()
+    assert rr.count == 1 and rr.kernels() == [f"unpool_fused_kernel<{ks},{kp}>"], rr.routes
     bad, bad2 = int((GB.bits(out) != GB.bits(d["ref"])).sum()), int((GB.bits(out2) != GB.bits(d["ref2"])).sum())
     diff = float((out - d["ref"]).abs().max())
     report(f"unpool fused ({ks},{kp},{c}) n={n} m={m} {pattern} {lp}", fp32_mismatches=bad, lp_mismatches=bad2, max_diff=diff)

@@ -1717,8 +1717,9 @@ BLOCK_ARMS = {
         ([_CONV_GEMM, ("gemm_kernel<", "gemm_dma_kernel<64,plain"), ("gemm_kernel<", "gemm_dma_kernel<64,plain"), "attn_"],
          [(900, 64, "f32"), (1000, 128, "tail-only"), (1000, 128, "none"), (600, 256, "none")]),
     "head: GEMM + two cdseg_layernorm launches, and proj GEMM + cdseg_layernorm (C > 512: rows wider than a fused LayerNorm finishes)":
-        (["gemm_kernel<b16,128,klong,gather,128>", "gemm_kernel<b16,128,klong,plain,64>", "gemm_kernel<b16,128,klong,plain,64>", "attn_",
-          "gemm_kernel<b16,128,klong,plain,64>", "gemm_kernel<b16,128,klong,plain,64>", "gemm_dma_kernel<64,plain"], [(200, 528, "none")]),
+        (["gemm_kernel<b16,128,klong,gather,128>", "gemm_kernel<b16,128,klong,plain,64>", "layernorm_kernel<4>", "layernorm_kernel<4>",
+          "gemm_kernel<b16,128,klong,plain,64>", "attn_", "gemm_kernel<b16,128,klong,plain,64>", "layernorm_kernel<4>",
+          "gemm_kernel<b16,128,klong,plain,64>", "gemm_dma_kernel<64,plain"], [(200, 528, "none")]),
     "tail: cdseg_attn_tail_rr2 (ping-pong)":
         (["attn_", "deep_tail_kernel<"], [(2300, 128, False), (5300, 256, False), (40, 256, False), (3200, 512, False), (790, 512, False)]),
     "tail: cdseg_attn_tail_rr at deep widths (tail image without head image: no ping-pong buffer)":
@@ -1735,6 +1736,7 @@ BLOCK_ARMS = {
 _ATT = dict(kernel="attn_bf16_kernel<")
 _G128 = dict(kernel="gemm_kernel<b16,128,klong,plain,64>", split=False)   # a 16-bit GEMM whose LayerNorm is finished in its tile
 _D64 = dict(kernel="gemm_dma_kernel<64,plain,128,2,ring>", split=False)
+_LN4 = dict(kernel="layernorm_kernel<4>", split=False)                    # a cdseg_layernorm launch on rows of 513 .. 1024 channels
 BLOCK_ROUTES = {
     (900, 32, False): [dict(kernel="conv_ll_kernel<32>"), dict(kernel="cpe_head_fused_kernel<32,64>"), _ATT, dict(kernel="tail_rr_kernel<32>")],
     (2300, 64, False): [dict(kernel="conv_ll_kernel<64>"), dict(kernel="cpe_head_fused_kernel<64,64>"), _ATT, dict(kernel="tail_rr_kernel<64>")],
@@ -1766,10 +1768,11 @@ BLOCK_ROUTES = {
                                dict(kernel="deep_head_kernel<512,32,1>", nsplit=1, ysum=False), _ATT, _D64,
                                dict(kernel="gemm_dma_kernel<128,plain,128,2,ring>", split=False),
                                dict(kernel="gemm_dma_kernel<64,plain,128,2,ring>", split=True)],
-    # C = 528 (33 heads; K no power of two and no multiple of 64): no LayerNorm is fused - the cdseg_layernorm launches between the
-    # GEMMs leave no record -, the conv divides in its gather and splits K, fc2 (K = 2112: 17 K steps) runs the DMA loop with split-K
-    (200, 528, "none"): [dict(kernel="gemm_kernel<b16,128,klong,gather,128>", split=True, partials=False), _G128, _G128, _ATT, _G128, _G128,
-                         dict(kernel="gemm_dma_kernel<64,plain,128,2,ring>", split=True)],
+    # C = 528 (33 heads; K no power of two and no multiple of 64): no LayerNorm is fused - the three cdseg_layernorm launches between
+    # the GEMMs are recorded (132 chunks a row on 64 lanes: three of layernorm_kernel<4>'s four passes) -, the conv divides in its
+    # gather and splits K, fc2 (K = 2112: 17 K steps) runs the DMA loop with split-K
+    (200, 528, "none"): [dict(kernel="gemm_kernel<b16,128,klong,gather,128>", split=True, partials=False), _G128, _LN4, _LN4, _G128, _ATT,
+                         _G128, _LN4, _G128, dict(kernel="gemm_dma_kernel<64,plain,128,2,ring>", split=True)],
     (2300, 128, False): [dict(kernel="gemm_dma_kernel<128,gather,128,2,ring>", split=True, partials=True),
                          dict(kernel="deep_head_kernel<128,32,1>", nsplit=1, ysum=True), _ATT,
                          dict(kernel="deep_tail_kernel<128,32,1>", nsplit=1)],

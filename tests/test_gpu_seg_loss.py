@@ -146,8 +146,12 @@ def test_fused_loss_is_as_accurate_as_the_torch_criteria(ops, lp, n, c, variant)
     """kernel error <= 2 * E_ref + 2^-24 * max|reference| for CE, Lovasz and dlogits under each upstream scalar, E_ref = the
     error of cdsegnet_amd/losses.py's torch criteria (fp32, same device, same input) against the fp64 oracle."""
     t, labels, win, o, tor = reference(n, c, variant)
-    got, saved = fused(ops, t, labels, win)
+    with ops.record_routes() as rr:
+        got, saved = fused(ops, t, labels, win)
     assert saved["n_valid"] == o["n_valid"] and saved["present"] == len(o["present"])
+    # the launch record: 16 lanes a row up to 32 classes (one or two classes a lane), 64 lanes with four classes each at 200
+    arm = {13: "16,1", 16: "16,1", 20: "16,2", 200: "64,4"}[c]
+    assert rr.kernels() == [f"loss_rows_kernel<{arm}>", f"loss_bwd_kernel<{arm}>", f"loss_bwd_kernel<{arm}>"], rr.routes
     worst = 0.0
     for k in ("ce", "lovasz", "d_ce", "d_lovasz"):
         top = float(o[k].abs().max())

@@ -72,7 +72,11 @@ def test_kernels_vs_the_fp64_restatement(n, c):
             x, child, cluster, ref = _case(n, c, 7 * n + c, lp)
             xd, chd, cld, refd = x.cuda(), child.cuda(), cluster.cuda(), ref.cuda()
             for rmap, rmapd in ((None, None), (ref, refd)):
-                st = O.skip_stats(xd, rmapd)
+                with O.record_routes() as rr:
+                    st = O.skip_stats(xd, rmapd)
+                # the launch record: the 16-byte arm for a width that is a multiple of four, else the scalar one
+                arm = f"sk_stats{'_scalar' if c % 4 else ''}_kernel<{'f32' if lp is None else 'b16'}>"
+                assert rr.count == 1 and rr.kernels() == [arm] and rr.routes[0].splits == chunks, rr.routes
                 want = R.stats(x, rmap)
                 scale = x.double().abs().sum(0).repeat(3)
                 rel = float(((st.cpu() - want).abs() / scale).max())
@@ -84,8 +88,10 @@ def test_kernels_vs_the_fp64_restatement(n, c):
                 for s, f, with_child, with_stats in ((0.8, 1.0, True, True), (1.1, 0.8838834764831844, True, True),
                                                      (0.9, 1.25, False, True), (1.0, 0.64, True, False), (1.0, 0.8, False, False)):
                     y = xd.clone()
-                    O.skip_merge(y, st if with_stats else None, s, f, rmapd, None, chd if with_child else None,
-                                 cld if with_child else None)
+                    with O.record_routes() as rr:
+                        O.skip_merge(y, st if with_stats else None, s, f, rmapd, None, chd if with_child else None,
+                                     cld if with_child else None)
+                    assert rr.kernels() == [f"sk_merge{'_scalar' if c % 4 else ''}_kernel"], rr.routes
                     want_y = R.merge(x, R.stats(x, rmap) if with_stats else None, s, f, rmap, None,
                                      child if with_child else None, cluster if with_child else None)
                     mag = (abs(f) * x64.abs()).clamp(min=1e-30)
@@ -96,7 +102,9 @@ def test_kernels_vs_the_fp64_restatement(n, c):
                     _check_merge(f"merge {n}x{c} s={s} f={f} child={with_child}", y, want_y, torch.maximum(mag, want_y.abs()), worst)
                 # folded: x + f k (u0 + u1 cos + u2 sin)
                 w = torch.randn(c, c, generator=torch.Generator().manual_seed(n + c)) / c ** 0.5
-                u = O.skip_fold(w.cuda(), st)
+                with O.record_routes() as rr:
+                    u = O.skip_fold(w.cuda(), st)
+                assert rr.kernels() == ["sk_fold_kernel<f32>"], rr.routes
                 want_u = (R.stats(x, rmap).view(3, c) @ w.double().t()).reshape(-1)
                 assert float(((u.cpu() - want_u).abs() / (scale.view(3, c) @ w.double().abs().t()).reshape(-1)).max()) <= STATS_REL
                 y = xd.clone()

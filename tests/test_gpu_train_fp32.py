@@ -60,6 +60,9 @@ DENSE = [(1, 16, 16), (3, 16, 48), (1027, 48, 80), (4101, 32, 96), (2050, 64, 25
          (2103, 512, 256), (2103, 512, 1536), (2103, 512, 2048), (2103, 2048, 512)]
 
 
+ROUTED = [(1, 16, 16), (2050, 64, 256)]  # the shapes whose launch record is asserted: one split, several
+
+
 def _partition(ops, M, N, K, kvol=1):
     part = ops.wgrad_partition(M, N, K, kvol, F32)
     assert (part.splits - 1) * part.rows_per_split < M <= part.splits * part.rows_per_split, tuple(part)
@@ -82,11 +85,22 @@ def test_default_wgrad_exact_on_integers(ops, M, K, N):
     xd, dyd = x.cuda(), dy.cuda()
     want_w, want_b = _want(dyd, xd)
     dw, db, dw_nob = torch.zeros(N, K, device="cuda"), torch.zeros(N, device="cuda"), torch.zeros(N, K, device="cuda")
-    ops.linear_wgrad(xd, dyd, dw, db)
+    with ops.record_routes() as rr:
+        ops.linear_wgrad(xd, dyd, dw, db)
     ops.linear_wgrad(xd, dyd, dw_nob, None)
     _sync()
     assert _eq(dw, want_w) and _eq(db, want_b), "contiguous"
     assert _eq(dw_nob, want_w), "db = None"
+    if (M, K, N) in ROUTED:  # the launch record: the atomic kernel, then the fixed-order one, on the partition asked for above
+        assert rr.count == 1 and rr.kernels() == ["wgrad_kernel"], rr.routes
+        assert (rr.routes[0].splits, rr.routes[0].xmode, rr.routes[0].aux) == (part.splits, part.rows_per_split, 1), rr.routes
+        dw_det, db_det = torch.zeros(N, K, device="cuda"), torch.zeros(N, device="cuda")
+        with ops.record_routes() as rr:
+            ops.linear_wgrad(xd, dyd, dw_det, db_det, deterministic=True)
+        _sync()
+        assert _eq(dw_det, want_w) and _eq(db_det, want_b), "deterministic"
+        assert rr.count == 1 and rr.kernels() == ["wgrad_det_kernel"], rr.routes
+        assert (rr.routes[0].splits, rr.routes[0].xmode, rr.routes[0].aux) == (part.splits, part.rows_per_split, 1), rr.routes
     # strided operands, pre-filled results
     xw, dyw = _ints(rng, M, K + 24).cuda(), _ints(rng, M, N + 16).cuda()
     xw[:, 8:8 + K] = xd
@@ -408,8 +422,11 @@ def test_attention_bwd_fp32_at_deep_head_counts(ops, name, lens, H, dup, cross, 
     assert (k.shape[0] == q.shape[0] + 50) == cross
     exact = _grads(q, k, v, do, launch, H, F32, mode="noround")
     ref32 = _torch_f32_grads(q, k, v, do, launch, H)
-    got = _kernel(F32, q, k, v, do, launch, H, packed=packed, dtype=F32)
+    with ops.record_routes() as rr:
+        got = _kernel(F32, q, k, v, do, launch, H, packed=packed, dtype=F32)
     _attn_assert(name, got, ref32, exact, launch)
+    assert rr.count == 2 and rr.kernels() == ["attn_bwd_q_mfma_kernel<>", "attn_bwd_kv_mfma_kernel<>"], rr.routes
+    assert all(r.splits == 1 and r.compute == ops.F32 for r in rr.routes), rr.routes  # (the fp32 form cuts no patch-head)
     if core:
         from cdsegnet_amd import train_graph
         C = 16 * H
