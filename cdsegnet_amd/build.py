@@ -15,7 +15,7 @@ LIB = os.path.join(HERE, "libcdseg_hip.so")
 LIB_F16 = os.path.join(HERE, "libcdseg_hip_f16.so")
 VARIANTS = [(LIB, "_build", []), (LIB_F16, "_build_f16", ["-DCDSEG_LP_F16"])]
 SOURCES = ["serialize.hip", "plan.hip", "gemm.hip", "elementwise.hip", "attention.hip", "attention_drop.hip", "conv.hip", "stem.hip", "mlp.hip", "blockrr.hip", "deep.hip", "pool.hip", "runtime.hip", "testtime.hip", "traintime.hip", "train.hip", "trainblock.hip", "loss.hip", "norm.hip", "fusion.hip", "skip.hip", "optim.hip", "prof.hip", "route.hip", "abi.hip"]
-HEADERS = ["common.h", "curves.h", "prof.h", "route.h", "deep.h", "wgrad_partition.h", "workspace.h", "attn_train.h", "tail_outputs.h", os.path.join("..", "..", "include", "cdseg.h")]
+HEADERS = ["common.h", "curves.h", "prof.h", "route.h", "deep.h", "wgrad_partition.h", "workspace.h", "colsum.h", "attn_train.h", "tail_outputs.h", os.path.join("..", "..", "include", "cdseg.h")]
 ARCH = "gfx950"
 
 

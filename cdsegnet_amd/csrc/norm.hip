@@ -3,31 +3,26 @@
 // projections of SerializedUnpooling (ptv3.py:464-555, 597-663), nn.SyncBatchNorm under engines/train.py:275-276, and
 // torch_scatter.segment_csr(reduce="max") with its arg-max backward (ptv3.py:510-515).  Definitions and limits: include/cdseg.h.
 //
-// All kernels are memory-bound row sweeps over fp32 (rows, c) tensors with a row stride, c a multiple of 16 in [16, 512].
-// Thread map (every kernel): a row is covered by L = c / 4 lanes of 16 bytes each, a 256-thread block holds R = 256 / L rows
-// at a time (threads beyond R * L idle: only at c = 48 .. where L does not divide 256); a thread keeps ONE column group for
-// its lifetime, so the per-channel operands (mean, invstd, gamma, beta) are loaded once into registers.
-// Arithmetic: fp64 throughout, one rounding per fp32 output.  Reductions (statistics, backward sums):  Block b owns the rows [b * rows_per_block, ...) of
-// cdseg_bn_partition; a thread adds its rows by ascending index, the R row slots of a block are added by ascending slot
-// through LDS, the block partials by ascending block index by a second launch.  No float atomics: every sum is a function of
-// (m, c) and the data alone.
+// All kernels are memory-bound row sweeps over fp32 (rows, c) tensors with a row stride, c a multiple of 16 in [16, 512], on
+// the thread map of csrc/colsum.h (colsum::RowMap): a thread keeps ONE column group for its lifetime, so the per-channel
+// operands (mean, invstd, gamma, beta) are loaded once into registers.
+// Arithmetic: fp64 throughout, one rounding per fp32 output.  Reductions (statistics, backward sums): the fixed order of
+// csrc/colsum.h over the blocks of cdseg_bn_partition, the block partials added in one chain (SEGS = 1).  No float atomics:
+// every sum is a function of (m, c) and the data alone.
 #include <hip/hip_runtime.h>
 
+#include "colsum.h"
 #include "common.h"
 
 namespace {
 
-constexpr int BN_THREADS = 256;
-constexpr int BN_MIN_C = 16, BN_MAX_C = 512;
-constexpr long BN_MIN_ROWS = 256;   // rows of a block at least (m = 5003 -> 20 blocks)
-constexpr long BN_MAX_BLOCKS = 256; // block partials at most: the chain of the ascending reduce
+using colsum::aligned;
+using colsum::ld_ok;
+using colsum::row_grid;
 
-inline void bn_partition(long m, long& rows_per_block, int& blocks) {
-  long rpb = (m + BN_MAX_BLOCKS - 1) / BN_MAX_BLOCKS;
-  rpb = rpb < BN_MIN_ROWS ? BN_MIN_ROWS : (rpb + 63) / 64 * 64;
-  rows_per_block = rpb;
-  blocks = m > 0 ? (int)((m + rpb - 1) / rpb) : 0;
-}
+constexpr int BN_THREADS = colsum::THREADS;
+constexpr int BN_WIDTH = 16;        // c = 16, 32, .. 512
+constexpr long BN_MAX_GRID = 2048;  // the row sweeps: grid-strided beyond
 
 // Element-wise arithmetic: fp64 from the fp32 operands, ONE rounding to fp32 at the store (as in csrc/loss.hip: memory bounds
 // these passes, not the arithmetic).  In fp32 the chain x_hat -> z -> GELU'(z) -> g - k1 - x_hat k2 -> gamma invstd (...) is
@@ -56,11 +51,10 @@ struct BnP {
 // MODE 0: per-channel sum x, sum x^2.  MODE 1: sum g, sum g x_hat with g = dy GELU'(z).  ws[block][2 c].
 template <int MODE>
 __global__ __launch_bounds__(BN_THREADS) void bn_partial_kernel(BnP p) {
-  __shared__ double red[BN_THREADS * 8];  // R row slots x 2 c sums (R * c <= 1024)
-  const int c = p.c, L = c >> 2, R = BN_THREADS / L;
-  const int r = (int)threadIdx.x / L, l = (int)threadIdx.x - r * L;
-  if (r < R) {
-    double a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
+  const colsum::RowMap t(p.c);
+  const int c = p.c, R = t.R, l = t.l;
+  double acc[2][4] = {};
+  if (t.active) {
     const long row0 = (long)blockIdx.x * p.rows_per_block;
     const long row1 = row0 + p.rows_per_block < p.m ? row0 + p.rows_per_block : p.m;
     float4 mu = {0.f, 0.f, 0.f, 0.f}, is = mu, ga = mu, be = mu;
@@ -71,15 +65,15 @@ __global__ __launch_bounds__(BN_THREADS) void bn_partial_kernel(BnP p) {
       be = *reinterpret_cast<const float4*>(p.beta + 4 * l);
     }
 #pragma unroll 2  // (MODE 1 carries an fp64 erfc and exp per element: registers, not loads in flight, are what is scarce)
-    for (long i = row0 + r; i < row1; i += R) {
+    for (long i = row0 + t.r; i < row1; i += R) {
       const float4 v = *reinterpret_cast<const float4*>(p.x + i * p.ldx + 4 * l);
       const float xv[4] = {v.x, v.y, v.z, v.w};
       if constexpr (MODE == 0) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const double d = (double)xv[e];
-          a[e] += d;
-          b[e] += d * d;  // (exact: a 48-bit product)
+          acc[0][e] += d;
+          acc[1][e] += d * d;  // (exact: a 48-bit product)
         }
       } else {
         const float4 d4 = *reinterpret_cast<const float4*>(p.dy + i * p.lddy + 4 * l);
@@ -91,36 +85,13 @@ __global__ __launch_bounds__(BN_THREADS) void bn_partial_kernel(BnP p) {
           double xh, z;
           bn_z(xv[e], m4[e], i4[e], g4[e], b4[e], xh, z);
           const double g = (double)dv[e] * gelu_grad(z);
-          a[e] += g;
-          b[e] += g * xh;
+          acc[0][e] += g;
+          acc[1][e] += g * xh;
         }
       }
     }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      red[r * 2 * c + 4 * l + e] = a[e];
-      red[r * 2 * c + c + 4 * l + e] = b[e];
-    }
   }
-  __syncthreads();
-  for (int j = threadIdx.x; j < 2 * c; j += BN_THREADS) {
-    double t = red[j];
-    for (int q = 1; q < R; ++q) t += red[q * 2 * c + j];
-    p.ws[(long)blockIdx.x * 2 * c + j] = t;
-  }
-}
-
-// Thread i < 2 c: t = p[0]; t += p[1]; ... by ascending block index.  count >= 0: out[2 c] = count (the statistics buffer).
-__global__ __launch_bounds__(64) void bn_reduce_kernel(const double* __restrict__ ws, int blocks, int c, double* __restrict__ out,
-                                                       double count) {
-  const int i = blockIdx.x * 64 + threadIdx.x;
-  if (i == 0 && count >= 0.0) out[2 * c] = count;
-  if (i >= 2 * c) return;
-  const double* p = ws + i;
-  double t = p[0];
-#pragma unroll 32
-  for (int b = 1; b < blocks; ++b) t += p[(long)b * 2 * c];
-  out[i] = t;
+  colsum::block_fold<2>(acc, t, c, p.ws + (long)blockIdx.x * 2 * c);
 }
 
 __global__ __launch_bounds__(64) void bn_finish_kernel(const double* __restrict__ stats, int c, double eps, double momentum,
@@ -158,9 +129,9 @@ struct BnEwP {
 // MODE 0: y = GELU(z).  MODE 1: dx = gamma invstd (g - sum g / n - x_hat sum g x_hat / n).
 template <int MODE>
 __global__ __launch_bounds__(BN_THREADS) void bn_rows_kernel(BnEwP p) {
-  const int c = p.c, L = c >> 2, R = BN_THREADS / L;
-  const int r = (int)threadIdx.x / L, l = (int)threadIdx.x - r * L;
-  if (r >= R) return;
+  const colsum::RowMap t(p.c);
+  if (!t.active) return;
+  const int c = p.c, R = t.R, r = t.r, l = t.l;
   const float4 mu = *reinterpret_cast<const float4*>(p.mean + 4 * l);
   const float4 is = *reinterpret_cast<const float4*>(p.invstd + 4 * l);
   const float4 ga = *reinterpret_cast<const float4*>(p.gamma + 4 * l);
@@ -211,9 +182,9 @@ __global__ __launch_bounds__(BN_THREADS) void segment_max_arg_kernel(const float
                                                                      const int32_t* __restrict__ seg, long m, int c,
                                                                      float* __restrict__ out, int ldo, int32_t* __restrict__ arg,
                                                                      int lda) {
-  const int L = c >> 2, R = BN_THREADS / L;
-  const int r = (int)threadIdx.x / L, l = (int)threadIdx.x - r * L;
-  if (r >= R) return;
+  const colsum::RowMap t(c);
+  if (!t.active) return;
+  const int R = t.R, r = t.r, l = t.l;
   for (long j = (long)blockIdx.x * R + r; j < m; j += (long)gridDim.x * R) {
     const int s = seg[j], e = seg[j + 1];
     float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
@@ -237,9 +208,9 @@ __global__ __launch_bounds__(BN_THREADS) void segment_max_bwd_kernel(const float
                                                                      const int32_t* __restrict__ arg, int lda,
                                                                      const int32_t* __restrict__ cluster, long n, int c,
                                                                      float* __restrict__ dy, int lddy) {
-  const int L = c >> 2, R = BN_THREADS / L;
-  const int r = (int)threadIdx.x / L, l = (int)threadIdx.x - r * L;
-  if (r >= R) return;
+  const colsum::RowMap t(c);
+  if (!t.active) return;
+  const int R = t.R, r = t.r, l = t.l;
 #pragma unroll 2
   for (long i = (long)blockIdx.x * R + r; i < n; i += (long)gridDim.x * R) {
     const long j = cluster[i];
@@ -251,20 +222,6 @@ __global__ __launch_bounds__(BN_THREADS) void segment_max_bwd_kernel(const float
   }
 }
 
-int width_status(int c) { return (c < BN_MIN_C || c > BN_MAX_C || (c & 15)) ? CDSEG_ERR_UNSUPPORTED : CDSEG_OK; }
-
-template <typename... P>
-bool aligned16(const P*... ptr) { return ((((uintptr_t)ptr) | ...) & 15) == 0; }
-
-bool ld_ok(int ld, int c) { return ld >= c && (ld & 3) == 0; }
-
-unsigned row_grid(long rows, int c, int rows_per_thread) {
-  const int R = BN_THREADS / (c >> 2);
-  long blocks = (rows + (long)R * rows_per_thread - 1) / ((long)R * rows_per_thread);
-  if (blocks < 1) blocks = 1;
-  if (blocks > 2048) blocks = 2048;
-  return (unsigned)blocks;
-}
 
 }  // namespace
 
@@ -272,44 +229,39 @@ extern "C" {
 
 int cdseg_bn_partition(long m, int c, long* rows_per_block, int* blocks) {
   if (m < 0 || !rows_per_block || !blocks) return CDSEG_ERR_ARG;
-  const int st = width_status(c);
-  if (st != CDSEG_OK) return st;
-  bn_partition(m, *rows_per_block, *blocks);
+  if (!colsum::width_ok(c, BN_WIDTH)) return CDSEG_ERR_UNSUPPORTED;
+  const colsum::Partition q = colsum::partition(m, colsum::MIN_ROWS_BN);
+  *rows_per_block = q.rows_per_block;
+  *blocks = q.blocks;
   return CDSEG_OK;
 }
 
 size_t cdseg_bn_ws_bytes(long m, int c) {
-  if (m <= 0 || width_status(c) != CDSEG_OK) return 0;
-  long rpb;
-  int blocks;
-  bn_partition(m, rpb, blocks);
-  return (size_t)blocks * 2 * (size_t)c * sizeof(double);
+  return colsum::width_ok(c, BN_WIDTH) ? colsum::ws_bytes(m, 2, c, colsum::MIN_ROWS_BN) : 0;
 }
 
 int cdseg_bn_stats(const float* x, int ldx, long m, int c, double* stats, void* ws, size_t ws_bytes, void* stream) {
   if (m < 0) return CDSEG_ERR_ARG;
-  const int st = width_status(c);
-  if (st != CDSEG_OK) return st;
+  if (!colsum::width_ok(c, BN_WIDTH)) return CDSEG_ERR_UNSUPPORTED;
   if (m == 0) return CDSEG_OK;
-  if (!x || !stats || !aligned16(x) || ((uintptr_t)stats & 7) || !ld_ok(ldx, c)) return CDSEG_ERR_ARG;
-  if (ws && !aligned16(ws)) return CDSEG_ERR_ARG;
+  if (!x || !stats || !aligned(15, x) || ((uintptr_t)stats & 7) || !ld_ok(ldx, c)) return CDSEG_ERR_ARG;
+  if (ws && !aligned(15, ws)) return CDSEG_ERR_ARG;
   if (!ws || ws_bytes < cdseg_bn_ws_bytes(m, c)) return CDSEG_ERR_WORKSPACE;
   BnP p = {};
   p.x = x; p.m = m; p.c = c; p.ldx = ldx; p.ws = (double*)ws;
-  int blocks;
-  bn_partition(m, p.rows_per_block, blocks);
+  const colsum::Partition q = colsum::partition(m, colsum::MIN_ROWS_BN);
+  p.rows_per_block = q.rows_per_block;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(bn_partial_kernel<0>, dim3((unsigned)blocks), dim3(BN_THREADS), 0, s, p);
-  hipLaunchKernelGGL(bn_reduce_kernel, dim3((unsigned)cdiv(2 * c, 64)), dim3(64), 0, s, (const double*)ws, blocks, c, stats, (double)m);
+  hipLaunchKernelGGL(bn_partial_kernel<0>, dim3((unsigned)q.blocks), dim3(BN_THREADS), 0, s, p);
+  colsum::launch_reduce<1>(p.ws, q.blocks, 2 * c, stats, (double)m, s);  // (and stats[2 c] = m)
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
 }
 
 int cdseg_bn_finish(const double* stats, int c, double eps, double momentum, float* mean, float* invstd, float* running_mean,
                     float* running_var, void* stream) {
-  const int st = width_status(c);
-  if (st != CDSEG_OK) return st;
-  if (!stats || !mean || !invstd || ((uintptr_t)stats & 7) || !aligned16(mean, invstd)) return CDSEG_ERR_ARG;
+  if (!colsum::width_ok(c, BN_WIDTH)) return CDSEG_ERR_UNSUPPORTED;
+  if (!stats || !mean || !invstd || ((uintptr_t)stats & 7) || !aligned(15, mean, invstd)) return CDSEG_ERR_ARG;
   if ((((uintptr_t)running_mean | (uintptr_t)running_var) & 3) || !(eps >= 0.0) || !(momentum >= 0.0 && momentum <= 1.0))
     return CDSEG_ERR_ARG;
   hipLaunchKernelGGL(bn_finish_kernel, dim3((unsigned)cdiv(c, 64)), dim3(64), 0, (hipStream_t)stream, stats, c, eps, momentum, mean,
@@ -321,15 +273,14 @@ int cdseg_bn_finish(const double* stats, int c, double eps, double momentum, flo
 int cdseg_bn_gelu_fwd(const float* x, int ldx, long m, int c, const float* mean, const float* invstd, const float* gamma,
                       const float* beta, float* y, int ldy, void* stream) {
   if (m < 0) return CDSEG_ERR_ARG;
-  const int st = width_status(c);
-  if (st != CDSEG_OK) return st;
+  if (!colsum::width_ok(c, BN_WIDTH)) return CDSEG_ERR_UNSUPPORTED;
   if (m == 0) return CDSEG_OK;
-  if (!x || !mean || !invstd || !gamma || !beta || !y || !aligned16(x, mean, invstd, gamma, beta, y) || !ld_ok(ldx, c) ||
+  if (!x || !mean || !invstd || !gamma || !beta || !y || !aligned(15, x, mean, invstd, gamma, beta, y) || !ld_ok(ldx, c) ||
       !ld_ok(ldy, c))
     return CDSEG_ERR_ARG;
   BnEwP p = {};
   p.x = x; p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.beta = beta; p.out = y; p.m = m; p.c = c; p.ldx = ldx; p.ldo = ldy;
-  hipLaunchKernelGGL(bn_rows_kernel<0>, dim3(row_grid(m, c, 4)), dim3(BN_THREADS), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(bn_rows_kernel<0>, dim3(row_grid(m, c, 4, BN_MAX_GRID)), dim3(BN_THREADS), 0, (hipStream_t)stream, p);
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
 }
@@ -338,22 +289,21 @@ int cdseg_bn_gelu_bwd_sums(const float* x, int ldx, const float* dy, int lddy, l
                            const float* invstd, const float* gamma, const float* beta, double* gsums, void* ws, size_t ws_bytes,
                            void* stream) {
   if (m < 0) return CDSEG_ERR_ARG;
-  const int st = width_status(c);
-  if (st != CDSEG_OK) return st;
+  if (!colsum::width_ok(c, BN_WIDTH)) return CDSEG_ERR_UNSUPPORTED;
   if (m == 0) return CDSEG_OK;
-  if (!x || !dy || !mean || !invstd || !gamma || !beta || !gsums || !aligned16(x, dy, mean, invstd, gamma, beta) ||
+  if (!x || !dy || !mean || !invstd || !gamma || !beta || !gsums || !aligned(15, x, dy, mean, invstd, gamma, beta) ||
       ((uintptr_t)gsums & 7) || !ld_ok(ldx, c) || !ld_ok(lddy, c))
     return CDSEG_ERR_ARG;
-  if (ws && !aligned16(ws)) return CDSEG_ERR_ARG;
+  if (ws && !aligned(15, ws)) return CDSEG_ERR_ARG;
   if (!ws || ws_bytes < cdseg_bn_ws_bytes(m, c)) return CDSEG_ERR_WORKSPACE;
   BnP p = {};
   p.x = x; p.dy = dy; p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.beta = beta;
   p.m = m; p.c = c; p.ldx = ldx; p.lddy = lddy; p.ws = (double*)ws;
-  int blocks;
-  bn_partition(m, p.rows_per_block, blocks);
+  const colsum::Partition q = colsum::partition(m, colsum::MIN_ROWS_BN);
+  p.rows_per_block = q.rows_per_block;
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(bn_partial_kernel<1>, dim3((unsigned)blocks), dim3(BN_THREADS), 0, s, p);
-  hipLaunchKernelGGL(bn_reduce_kernel, dim3((unsigned)cdiv(2 * c, 64)), dim3(64), 0, s, (const double*)ws, blocks, c, gsums, -1.0);
+  hipLaunchKernelGGL(bn_partial_kernel<1>, dim3((unsigned)q.blocks), dim3(BN_THREADS), 0, s, p);
+  colsum::launch_reduce<1>(p.ws, q.blocks, 2 * c, gsums, -1.0, s);
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
 }
@@ -362,17 +312,16 @@ int cdseg_bn_gelu_bwd_dx(const float* x, int ldx, const float* dy, int lddy, lon
                          const float* gamma, const float* beta, const double* gsums, const double* count, float* dx, int lddx,
                          void* stream) {
   if (m < 0) return CDSEG_ERR_ARG;
-  const int st = width_status(c);
-  if (st != CDSEG_OK) return st;
+  if (!colsum::width_ok(c, BN_WIDTH)) return CDSEG_ERR_UNSUPPORTED;
   if (m == 0) return CDSEG_OK;
   if (!x || !dy || !mean || !invstd || !gamma || !beta || !gsums || !count || !dx ||
-      !aligned16(x, dy, mean, invstd, gamma, beta, dx) || (((uintptr_t)gsums | (uintptr_t)count) & 7) || !ld_ok(ldx, c) ||
+      !aligned(15, x, dy, mean, invstd, gamma, beta, dx) || (((uintptr_t)gsums | (uintptr_t)count) & 7) || !ld_ok(ldx, c) ||
       !ld_ok(lddy, c) || !ld_ok(lddx, c))
     return CDSEG_ERR_ARG;
   BnEwP p = {};
   p.x = x; p.dy = dy; p.mean = mean; p.invstd = invstd; p.gamma = gamma; p.beta = beta; p.gsums = gsums; p.count = count;
   p.out = dx; p.m = m; p.c = c; p.ldx = ldx; p.lddy = lddy; p.ldo = lddx;
-  hipLaunchKernelGGL(bn_rows_kernel<1>, dim3(row_grid(m, c, 4)), dim3(BN_THREADS), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(bn_rows_kernel<1>, dim3(row_grid(m, c, 4, BN_MAX_GRID)), dim3(BN_THREADS), 0, (hipStream_t)stream, p);
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
 }
@@ -380,15 +329,14 @@ int cdseg_bn_gelu_bwd_dx(const float* x, int ldx, const float* dy, int lddy, lon
 int cdseg_segment_max_arg(const float* y, int ldy, const int32_t* seg_start, long m, int c, float* out, int ldo, int32_t* arg,
                           int lda, void* stream) {
   if (m < 0) return CDSEG_ERR_ARG;
-  const int st = width_status(c);
-  if (st != CDSEG_OK) return st;
+  if (!colsum::width_ok(c, BN_WIDTH)) return CDSEG_ERR_UNSUPPORTED;
   if (m >= (1L << 31)) return CDSEG_ERR_UNSUPPORTED;
   if (m == 0) return CDSEG_OK;
-  if (!y || !seg_start || !out || !arg || !aligned16(y, out, arg) || ((uintptr_t)seg_start & 3) || !ld_ok(ldy, c) ||
+  if (!y || !seg_start || !out || !arg || !aligned(15, y, out, arg) || ((uintptr_t)seg_start & 3) || !ld_ok(ldy, c) ||
       !ld_ok(ldo, c) || !ld_ok(lda, c))
     return CDSEG_ERR_ARG;
-  hipLaunchKernelGGL(segment_max_arg_kernel, dim3(row_grid(m, c, 2)), dim3(BN_THREADS), 0, (hipStream_t)stream, y, ldy, seg_start, m, c,
-                     out, ldo, arg, lda);
+  hipLaunchKernelGGL(segment_max_arg_kernel, dim3(row_grid(m, c, 2, BN_MAX_GRID)), dim3(BN_THREADS), 0, (hipStream_t)stream, y, ldy,
+                     seg_start, m, c, out, ldo, arg, lda);
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
 }
@@ -396,15 +344,14 @@ int cdseg_segment_max_arg(const float* y, int ldy, const int32_t* seg_start, lon
 int cdseg_segment_max_bwd(const float* dout, int lddo, const int32_t* arg, int lda, const int32_t* cluster, long n, int c,
                           float* dy, int lddy, void* stream) {
   if (n < 0) return CDSEG_ERR_ARG;
-  const int st = width_status(c);
-  if (st != CDSEG_OK) return st;
+  if (!colsum::width_ok(c, BN_WIDTH)) return CDSEG_ERR_UNSUPPORTED;
   if (n >= (1L << 31)) return CDSEG_ERR_UNSUPPORTED;
   if (n == 0) return CDSEG_OK;
-  if (!dout || !arg || !cluster || !dy || !aligned16(dout, arg, dy) || ((uintptr_t)cluster & 3) || !ld_ok(lddo, c) ||
+  if (!dout || !arg || !cluster || !dy || !aligned(15, dout, arg, dy) || ((uintptr_t)cluster & 3) || !ld_ok(lddo, c) ||
       !ld_ok(lda, c) || !ld_ok(lddy, c))
     return CDSEG_ERR_ARG;
-  hipLaunchKernelGGL(segment_max_bwd_kernel, dim3(row_grid(n, c, 4)), dim3(BN_THREADS), 0, (hipStream_t)stream, dout, lddo, arg, lda,
-                     cluster, n, c, dy, lddy);
+  hipLaunchKernelGGL(segment_max_bwd_kernel, dim3(row_grid(n, c, 4, BN_MAX_GRID)), dim3(BN_THREADS), 0, (hipStream_t)stream, dout, lddo,
+                     arg, lda, cluster, n, c, dy, lddy);
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
 }

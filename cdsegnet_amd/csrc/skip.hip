@@ -8,33 +8,27 @@
 //   S0_c = sum_m x[m][c],  A_c = sum_m x[m][c] cos theta_m,  B_c = sum_m x[m][c] sin theta_m
 // - three column sums (cdseg_skip_stats) and one element-wise pass (cdseg_skip_merge) that also applies the skip scale f and
 // adds the unpooled child row.  The operator is I + k P with P symmetric: its backward is the same pair of calls.
-// Thread map as in fusion.hip: on the vector path (c a multiple of 4, operands aligned for 4 elements per access) a row is
-// covered by L = c / 4 lanes, a 256-thread block holds R = 256 / L rows at a time and a thread keeps ONE column group for its
-// lifetime; the scalar path (any other c or alignment) moves one element per access with the same arithmetic.
+// On the vector path (c a multiple of 4, operands aligned for 4 elements per access) the thread map of csrc/colsum.h
+// (colsum::RowMap), a thread keeps ONE column group for its lifetime; the scalar path (any other c or alignment) moves one
+// element per access with the same arithmetic.
 // Arithmetic: cos / sin in fp64 (sincospi(2 n / N)), every element-wise expression in fp64 from the stored operands and rounded
-// to fp32 once.  The sums are accumulated in fp64: chunk b owns the rows [b rows_per_chunk, ...), a thread adds its rows by
-// ascending index, the R row slots of a block by ascending slot through LDS, the chunk partials (workspace) in a second launch:
-// by ascending chunk index inside each of 16 segments of consecutive chunks, then the segment sums by ascending segment.  No float
-// atomics: a sum is a function of (n, c), the path and the data alone.
+// to fp32 once.  The sums are accumulated in fp64 in the fixed order of csrc/colsum.h: chunks (its blocks) of 64 rows at least,
+// the chunk partials (workspace) added in 16 segments of consecutive chunks (SEGS = 16: 256 chunks are 16 of 16).  No float atomics: a
+// sum is a function of (n, c), the path and the data alone.
 #include <hip/hip_runtime.h>
 
+#include "colsum.h"
 #include "common.h"
 #include "route.h"
 
 namespace {
 
-constexpr int SK_THREADS = 256;
-constexpr int SK_MIN_C = 1, SK_MAX_C = 512;
-constexpr long SK_MIN_ROWS = 64;    // rows of a chunk at least
-constexpr long SK_MAX_CHUNKS = 256; // chunk partials at most: 16 segments of 16 in the finish
-constexpr long SK_MAX_GRID = 4096;  // merge: grid-strided beyond
+using colsum::aligned;
 
-inline void sk_partition(long n, long& rows_per_chunk, int& chunks) {
-  long rpc = (n + SK_MAX_CHUNKS - 1) / SK_MAX_CHUNKS;
-  rpc = rpc < SK_MIN_ROWS ? SK_MIN_ROWS : (rpc + 63) / 64 * 64;
-  rows_per_chunk = rpc;
-  chunks = n > 0 ? (int)((n + rpc - 1) / rpc) : 0;
-}
+constexpr int SK_THREADS = colsum::THREADS;
+constexpr int SK_WIDTH = 1;         // any c in [1, 512]
+constexpr int SK_SEGS = 16;         // the finish of the statistics
+constexpr long SK_MAX_GRID = 4096;  // merge: grid-strided beyond
 
 struct SkP {
   const void* src;         // stats: the skip feature, fp32 or the build's 16-bit type
@@ -70,37 +64,25 @@ __device__ __forceinline__ void sk_load4(const void* base, long off, double v[4]
 // ws[chunk][3 c] = the chunk's [S0 A B].
 template <bool LP>
 __global__ __launch_bounds__(SK_THREADS) void sk_stats_kernel(SkP p) {
-  __shared__ double red[SK_THREADS * 12];  // R row slots x 3 c sums (R * c <= 1024)
-  const int c = p.c, L = c >> 2, R = SK_THREADS / L;
-  const int r = (int)threadIdx.x / L, l = (int)threadIdx.x - r * L;
-  if (r < R) {
-    double s0[4] = {0.0, 0.0, 0.0, 0.0}, a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
+  const colsum::RowMap t(p.c);
+  const int c = p.c, R = t.R, l = t.l;
+  double acc[3][4] = {};  // S0, A, B
+  if (t.active) {
     const long row0 = (long)blockIdx.x * p.rows_per_chunk;
     const long row1 = row0 + p.rows_per_chunk < p.n ? row0 + p.rows_per_chunk : p.n;
-    for (long i = row0 + r; i < row1; i += R) {
+    for (long i = row0 + t.r; i < row1; i += R) {
       double v[4], cs, sn;
       sk_load4<LP>(p.src, i * p.ld + 4 * l, v);
       sk_angle(p, i, cs, sn);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        s0[e] += v[e];
-        a[e] += v[e] * cs;
-        b[e] += v[e] * sn;
+        acc[0][e] += v[e];
+        acc[1][e] += v[e] * cs;
+        acc[2][e] += v[e] * sn;
       }
     }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      red[r * 3 * c + 4 * l + e] = s0[e];
-      red[r * 3 * c + c + 4 * l + e] = a[e];
-      red[r * 3 * c + 2 * c + 4 * l + e] = b[e];
-    }
   }
-  __syncthreads();
-  for (int j = threadIdx.x; j < 3 * c; j += SK_THREADS) {
-    double t = red[j];
-    for (int q = 1; q < R; ++q) t += red[q * 3 * c + j];
-    p.ws[(long)blockIdx.x * 3 * c + j] = t;
-  }
+  colsum::block_fold<3>(acc, t, c, p.ws + (long)blockIdx.x * 3 * c);
 }
 
 template <bool LP>
@@ -127,35 +109,6 @@ __global__ __launch_bounds__(SK_THREADS) void sk_stats_scalar_kernel(SkP p) {
   }
 }
 
-// The finish: output i = the sum of its `chunks` partials.  A serial chain over up to 256 partials is bound by the latency of its
-// loads (45 us measured), so the chain is cut into SK_SEGS segments of seg = ceil(chunks / SK_SEGS) consecutive chunks: thread
-// (g, o) of a block adds segment g of output blockIdx * 16 + o by ascending chunk index (its loads are independent and in flight
-// together), thread (0, o) then adds the segment sums by ascending segment.  The order is a function of `chunks` alone.
-constexpr int SK_SEGS = 16;
-
-__global__ __launch_bounds__(256) void sk_reduce_kernel(const double* __restrict__ ws, int chunks, int count, double* __restrict__ out) {
-  __shared__ double red[SK_SEGS][16];
-  const int o = threadIdx.x & 15, g = threadIdx.x >> 4;
-  const int i = blockIdx.x * 16 + o;
-  const int seg = (chunks + SK_SEGS - 1) / SK_SEGS;
-  const int b0 = g * seg, b1 = b0 + seg < chunks ? b0 + seg : chunks;
-  double t = 0.0;
-  if (i < count && b0 < b1) {
-    const double* p = ws + i;
-    t = p[(long)b0 * count];
-#pragma unroll 16
-    for (int b = b0 + 1; b < b1; ++b) t += p[(long)b * count];
-  }
-  red[g][o] = t;
-  __syncthreads();
-  if (g == 0 && i < count) {
-    double v = red[0][o];
-    const int segs = (chunks + seg - 1) / seg;
-    for (int q = 1; q < segs; ++q) v += red[q][o];
-    out[i] = v;
-  }
-}
-
 // One element of the merge: v = x; with stats v += k (S0 + A cos + B sin), all of it times f (folded: only the added term is
 // times f, x carries f already); then + child.
 __device__ __forceinline__ float sk_element(const SkP& p, double x, double s0, double a, double b, double cs, double sn,
@@ -172,9 +125,9 @@ __device__ __forceinline__ float sk_element(const SkP& p, double x, double s0, d
 }
 
 __global__ __launch_bounds__(SK_THREADS) void sk_merge_kernel(SkP p) {
-  const int c = p.c, L = c >> 2, R = SK_THREADS / L;
-  const int r = (int)threadIdx.x / L, l = (int)threadIdx.x - r * L;
-  if (r >= R) return;
+  const colsum::RowMap t(p.c);
+  if (!t.active) return;
+  const int c = p.c, R = t.R, r = t.r, l = t.l;
   const bool filt = p.stats != nullptr, has_child = p.child != nullptr;
   double s0[4] = {0.0, 0.0, 0.0, 0.0}, a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
   if (filt) {
@@ -244,48 +197,41 @@ __global__ __launch_bounds__(64) void sk_fold_kernel(const void* __restrict__ w,
   }
 }
 
-int sk_width_status(int c) { return (c < SK_MIN_C || c > SK_MAX_C) ? CDSEG_ERR_UNSUPPORTED : CDSEG_OK; }
-
-bool sk_aligned(uintptr_t mask, const void* p) { return (((uintptr_t)p) & mask) == 0; }
-
 }  // namespace
 
 extern "C" {
 
 int cdseg_skip_partition(long n, int c, long* rows_per_chunk, int* chunks) {
   if (n < 0 || !rows_per_chunk || !chunks) return CDSEG_ERR_ARG;
-  const int st = sk_width_status(c);
-  if (st != CDSEG_OK) return st;
-  sk_partition(n, *rows_per_chunk, *chunks);
+  if (!colsum::width_ok(c, SK_WIDTH)) return CDSEG_ERR_UNSUPPORTED;
+  const colsum::Partition q = colsum::partition(n, colsum::MIN_ROWS_SWEEP);
+  *rows_per_chunk = q.rows_per_block;
+  *chunks = q.blocks;
   return CDSEG_OK;
 }
 
 size_t cdseg_skip_stats_ws_bytes(long n, int c) {
-  if (n <= 0 || sk_width_status(c) != CDSEG_OK) return 0;
-  long rpc;
-  int chunks;
-  sk_partition(n, rpc, chunks);
-  return (size_t)chunks * 3 * (size_t)c * sizeof(double);
+  return colsum::width_ok(c, SK_WIDTH) ? colsum::ws_bytes(n, 3, c, colsum::MIN_ROWS_SWEEP) : 0;
 }
 
 int cdseg_skip_stats(const void* x, int dtype, int ldx, long n, int c, const int32_t* ref_of_row, long n_total, double* stats,
                      void* ws, size_t ws_bytes, void* stream) {
   if (n < 0 || (dtype != CDSEG_F32 && dtype != CDSEG_BF16)) return CDSEG_ERR_ARG;
-  const int st = sk_width_status(c);
-  if (st != CDSEG_OK) return st;
+  if (!colsum::width_ok(c, SK_WIDTH)) return CDSEG_ERR_UNSUPPORTED;
   if (n >= (1L << 31) || n_total >= (1L << 31)) return CDSEG_ERR_UNSUPPORTED;  // the row map is int32
   if (n == 0) return CDSEG_OK;
   const bool lp = dtype == CDSEG_BF16;
-  if (!x || !stats || ldx < c || n_total < n || !sk_aligned(lp ? 1 : 3, x) || !sk_aligned(3, ref_of_row) || !sk_aligned(7, stats))
+  if (!x || !stats || ldx < c || n_total < n || !aligned(lp ? 1 : 3, x) || !aligned(3, ref_of_row) || !aligned(7, stats))
     return CDSEG_ERR_ARG;
-  if (ws && !sk_aligned(15, ws)) return CDSEG_ERR_ARG;
+  if (ws && !aligned(15, ws)) return CDSEG_ERR_ARG;
   if (!ws || ws_bytes < cdseg_skip_stats_ws_bytes(n, c)) return CDSEG_ERR_WORKSPACE;
   SkP p = {};
   p.src = x; p.ref = ref_of_row; p.ws = (double*)ws; p.n = n; p.c = c; p.ld = ldx; p.inv_n2 = 2.0 / (double)n_total;
-  int chunks;
-  sk_partition(n, p.rows_per_chunk, chunks);
+  const colsum::Partition part = colsum::partition(n, colsum::MIN_ROWS_SWEEP);
+  const int chunks = part.blocks;
+  p.rows_per_chunk = part.rows_per_block;
   hipStream_t q = (hipStream_t)stream;
-  const bool vec = (c & 3) == 0 && (ldx & 3) == 0 && sk_aligned(lp ? 7 : 15, x);
+  const bool vec = (c & 3) == 0 && (ldx & 3) == 0 && aligned(lp ? 7 : 15, x);
   const int rflags = (vec ? CDSEG_ROUTE_F_VEC_OK : 0) | (dtype << CDSEG_ROUTE_F_CT_SHIFT);
   if (vec && lp) {
     cdseg_route_rec(CDSEG_RK_SK_STATS_B16, 0, c, chunks, 0, 0, rflags, 0);
@@ -301,16 +247,16 @@ int cdseg_skip_stats(const void* x, int dtype, int ldx, long n, int c, const int
     hipLaunchKernelGGL(sk_stats_scalar_kernel<false>, dim3((unsigned)chunks), dim3(SK_THREADS), 0, q, p);
   }
   CDSEG_CHECK_LAUNCH();
-  hipLaunchKernelGGL(sk_reduce_kernel, dim3((unsigned)cdiv(3 * c, 16)), dim3(256), 0, q, (const double*)ws, chunks, 3 * c, stats);
+  colsum::launch_reduce<SK_SEGS>(p.ws, chunks, 3 * c, stats, -1.0, q);
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;
 }
 
 int cdseg_skip_fold(const void* w, int dtype, int ldw, int cout, int cin, const double* stats, double* u, void* stream) {
   if (dtype != CDSEG_F32 && dtype != CDSEG_BF16) return CDSEG_ERR_ARG;
-  if (sk_width_status(cin) != CDSEG_OK || sk_width_status(cout) != CDSEG_OK) return CDSEG_ERR_UNSUPPORTED;
+  if (!colsum::width_ok(cin, SK_WIDTH) || !colsum::width_ok(cout, SK_WIDTH)) return CDSEG_ERR_UNSUPPORTED;
   const bool lp = dtype == CDSEG_BF16;
-  if (!w || !stats || !u || ldw < cin || !sk_aligned(lp ? 1 : 3, w) || !sk_aligned(7, stats) || !sk_aligned(7, u)) return CDSEG_ERR_ARG;
+  if (!w || !stats || !u || ldw < cin || !aligned(lp ? 1 : 3, w) || !aligned(7, stats) || !aligned(7, u)) return CDSEG_ERR_ARG;
   if (lp) {
     cdseg_route_rec(CDSEG_RK_SK_FOLD_B16, cout, cin, 1, 0, 0, CDSEG_BF16 << CDSEG_ROUTE_F_CT_SHIFT, 0);
     hipLaunchKernelGGL(sk_fold_kernel<true>, dim3((unsigned)cout), dim3(64), 0, (hipStream_t)stream, w, ldw, cin, cout, stats, u);
@@ -325,12 +271,11 @@ int cdseg_skip_fold(const void* w, int dtype, int ldw, int cout, int cin, const 
 int cdseg_skip_merge(float* x, int ldx, long n, int c, const double* stats, int folded, double s, long n_total, double f,
                      const int32_t* ref_of_row, const float* child, int ldchild, const int32_t* cluster, long n_child, void* stream) {
   if (n < 0) return CDSEG_ERR_ARG;
-  const int st = sk_width_status(c);
-  if (st != CDSEG_OK) return st;
+  if (!colsum::width_ok(c, SK_WIDTH)) return CDSEG_ERR_UNSUPPORTED;
   if (n >= (1L << 31) || n_total >= (1L << 31) || n_child >= (1L << 31)) return CDSEG_ERR_UNSUPPORTED;
   if (n == 0) return CDSEG_OK;
-  if (!x || ldx < c || !sk_aligned(3, x) || !sk_aligned(3, ref_of_row) || !sk_aligned(3, child) || !sk_aligned(3, cluster) ||
-      !sk_aligned(7, stats) || (stats && n_total < n) || (folded && !stats) || (child && (!cluster || n_child <= 0 || ldchild < c)) ||
+  if (!x || ldx < c || !aligned(3, x) || !aligned(3, ref_of_row) || !aligned(3, child) || !aligned(3, cluster) ||
+      !aligned(7, stats) || (stats && n_total < n) || (folded && !stats) || (child && (!cluster || n_child <= 0 || ldchild < c)) ||
       (!child && cluster) || !(f == f) || !(s == s))
     return CDSEG_ERR_ARG;
   SkP p = {};
@@ -340,18 +285,15 @@ int cdseg_skip_merge(float* x, int ldx, long n, int c, const double* stats, int 
     p.k = ((double)(float)s - 1.0) / (double)n_total;  // the reference's mask is a float32 tensor
     p.inv_n2 = 2.0 / (double)n_total;
   }
-  const bool vec = (c & 3) == 0 && (ldx & 3) == 0 && sk_aligned(15, x) && (!child || ((ldchild & 3) == 0 && sk_aligned(15, child)));
+  const bool vec = (c & 3) == 0 && (ldx & 3) == 0 && aligned(15, x) && (!child || ((ldchild & 3) == 0 && aligned(15, child)));
   if (vec) {
-    const int R = SK_THREADS / (c >> 2);
-    long blocks = (n + (long)R * 4 - 1) / ((long)R * 4);  // about four rows a thread
-    blocks = blocks < 1 ? 1 : (blocks > SK_MAX_GRID ? SK_MAX_GRID : blocks);
+    const unsigned grid = colsum::row_grid(n, c, 4, SK_MAX_GRID);  // about four rows a thread
     cdseg_route_rec(CDSEG_RK_SK_MERGE, 0, c, 1, 0, 0, CDSEG_ROUTE_F_VEC_OK | (CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT), 0);
-    hipLaunchKernelGGL(sk_merge_kernel, dim3((unsigned)blocks), dim3(SK_THREADS), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(sk_merge_kernel, dim3(grid), dim3(SK_THREADS), 0, (hipStream_t)stream, p);
   } else {
-    long blocks = (n * c + (long)SK_THREADS * 4 - 1) / ((long)SK_THREADS * 4);
-    blocks = blocks < 1 ? 1 : (blocks > SK_MAX_GRID ? SK_MAX_GRID : blocks);
+    const unsigned grid = colsum::elem_grid(n * c, 4, SK_MAX_GRID);  // about four elements a thread
     cdseg_route_rec(CDSEG_RK_SK_MERGE_SCALAR, 0, c, 1, 0, 0, CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, 0);
-    hipLaunchKernelGGL(sk_merge_scalar_kernel, dim3((unsigned)blocks), dim3(SK_THREADS), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(sk_merge_scalar_kernel, dim3(grid), dim3(SK_THREADS), 0, (hipStream_t)stream, p);
   }
   CDSEG_CHECK_LAUNCH();
   return CDSEG_OK;

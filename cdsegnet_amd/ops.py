@@ -1882,12 +1882,18 @@ def gelu_bwd_cast(u, dg, variant=None):
 BN_WIDTHS = range(16, 513, 16)  # channel counts of the kernels of csrc/norm.hip
 
 
-class BnPartition(tuple):
-    """(rows_per_block, blocks) of the two BatchNorm reduction passes: block b covers rows b * rows_per_block .. (the last may be
-    shorter); the block partials are added by ascending block index."""
+class RowPartition(tuple):
+    """(rows_per_block, blocks) of a fixed-order column sum (csrc/colsum.h: the two BatchNorm reduction passes, the skip
+    statistics): block b covers rows b * rows_per_block .. (the last may be shorter); the order in which the block partials are
+    added is the op's (BatchNorm: ascending block index; skip statistics: 16 segments of consecutive blocks)."""
     __slots__ = ()
     rows_per_block = property(lambda self: self[0])
     blocks = property(lambda self: self[1])
+
+
+def _sums_ws(ws_bytes, rows, c, device):
+    """The block partials of a fixed-order column sum, sized by the op's cdseg_*_ws_bytes (never empty: the pointer is checked)."""
+    return _scratch(max(16, ws_bytes(int(rows), int(c))), device)
 
 
 def bn_partition(m, c):
@@ -1895,7 +1901,7 @@ def bn_partition(m, c):
     code, no GPU needed, the same in both builds)."""
     rows, blocks = ctypes.c_long(0), ctypes.c_int(0)
     check(_lib.load().cdseg_bn_partition(int(m), int(c), ctypes.byref(rows), ctypes.byref(blocks)), "bn_partition")
-    return BnPartition((rows.value, blocks.value))
+    return RowPartition((rows.value, blocks.value))
 
 
 def _bn_rows(what, *ts):
@@ -1913,10 +1919,6 @@ def _a16(t):
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
-def _bn_ws(lib, m, c, device):
-    return _scratch(max(16, lib.cdseg_bn_ws_bytes(int(m), int(c))), device)
-
-
 def bn_stats(x):
     """Per-channel statistics of fp32 x (m, c): a (2 c + 1) fp64 device tensor [sum x, sum x^2, m], summed in fp64 in an order
     fixed by (m, c) (cdseg_bn_stats).  Buffers of several row shards merge by plain addition; m = 0 gives zeros."""
@@ -1927,7 +1929,7 @@ def bn_stats(x):
         return torch.zeros(2 * c + 1, dtype=torch.float64, device=x.device)
     lib = _lib.load()
     stats = torch.empty(2 * c + 1, dtype=torch.float64, device=x.device)
-    ws = _bn_ws(lib, m, c, x.device)
+    ws = _sums_ws(lib.cdseg_bn_ws_bytes, m, c, x.device)
     check(lib.cdseg_bn_stats(_ptr(x), x.stride(0), m, c, _ptr(stats), _ptr(ws), ws.numel(), _stream()), "bn_stats")
     return stats
 
@@ -1974,7 +1976,7 @@ def bn_gelu_bwd(x, dy, mean, invstd, gamma, beta, count, hook=None, out=None):
         gsums = torch.zeros(2 * c, dtype=torch.float64, device=x.device)
     else:
         gsums = torch.empty(2 * c, dtype=torch.float64, device=x.device)
-        ws = _bn_ws(lib, m, c, x.device)
+        ws = _sums_ws(lib.cdseg_bn_ws_bytes, m, c, x.device)
         check(lib.cdseg_bn_gelu_bwd_sums(_ptr(x), x.stride(0), _ptr(dy), dy.stride(0), m, c, _ptr(mean), _ptr(invstd), _ptr(gamma),
                                          _ptr(beta), _ptr(gsums), _ptr(ws), ws.numel(), _stream()), "bn_gelu_bwd (sums)")
     total = gsums if hook is None else hook(gsums).contiguous()
@@ -2022,7 +2024,7 @@ def fuse_gate_bwd(dy, s, a, alpha, gamma, m=None):
         return ds, da, torch.zeros(2 * c, dtype=torch.float64, device=s.device)
     lib = _lib.load()
     sums = torch.empty(2 * c, dtype=torch.float64, device=s.device)
-    ws = _scratch(max(16, lib.cdseg_fuse_gate_ws_bytes(rows, c)), s.device)
+    ws = _sums_ws(lib.cdseg_fuse_gate_ws_bytes, rows, c, s.device)
     check(lib.cdseg_fuse_gate_bwd(_ptr(dy), _ptr(s), _ptr(a), _ptr(_fg_mask("fuse_gate_bwd", m, rows)), _ptr(_a16(alpha)),
                                   _ptr(_a16(gamma)), _ptr(ds), _ptr(da), _ptr(sums), rows, c, _ptr(ws), ws.numel(), _stream()),
           "fuse_gate_bwd")
@@ -2044,7 +2046,7 @@ def skip_partition(n, c):
     """(rows_per_chunk, chunks) of `skip_stats` for an (n, c) feature: host only, a function of the shape."""
     rpc, chunks = ctypes.c_long(0), ctypes.c_int(0)
     check(_lib.load().cdseg_skip_partition(int(n), int(c), ctypes.byref(rpc), ctypes.byref(chunks)), "skip_partition")
-    return rpc.value, chunks.value
+    return RowPartition((rpc.value, chunks.value))
 
 
 def skip_stats(x, ref_of_row=None, n_total=None):
@@ -2060,7 +2062,7 @@ def skip_stats(x, ref_of_row=None, n_total=None):
         return torch.zeros(3 * c, dtype=torch.float64, device=x.device)
     lib = _lib.load()
     stats = torch.empty(3 * c, dtype=torch.float64, device=x.device)
-    ws = _scratch(max(16, lib.cdseg_skip_stats_ws_bytes(n, c)), x.device)
+    ws = _sums_ws(lib.cdseg_skip_stats_ws_bytes, n, c, x.device)
     check(lib.cdseg_skip_stats(_ptr(x), dt(x), x.stride(0), n, c, _ptr(_sk_map("skip_stats", ref_of_row, n)), n_total, _ptr(stats),
                                _ptr(ws), ws.numel(), _stream()), "skip_stats")
     return stats

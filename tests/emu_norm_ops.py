@@ -8,7 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from cdsegnet_amd._lib import CdsegError
-from tests import emu_rows_ops
+from tests import colsum_rule, emu_rows_ops
 
 
 def __getattr__(name):  # every op this file does not define
@@ -16,13 +16,11 @@ def __getattr__(name):  # every op this file does not define
 
 
 def bn_partition(m, c):
-    """The launch rule of csrc/norm.hip restated: at most 256 blocks of at least 256 rows, a multiple of 64 beyond that; like the
-    library, only for the kernels' widths (multiples of 16 up to 512) and m >= 0."""
+    """The launch rule of csrc/norm.hip restated (tests/colsum_rule.py: at most 256 blocks of at least 256 rows, a multiple of 64
+    beyond that); like the library, only for the kernels' widths (multiples of 16 up to 512) and m >= 0."""
     if m < 0 or c < 16 or c > 512 or c % 16:
         raise CdsegError(f"bn_partition failed: no kernel for ({m}, {c})")
-    rpb = -(-m // 256)
-    rpb = 256 if rpb < 256 else -(-rpb // 64) * 64
-    return rpb, (-(-m // rpb) if m > 0 else 0)
+    return colsum_rule.partition(m, colsum_rule.MIN_ROWS_BN)
 
 
 def bn_stats(x):

@@ -1,6 +1,8 @@
 """GPU: the Feature Fusion Module options - the gate kernels of csrc/fusion.hip against fp64, and the learned fusion scales and
 bidirectional fusion end to end (inference engine, training graph) against the reference's recordings
 (tools/make_fusion_golden.py -> tests/golden/fusion_*.npz).  Host logic on the CPU: tests/test_cpu_fusion.py."""
+import math
+
 import numpy as np
 import pytest
 import torch
@@ -9,7 +11,7 @@ import cdsegnet_amd.models  # noqa: F401
 import cdsegnet_amd.ops as O
 from cdsegnet_amd import _lib
 from cdsegnet_amd.optim import FusedAdamW
-from tests import guard_bands as GB
+from tests import colsum_rule, guard_bands as GB
 from tests.fusion_helpers import INFER_TAGS, ddim_draws, infer_model, ssi_draws, train_draws, train_model
 from tests.helpers import fixture_input, load_fixture
 
@@ -85,7 +87,9 @@ def test_gate_kernels_many_rows(rows, c):
     s, a, dy, m, alpha, gamma = _operands(rows, c, True, rows + c)
     d = lambda t: t.double()  # noqa: E731
     m2 = m[:, None]
-    assert _lib.load().cdseg_fuse_gate_ws_bytes(rows, c) == -(-rows // (128 if rows == 20000 else 192)) * 2 * c * 8
+    rpb, blocks = colsum_rule.partition(rows, colsum_rule.MIN_ROWS_SWEEP)
+    assert rpb == (128 if rows == 20000 else 192) and blocks == -(-rows // rpb)
+    assert _lib.load().cdseg_fuse_gate_ws_bytes(rows, c) == blocks * 2 * c * 8
     _within(f"fwd {rows}x{c}", O.fuse_gate_fwd(s, a, alpha, gamma, m), alpha * s + gamma * (m2 * a), d(alpha) * d(s) + d(gamma) * (d(m2) * d(a)))
     ds, da, sums = O.fuse_gate_bwd(dy, s, a, alpha, gamma, m)
     _within(f"bwd ds {rows}x{c}", ds, alpha * dy, d(alpha) * d(dy))
@@ -94,6 +98,34 @@ def test_gate_kernels_many_rows(rows, c):
     _within(f"bwd sum dy s {rows}x{c}", sums[c:], (dy * s).sum(0), (d(dy) * d(s)).sum(0))
     r = O.fuse_gate_bwd(dy, s, a, alpha, gamma, m)
     assert GB.same_bits(ds, r[0]) and GB.same_bits(da, r[1]) and GB.same_bits(sums, r[2])
+
+
+def test_gate_sums_are_added_in_the_documented_order():
+    """s = 1, a = 0, alpha = gamma = 1: sums[c:] = sum_r dy, and dy is zero except four rows holding 2^60, 1, -2^60, 1, so in
+    fp64 the sum tells the order (a 1 added to 2^60 is lost).  Expected values: the order of csrc/colsum.h restated in
+    tests/colsum_rule.py (64-row blocks, R = 32 row slots at c = 32, one chain over the blocks), never the kernel's output.
+    (a) one row in each of blocks 0 .. 3: ((2^60 + 1) - 2^60) + 1 = 1.0; with the middle two swapped (2^60 - 2^60) + 1 + 1 = 2.0.
+    (b) inside one block, rows 0, 32, 1, 2: rows 0 and 32 are one thread's (slot 0: 2^60 + 1 = 2^60), then the slots ascending,
+    (2^60 - 2^60) + 1 = 1.0; a plain ascending-row sum would give 2.0."""
+    c, big = 32, 2.0 ** 60
+    lib = _lib.load()
+    s, a, one = torch.ones(300, c).cuda(), torch.zeros(300, c).cuda(), torch.ones(c).cuda()
+    assert lib.cdseg_fuse_gate_ws_bytes(300, c) == 5 * 2 * c * 8  # 5 blocks of 64 rows
+    block_rows = [64 * b + (17 * b + 5) % 64 for b in range(4)]
+    for rows, where, vals, want in ((300, block_rows, [big, 1.0, -big, 1.0], 1.0), (300, block_rows, [big, -big, 1.0, 1.0], 2.0),
+                                    (64, [0, 32, 1, 2], [big, 1.0, -big, 1.0], 1.0)):
+        column = [0.0] * rows
+        for r, v in zip(where, vals):
+            column[r] = v
+        restated = colsum_rule.ordered_sum(column, c, colsum_rule.MIN_ROWS_SWEEP, 1)
+        assert restated == want and math.fsum(column) == 2.0  # (the exact sum is 2 in every placement)
+        dy = torch.tensor(column, dtype=torch.float32)[:, None].repeat(1, c).cuda()
+        with O.record_routes() as rr:
+            _, _, sums = O.fuse_gate_bwd(dy, s[:rows], a[:rows], one, one)
+        assert rr.kernels() == ["fg_bwd_kernel"], rr.routes
+        print(f"[measure] gate sums {rows}x{c} rows {where}: {sums[c:].tolist()[:2]} .. (restated {restated})")
+        assert torch.equal(sums[c:], torch.full((c,), restated, dtype=torch.float64, device="cuda")), sums[c:]
+        assert torch.equal(sums[:c], torch.zeros(c, dtype=torch.float64, device="cuda"))
 
 
 @pytest.mark.parametrize("rows,c,shift", [(3, 30, 0), (65, 1, 0), (130, 511, 0), (257, 32, 1), (70, 36, 3)])

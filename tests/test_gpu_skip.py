@@ -13,7 +13,7 @@ import cdsegnet_amd.ops as O
 import cdsegnet_amd.train_graph as tg
 from cdsegnet_amd import _lib
 from cdsegnet_amd.optim import FusedAdamW
-from tests import guard_bands as GB, skip_restatement as R
+from tests import colsum_rule, guard_bands as GB, skip_restatement as R
 from tests.helpers import fixture_input, load_fixture
 from tests.skip_helpers import INFER, ddim_draws, fixture_model, ssi_draws, train_draws
 
@@ -122,6 +122,42 @@ def test_sixteen_bit_stats_read_the_stored_values():
         with _lib.use(variant):
             x, _, _, ref = _case(777, 128, 3, lp)
             assert GB.same_bits(O.skip_stats(x.cuda(), ref.cuda()), O.skip_stats(x.float().cuda(), ref.cuda()))
+
+
+def test_stats_are_added_in_sixteen_segments_of_chunks():
+    """S0 = stats[:c] of a feature that is zero except four rows holding 2^60, -2^60, 1, 1: in fp64 a 1 added to +-2^60 is lost,
+    so the sum tells the order.  Expected values: the order of csrc/colsum.h restated in tests/colsum_rule.py (64-row chunks,
+    R = 32 row slots at c = 32, 16 segments of consecutive chunks), never the kernel's output.  n = 2100: 33 chunks, segments
+    of 3.  Chunks 0, 2, 3, 4 holding 2^60, 1, -2^60, 1: segment 0 = 2^60 (+ 1 lost), segment 1 = -2^60 (+ 1 lost) -> 0.0, where
+    one ascending chain over the chunks gives 1.0.  Chunks 0, 3, 5, 6 holding 2^60, -2^60, 1, 1: 2^60, -2^60 (+ 1 lost), 1 ->
+    1.0 (a chain: 2.0).  n = 64, rows 0, 32, 1, 2 holding 2^60, 1, -2^60, 1: rows 0 and 32 are one thread's, the row slots of a
+    chunk ascending -> 1.0 (ascending rows: 2.0).  The first two also on the 16-bit vector path of the bf16 build, where
+    2^60 and 1 are exact; IEEE half spans 2^-24 .. 2^15 only, so no two of its values lose one another in an fp64 sum and
+    the f16 build has no such leg."""
+    c, big = 32, 2.0 ** 60
+    assert tuple(O.skip_partition(2100, c)) == (64, 33)
+
+    def row(chunk):
+        return 64 * chunk + (17 * chunk + 5) % 64
+
+    cases = ((2100, [row(b) for b in (0, 2, 3, 4)], [big, 1.0, -big, 1.0], 0.0, 1.0),
+             (2100, [row(b) for b in (0, 3, 5, 6)], [big, -big, 1.0, 1.0], 1.0, 2.0),
+             (64, [0, 32, 1, 2], [big, 1.0, -big, 1.0], 1.0, 1.0))
+    for n, where, vals, want, chain in cases:
+        column = [0.0] * n
+        for r, v in zip(where, vals):
+            column[r] = v
+        restated = colsum_rule.ordered_sum(column, c, colsum_rule.MIN_ROWS_SWEEP, 16)
+        assert restated == want and colsum_rule.ordered_sum(column, c, colsum_rule.MIN_ROWS_SWEEP, 1) == chain
+        x = torch.tensor(column, dtype=torch.float32)[:, None].repeat(1, c)
+        legs = [(v, None) for v in _lib.VARIANTS] + ([("bf16", torch.bfloat16)] if n == 2100 else [])
+        for variant, lp in legs:
+            with _lib.use(variant):
+                with O.record_routes() as rr:
+                    st = O.skip_stats((x if lp is None else x.to(lp)).cuda())
+            assert rr.kernels() == [f"sk_stats_kernel<{'f32' if lp is None else 'b16'}>"], rr.routes
+            print(f"[measure] skip S0 {n}x{c} rows {where} {variant} {lp}: {st[:2].tolist()} .. (restated {restated})")
+            assert torch.equal(st[:c], torch.full((c,), restated, dtype=torch.float64, device="cuda")), (n, where, variant, lp, st[:c])
 
 
 def test_row_map_permutes_and_backward_is_the_transpose():
