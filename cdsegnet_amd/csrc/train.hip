@@ -1014,6 +1014,8 @@ static int attention_bwd_launch(const void* q, const void* k, const void* v, int
   // 16-byte operand loads (float4 / eight 16-bit values): 16-byte aligned rows
   const int op_mask = dtype == CDSEG_F32 ? 3 : 7;
   if (((ldq | ldk | ldv | lddo) & op_mask) || ((lddq | lddk | lddv) & 3)) return CDSEG_ERR_ARG;
+  const long row = (long)num_heads * 16;  // a row is num_heads heads of 16 channels: a shorter stride overlaps the next row
+  if (ldq < row || ldk < row || ldv < row || lddo < row || lddq < row || lddk < row || lddv < row) return CDSEG_ERR_ARG;
   if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) & 15) != 0)
     return CDSEG_ERR_ARG;
   if (!ws || ws_bytes < cdseg_attention_bwd_ws_bytes(num_slots, num_heads)) return CDSEG_ERR_WORKSPACE;
@@ -1129,11 +1131,16 @@ static bool wgrad_args_ok(const float* x, const int32_t* xidx, const float* dy, 
   return x && dy && dw && f32_aligned(x, xidx, dy, dw, db);
 }
 
+// A row stride shorter than the row makes consecutive rows overlap: for an input a wrong sum, for an output (dx, dw) adds
+// onto the neighbouring rows' elements.  Every entry point below refuses it before any launch (include/cdseg.h).
+static bool wgrad_lds_ok(int ldx, int k, int lddy, int n, int lddw) { return ldx >= k && lddy >= n && lddw >= k; }
+
 extern "C" int cdseg_layernorm_bwd(const float* x, int ldx, const float* gamma, float eps, const float* dy, int lddy, float* dx,
                                    int lddx, int accumulate, float* dgamma, float* dbeta, long m, int c, void* stream) {
   if (m <= 0) return CDSEG_OK;
   if (c <= 0 || !x || !gamma || !dy || !dx) return CDSEG_ERR_ARG;
   if (!f32_aligned(x, gamma, dy, dx, dgamma, dbeta)) return CDSEG_ERR_ARG;
+  if (ldx < c || lddy < c || lddx < c) return CDSEG_ERR_ARG;
   cdseg_route_rec(CDSEG_RK_LN_BWD, 4 * LNB_ROWS, c, 1, 0, 0, CDSEG_F32 << CDSEG_ROUTE_F_CT_SHIFT, 0);
   hipLaunchKernelGGL(layernorm_bwd_kernel, dim3((unsigned)cdiv(m, 4 * LNB_ROWS)), dim3(256), 0, (hipStream_t)stream, x, ldx, gamma, eps, dy,
                      lddy, dx, lddx, accumulate, dgamma, dbeta, m, c);
@@ -1181,7 +1188,7 @@ static int launch_wgrad(WgradP p, int noff, hipStream_t stream, float* ws = null
 extern "C" int cdseg_linear_wgrad(const float* x, int ldx, const int32_t* xidx, const float* dy, int lddy, long m, int k, int n,
                                   float* dw, int lddw, float* db, void* stream) {
   if (m <= 0 || n <= 0 || k <= 0) return CDSEG_OK;
-  if (!wgrad_args_ok(x, xidx, dy, dw, db)) return CDSEG_ERR_ARG;
+  if (!wgrad_args_ok(x, xidx, dy, dw, db) || !wgrad_lds_ok(ldx, k, lddy, n, lddw)) return CDSEG_ERR_ARG;
   if ((n & 15) || (k & 15)) return CDSEG_ERR_UNSUPPORTED;
   WgradP p;
   p.dy = dy; p.x = x; p.xidx = xidx; p.dw = dw; p.db = db; p.M = m; p.N = n; p.K = k; p.lddy = lddy; p.ldx = ldx; p.lddw = lddw;
@@ -1192,7 +1199,7 @@ extern "C" int cdseg_linear_wgrad(const float* x, int ldx, const int32_t* xidx, 
 extern "C" int cdseg_conv_wgrad(const float* x, int ldx, const int32_t* nbr_kmajor, int kvol, const float* dy, int lddy, long m,
                                 int cin, int cout, float* dw, float* db, void* stream) {
   if (m <= 0 || kvol <= 0 || cin <= 0 || cout <= 0) return CDSEG_OK;
-  if (!nbr_kmajor || !wgrad_args_ok(x, nbr_kmajor, dy, dw, db)) return CDSEG_ERR_ARG;
+  if (!nbr_kmajor || !wgrad_args_ok(x, nbr_kmajor, dy, dw, db) || !wgrad_lds_ok(ldx, cin, lddy, cout, cin)) return CDSEG_ERR_ARG;
   if ((cin & 15) || (cout & 15)) return CDSEG_ERR_UNSUPPORTED;
   WgradP p;
   p.dy = dy; p.x = x; p.xidx = nbr_kmajor; p.dw = dw; p.db = db; p.M = m; p.N = cout; p.K = cin; p.lddy = lddy; p.ldx = ldx;
@@ -1248,7 +1255,7 @@ static bool wgrad16_args_ok(const void* x, int ldx, const void* xidx, const void
 extern "C" int cdseg_linear_wgrad16(const void* x, int ldx, const int32_t* xidx, const void* dy, int lddy, long m, int k, int n,
                                     float* dw, int lddw, float* db, void* stream) {
   if (m <= 0 || n <= 0 || k <= 0) return CDSEG_OK;
-  if (!wgrad16_args_ok(x, ldx, xidx, dy, lddy, dw, db)) return CDSEG_ERR_ARG;
+  if (!wgrad16_args_ok(x, ldx, xidx, dy, lddy, dw, db) || !wgrad_lds_ok(ldx, k, lddy, n, lddw)) return CDSEG_ERR_ARG;
   if ((n & 15) || (k & 15)) return CDSEG_ERR_UNSUPPORTED;
   Wgrad16P p;
   p.dy = (const bf16_t*)dy; p.x = (const bf16_t*)x; p.xidx = xidx; p.dw = dw; p.db = db; p.M = m; p.N = n; p.K = k; p.lddy = lddy;
@@ -1259,7 +1266,8 @@ extern "C" int cdseg_linear_wgrad16(const void* x, int ldx, const int32_t* xidx,
 extern "C" int cdseg_conv_wgrad16(const void* x, int ldx, const int32_t* nbr_kmajor, int kvol, const void* dy, int lddy, long m,
                                   int cin, int cout, float* dw, float* db, void* stream) {
   if (m <= 0 || kvol <= 0) return CDSEG_OK;
-  if (!nbr_kmajor || !wgrad16_args_ok(x, ldx, nbr_kmajor, dy, lddy, dw, db)) return CDSEG_ERR_ARG;
+  if (!nbr_kmajor || !wgrad16_args_ok(x, ldx, nbr_kmajor, dy, lddy, dw, db) || !wgrad_lds_ok(ldx, cin, lddy, cout, cin))
+    return CDSEG_ERR_ARG;
   if ((cin & 15) || (cout & 15)) return CDSEG_ERR_UNSUPPORTED;
   Wgrad16P p;
   p.dy = (const bf16_t*)dy; p.x = (const bf16_t*)x; p.xidx = nbr_kmajor; p.dw = dw; p.db = db; p.M = m; p.N = cout; p.K = cin;
@@ -1295,7 +1303,7 @@ static int wgrad_det(const void* x, int ldx, const int32_t* xidx, int kvol, cons
   } else if (!x || !dy || !dw || ((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dw | (uintptr_t)db | (uintptr_t)xidx) & 3) != 0)) {
     return CDSEG_ERR_ARG;
   }
-  if (((uintptr_t)ws & 15) != 0) return CDSEG_ERR_ARG;
+  if (((uintptr_t)ws & 15) != 0 || !wgrad_lds_ok(ldx, k, lddy, n, lddw)) return CDSEG_ERR_ARG;
   if ((n & 15) || (k & 15)) return CDSEG_ERR_UNSUPPORTED;
   long rows = 0;
   int splits = 0;
@@ -1334,6 +1342,7 @@ extern "C" int cdseg_layernorm_bwd_det(const float* x, int ldx, const float* gam
                                        void* stream) {
   if (m <= 0 || c <= 0) return CDSEG_OK;
   if (!x || !gamma || !dy || !dx) return CDSEG_ERR_ARG;
+  if (!f32_aligned(x, gamma, dy, dx, dgamma, dbeta) || ldx < c || lddy < c || lddx < c) return CDSEG_ERR_ARG;
   if (c > LNB_MAXC) return CDSEG_ERR_UNSUPPORTED;  // (the default form's per-element-atomic path: no fixed order)
   if (((uintptr_t)ws & 3) != 0) return CDSEG_ERR_ARG;
   if (!ws || ws_bytes < cdseg_layernorm_bwd_det_ws_bytes(m, c)) return CDSEG_ERR_WORKSPACE;
@@ -1350,7 +1359,7 @@ extern "C" int cdseg_layernorm_bwd_det(const float* x, int ldx, const float* gam
 
 extern "C" int cdseg_segment_sum(const float* src, int ld, const int32_t* seg_start, long m, int c, float* out, int ldo, void* stream) {
   if (m <= 0 || c <= 0) return CDSEG_OK;
-  if (!src || !seg_start || !out) return CDSEG_ERR_ARG;
+  if (!src || !seg_start || !out || !f32_aligned(src, out) || ((uintptr_t)seg_start & 3) || ld < c || ldo < c) return CDSEG_ERR_ARG;
   const int cw = c <= 16 ? 16 : c <= 32 ? 32 : 64;
   const long rows_per_block = 4 * (64 / cw);
   hipLaunchKernelGGL(segment_sum_kernel, dim3((unsigned)cdiv(m, rows_per_block)), dim3(256), 0, (hipStream_t)stream, src, ld, seg_start, m,

@@ -797,8 +797,11 @@ int cdseg_plan_finish(const cdseg_plan_spec* spec, const cdseg_plan_finish_io* i
  *                 rounded to the 16-bit type as MFMA operands only; all accumulators are fp32.  dout is not clamped and dS
  *                 is converted without saturation (half build): a gradient beyond the 16-bit range arrives as inf / NaN.
  *   Alignment (CDSEG_ERR_ARG otherwise): every pointer 16-byte aligned; ldq, ldk, ldv, lddo (in elements) multiples of 4
- *   (CDSEG_F32) or of 8 (CDSEG_BF16), i.e. 16-byte rows; lddq, lddk, lddv multiples of 4.
+ *   (CDSEG_F32) or of 8 (CDSEG_BF16), i.e. 16-byte rows; lddq, lddk, lddv multiples of 4; every one of the seven strides
+ *   at least the row, num_heads * 16 elements.
  * cdseg_layernorm_bwd: dx (=, or += when accumulate) for y = LayerNorm(x) * gamma + beta; optional dgamma / dbeta (+=).
+ *   CDSEG_ERR_ARG: a NULL x, gamma, dy or dx, a pointer that is not 4-byte aligned, or ldx, lddy or lddx < c (scalar
+ *   accesses: any stride from c on, odd ones included).
  * cdseg_gelu_bwd: dx = dy * d/du GELU(u) on the pre-activation u (erf form, torch.nn.GELU()).
  * cdseg_linear_wgrad: dw[n][k] += sum_m dy[m][n] * x[row(m)][k] and (db != NULL) db[n] += sum_m dy[m][n], fp32; row(m) = m,
  *   or xidx[m] with -1 = skip: ONE kernel offset of a submanifold conv (xidx = that offset's row of the offset-major kernel
@@ -806,7 +809,10 @@ int cdseg_plan_finish(const cdseg_plan_spec* spec, const cdseg_plan_finish_io* i
  *   gradient, ptv3.py:356-362).  n, k multiples of 16.  Accumulates (the caller zeroes dw / db); partial sums are added
  *   with fp32 atomics (summation order not fixed).  The DATA gradient of a Linear / of the conv needs no entry point of
  *   its own: it is cdseg_gemm on the transposed weight / on the mirrored, transposed kernel (W'[ci][o][co] = W[co][26-o][ci])
- *   with the same kernel map. */
+ *   with the same kernel map.
+ *   CDSEG_ERR_ARG: a NULL x, dy or dw, a pointer that is not 4-byte aligned, or a stride shorter than its row: ldx < k,
+ *   lddy < n, lddw < k (cdseg_conv_wgrad: ldx < cin, lddy < cout; its dw is contiguous).  Any stride from the row length on
+ *   is taken, odd ones included (scalar accesses). */
 size_t cdseg_attention_bwd_ws_bytes(long num_slots, int num_heads);
 int cdseg_attention_bwd(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const int32_t* q_gidx,
                         const int32_t* kv_gidx, const int32_t* widx, const int32_t* patch_start, int num_patches,
@@ -829,7 +835,8 @@ int cdseg_conv_wgrad(const float* x, int ldx, const int32_t* nbr_kmajor, int kvo
  * without saturation) arrives in the dw rows and the db entry of its column, where a GradScaler finds it.
  * Row chunks staged row-major in LDS, both operands read with ds_read_b64_tr_b16; a chunk of 64 rows in which the offset
  * has no live neighbour is skipped.
- *   CDSEG_ERR_ARG: a pointer that is not 16-byte aligned, or ldx / lddy (in elements) not a multiple of 8.
+ *   CDSEG_ERR_ARG: a pointer that is not 16-byte aligned, ldx / lddy (in elements) not a multiple of 8, or a stride
+ *   shorter than its row (ldx < k, lddy < n, lddw < k; lddw is in fp32 elements and need not be a multiple of anything).
  *   CDSEG_ERR_UNSUPPORTED: n, k (cin, cout) not multiples of 16 (a 16-wide shape runs as a zero-padded 32-wide tile).
  *   m <= 0: CDSEG_OK, nothing written. */
 int cdseg_linear_wgrad16(const void* x, int ldx, const int32_t* xidx, const void* dy, int lddy, long m, int k, int n, float* dw,
@@ -903,10 +910,14 @@ int cdseg_dropout(const float* x, int ldx, float* y, int ldy, long m, int c, dou
  *                     CDSEG_ERR_UNSUPPORTED (the default form handles them with per-element atomics).
  *   segment sum       out[j] = sum_i src[i], i = seg_start[j] .. seg_start[j + 1] - 1 ascending (out is overwritten; an empty
  *                     run gives 0): the backward of the unpooling gather child[cluster], whose children are contiguous.
+ *                     CDSEG_ERR_ARG: a NULL src, seg_start or out, src / out / seg_start not 4-byte aligned, ld < c or
+ *                     ldo < c (scalar accesses: any stride from c on, odd ones included).
  * No block waits for another; the library allocates nothing.  Status codes, checked before any launch:
  *   CDSEG_ERR_WORKSPACE    ws NULL or ws_bytes below the matching _ws_bytes query.
  *   CDSEG_ERR_ARG          CDSEG_BF16: as the 16-bit forms above (16-byte aligned pointers, ldx / lddy multiples of 8);
- *                          CDSEG_F32: a NULL or not 4-byte aligned operand; ws not 16-byte aligned.
+ *                          CDSEG_F32: a NULL or not 4-byte aligned operand; ws not 16-byte aligned (LayerNorm: 4-byte);
+ *                          a stride shorter than its row, as in the default forms (ldx < k, lddy < n, lddw < k; LayerNorm:
+ *                          ldx, lddy, lddx < c).
  *   CDSEG_ERR_UNSUPPORTED  another dtype; n, k (cin, cout) not multiples of 16.
  * The partition query is host only: the launch rule is a function of (m, n, k, kvol, dtype) alone (kvol = 1: the Linear form)
  * and never asks the device.  It returns the rows per split (the last split may be shorter) and the number of splits. */

@@ -12,6 +12,8 @@ whether its result depends on memory that was never part of the call:
                                   slack ops.workspace() has always granted, so whatever worked before lands in the band.
   poisoned_input(t)               t copied into a larger buffer whose guard rows and columns are NaN (floating-point payload
                                   operands ONLY; index operands get guard_index()).
+  banded_vector(n, dtype, ...)    the same for a 1-D vector (gamma, mean, db, statistics, the optimizer's flat tensors): `guard`
+  poisoned_vector(t)              elements in front and behind, the alignment class (data_ptr() % 16) chosen by the caller.
   guard_index(idx, none=...)      an index array whose guard entries stay valid for the call: -1 where the ABI defines it as
                                   "none", otherwise a copy of the last real entry.  An over-read never becomes a wild access.
 
@@ -80,8 +82,8 @@ def _fill_bits(fill, dtype):
 
 def banded(shape, dtype, *, rows=256, cols=8, fill, align=0, ld=None, device="cuda", name="out"):
     """-> (inner view of `shape` (n, c), Band).  Every element, inner ones included, starts as `fill`.
-    align: data_ptr() % 16 of the inner view (0, or 8 = 8-byte but not 16-byte aligned); ld: row stride in elements (default
-    c + 2 * cols rounded up so that every row keeps the alignment class)."""
+    align: data_ptr() % 16 of the inner view (0, or 8 = 8-byte but not 16-byte aligned; 4-byte elements also 4 or 12);
+    ld: row stride in elements (default c + 2 * cols rounded up so that every row keeps the alignment class)."""
     n, c = shape
     es = torch.empty(0, dtype=dtype).element_size()
     per16 = 16 // es
@@ -104,6 +106,32 @@ def poisoned_input(t, rows=256, *, cols=8, align=0, ld=None, name="in"):
     assert t.is_floating_point() and t.dim() == 2
     inner, band = banded(tuple(t.shape), t.dtype, rows=rows, cols=cols, fill=float("nan"), align=align, ld=ld, device=t.device,
                          name=name)
+    inner.copy_(t)
+    return inner, band
+
+
+def banded_vector(n, dtype, *, fill, guard=256, align=0, device="cuda", name="vec"):
+    """-> (1-D inner view of n elements, Band): `guard` elements (at least; whole 16-byte groups) holding `fill` in front and
+    behind, the inner view included.  align: data_ptr() % 16 of the inner view, any multiple of the element size below 16
+    (fp32: 0, 4, 8 or 12 - the alignment class the caller's entry point is to be shown).  The Band is that of a one-row
+    buffer: a damaged element is reported in its 'left' (in front) or 'right' (behind) guard with inner column = its index."""
+    es = torch.empty(0, dtype=dtype).element_size()
+    assert 0 <= align < 16 and align % es == 0, f"align = {align} is no alignment class of {es}-byte elements"
+    per16 = 16 // es
+    c0 = -(-guard // per16) * per16 + align // es
+    total = c0 + n + guard + per16
+    flat = _aligned_base(total, dtype, device, 0)
+    bits(flat).fill_(_fill_bits(fill, dtype))
+    buf = flat.view(1, total)
+    inner = buf[0, c0:c0 + n]
+    assert inner.data_ptr() % 16 == align and total - c0 - n >= guard
+    return inner, Band(buf, 0, 1, c0, n, _fill_bits(fill, dtype), name)
+
+
+def poisoned_vector(t, *, guard=256, align=0, name="vec"):
+    """-> (1-D inner view holding t's values, Band whose guard elements are NaN).  Floating-point vectors only."""
+    assert t.is_floating_point() and t.dim() == 1
+    inner, band = banded_vector(t.numel(), t.dtype, fill=float("nan"), guard=guard, align=align, device=t.device, name=name)
     inner.copy_(t)
     return inner, band
 

@@ -125,3 +125,52 @@ def test_guard_index_holds_valid_entries():
     inner2._base[0, 0] = 7
     with pytest.raises(AssertionError):
         check2()
+
+
+@pytest.mark.parametrize("dtype,align", [(torch.float32, 0), (torch.float32, 4), (torch.float32, 8), (torch.float32, 12),
+                                         (torch.float64, 0), (torch.float64, 8), (torch.bfloat16, 2), (torch.float16, 8)])
+@pytest.mark.parametrize("n", [1, 5, 4096])
+def test_banded_vector_has_the_alignment_class_asked_for_and_reports_both_sides(dtype, align, n):
+    inner, band = GB.banded_vector(n, dtype, fill=-3.0, align=align, device="cpu")
+    assert inner.dim() == 1 and inner.numel() == n and inner.is_contiguous() and inner.data_ptr() % 16 == align
+    assert band.region("left").numel() >= 256 and band.region("right").numel() >= 256
+    assert band.region("front").numel() == 0 and band.region("behind").numel() == 0
+    inner.copy_(torch.randn(n).to(dtype))  # every element, the first and the last included
+    band.check()
+    c0 = band.c0
+    band.buf[0, c0 - 1] = 1.0
+    assert band.damaged() == (0, c0 - 1, "left", 1)
+    with pytest.raises(AssertionError, match="inner \\(row 0, column -1\\), in the 'left' guard"):
+        band.check()
+    band.buf[0, c0 - 1] = -3.0
+    band.buf[0, c0 + n] = 1.0
+    assert band.damaged() == (0, c0 + n, "right", 1)
+    with pytest.raises(AssertionError, match=f"inner \\(row 0, column {n}\\), in the 'right' guard"):
+        band.check()
+
+
+def test_banded_vector_refuses_an_alignment_the_element_size_cannot_have():
+    for dtype, align in ((torch.float32, 2), (torch.float64, 4), (torch.float32, 16)):
+        with pytest.raises(AssertionError):
+            GB.banded_vector(8, dtype, fill=0.0, align=align, device="cpu")
+
+
+def test_poisoned_vector_keeps_the_values_between_nan_guards():
+    t = torch.randn(37, dtype=torch.float64)
+    inner, band = GB.poisoned_vector(t, align=8)
+    assert GB.same_bits(inner, t) and inner.data_ptr() % 16 == 8
+    assert bool(torch.isnan(band.region("left")).all()) and bool(torch.isnan(band.region("right")).all())
+    band.check()
+    with pytest.raises(AssertionError):
+        GB.poisoned_vector(torch.arange(4))  # index operands are never poisoned
+    with pytest.raises(AssertionError):
+        GB.poisoned_vector(torch.zeros(2, 2))
+
+
+def test_banded_admits_the_4_byte_alignment_class_of_fp32_with_an_odd_row_stride():
+    inner, band = GB.banded((5, 16), torch.float32, fill=2.0, cols=0, align=4, ld=17, device="cpu")
+    assert inner.data_ptr() % 16 == 4 and inner.stride(0) == 17 and band.c0 == 1
+    inner.zero_()
+    band.check()
+    band.buf[256 + 2, 0] = 0.0  # the one guard column in front of row 2 (= the element behind row 1)
+    assert band.damaged() == (258, 0, "left", 1)
